@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the ResShift sampling hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision POLICY] [--config NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision POLICY] [--config NAME] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1], the default): realsr_swinunet_realesrgan256, 64x64 -> 256x256, 15 diffusion steps,
 batch 32 per GPU, random-init weights, synthetic inputs already resident in HBM.  One "step" of this benchmark = one
@@ -16,6 +16,11 @@ them itself: it re-executes this file under torch.distributed.run with a free re
 ranks-share-a-GPU plumbing configuration.  Rank 0 packs the weights and the blob reaches the other ranks through ONE
 broadcast; every rank then processes its own batch (weak scaling, no data-path collective).  The line carries `n_gpus` =
 the world size of the process group, the per-rank images/sec, and the broadcast's bytes and time.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the timed path returned in its LAST timed step - the images of the batch, what
+a caller of `rs_sample` receives - to DIR/image.npy (float32, N x 3 x H x W).  Weights, inputs and noise are seeded, so the same arguments
+give the same inputs on every run and two builds can be compared output for output.  Above DUMP_BYTES, a fixed seeded sample of the
+elements is written instead, with their flat indices in DIR/image_index.npy (float64).
 
 Rank 0 prints ONE JSON line with the contract fields.  EVERYTHING at the top level of the line - `value`, `ms_per_step`, `dtype`,
 `roofline` (+ `per_kernel`, `groupnorm`, `traffic`), `cpu_baseline.gpu_vs_cpu_psnr_db` - describes ONE precision policy, the one
@@ -101,6 +106,32 @@ def policy_args(name: str, steps: int):
         k = int(name[5:] or 1)
         return ["fp32" if t < k else "fp16" for t in range(steps)], "fp16", "fp16"
     raise SystemExit(f"unknown precision policy {name}")
+
+
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: at most this many bytes in all
+DUMP_SEED = 20240601
+
+
+def dump_outputs(path: str, outputs: dict) -> dict:
+    """--dump-outputs: each tensor as <path>/<name>.npy in float32.  When they add up to more than DUMP_BYTES, each keeps a fixed seeded
+    sample of its elements (its share of the budget, index included) and its flat element indices go to <name>_index.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_BYTES - 2 * 4096 * len(arrays)   # (room for the .npy headers)
+    info = {"dir": path, "files": {}}
+    for name, a in arrays.items():
+        if total <= budget:
+            np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+            info["files"][name] = {"shape": list(a.shape), "sampled": False}
+            continue
+        k = min(a.size, int(budget * a.nbytes / total) // (a.itemsize + 8))
+        idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(a.size, size=k, replace=False))
+        np.save(os.path.join(path, f"{name}.npy"), a.reshape(-1)[idx])
+        np.save(os.path.join(path, f"{name}_index.npy"), idx.astype(np.float64))
+        info["files"][name] = {"shape": list(a.shape), "sampled": True, "elements": int(k)}
+    log(f"outputs of the last timed step written to {path}: {info['files']}")
+    return info
 
 
 _T0 = time.time()
@@ -225,6 +256,7 @@ def tiled_main(args):
             torch.cuda.synchronize()
             ts.append(time.perf_counter() - t0)
         assert tuple(out.shape) == (1, 3, sf * H, sf * W) and torch.isfinite(out).all() and out.abs().max().item() <= 1.0
+        last_out = out
         sec = float(np.median(ts[1:]))   # (the first call allocates the arena)
         res[bs] = {"chop_bs": bs, "seconds_per_image": round(sec, 4), "tiles_per_sec": round(ntiles / sec, 3),
                    "output_megapixels_per_sec": round(sf * H * sf * W / sec / 1e6, 3), "first_call_s": round(ts[0], 3),
@@ -232,12 +264,13 @@ def tiled_main(args):
         del smp
         torch.cuda.empty_cache()
     best = max(res.values(), key=lambda r: r["tiles_per_sec"])
+    dumped = dump_outputs(args.dump_outputs, {"image": last_out}) if args.dump_outputs else None
     print(json.dumps({"metric": "tiles/sec, tiled large-image path (ImageSpliterTh-equivalent on the GPU), 15 steps", "value": best["tiles_per_sec"],
                       "unit": "tiles/s", "n_gpus": 1, "steps": args.steps, "warmup": 1, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                       "dtype": f"{args.precision} policy", "data": "synthetic",
                       "config": {"workload": f"{cname}: one {H}x{W} LR image -> {sf * H}x{sf * W}, chop_size {chop}, stride {stride}, {ntiles} tiles",
                                  "precision_policy": args.precision},
-                      "by_chop_bs": list(res.values())}), flush=True)
+                      "by_chop_bs": list(res.values()), "dumped_outputs": dumped}), flush=True)
 
 
 def main():
@@ -263,7 +296,10 @@ def main():
     ap.add_argument("--tiled", default=None, metavar="HxW", help="time the tiled large-image path on one HxW LR image instead of the batch workload (one GPU)")
     ap.add_argument("--chop-size", type=int, default=128, help="--tiled: LR tile side (the reference's default for x4 models is 512)")
     ap.add_argument("--chop-bs", type=int, default=8, help="--tiled: tiles per sampler call of the batched leg (chop_bs = 1 is always timed too)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the images of the last timed step to DIR/image.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.tiled:
         if args.gpus != 1:
@@ -374,6 +410,7 @@ def main():
     value = world * B * args.steps / elapsed
     launches = eng.last_launch_count()
     log(f"timed region done ({args.precision}): {ms_per_step:.1f} ms/step, {value:.2f} img/s, {launches} kernel launches per step")
+    dumped = dump_outputs(args.dump_outputs, {"image": out}) if args.dump_outputs and rank == 0 else None
 
     # ---- N > 1: the OTHER reference policy (fp16 when the headline is parity, parity otherwise) timed across all ranks exactly like the
     # headline (barriers, max over ranks), so that the scaling curve exists for both.  Parity against the CPU oracle is an N = 1 matter.
@@ -716,7 +753,7 @@ def main():
                       "weight_broadcast_ms": round(1e3 * float(getattr(eng, "broadcast_s", 0.0)), 3)},
             "roofline": roofline, "cpu_baseline": cpu_baseline, "parity_vs_cpu_oracle": parity,
             "value_at_parity": value_at_parity, "value_fp16_unqualified": value_fp16, "other_policy_all_ranks": other_policy_all_ranks,
-            torch_key: torch_baseline,
+            torch_key: torch_baseline, "dumped_outputs": dumped,
         }
         line.update(extra)
         print(json.dumps(line), flush=True)

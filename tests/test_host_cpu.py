@@ -14,6 +14,9 @@ import torch.multiprocessing as mp
 import helpers as H
 
 ROOT = H.ROOT
+# the child processes of the GPU-less tests below see no HIP device, also when the suite runs on a GPU machine (an invalid device index ends
+# HIP's list of visible devices)
+NO_GPU = {"HIP_VISIBLE_DEVICES": "-1"}
 
 
 def test_c_abi_library_loads_and_exports_every_declared_symbol():
@@ -189,7 +192,9 @@ def _worker(rank, world, port, q):
     dist.destroy_process_group()
 
 
-def test_two_process_gloo_broadcast_and_sharding():
+def test_two_process_gloo_broadcast_and_sharding(monkeypatch):
+    for k, v in NO_GPU.items():   # (spawned children start from this environment)
+        monkeypatch.setenv(k, v)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -475,7 +480,7 @@ def test_dry_and_real_pass_agree_without_a_gpu(cname, B, prec):
     # (round 6: the hook is compiled only into the test-hooks build of the library - the production libresshift_hip.so has no RS_FAKE_DEVICE)
     from resshift_amd import build as _b
 
-    env = dict(os.environ, RS_FAKE_DEVICE="1", RESSHIFT_HIP_LIB=_b.build_testhooks())
+    env = dict(os.environ, RS_FAKE_DEVICE="1", RESSHIFT_HIP_LIB=_b.build_testhooks(), **NO_GPU)
     r = subprocess.run([sys.executable, os.path.join(H.ROOT, "tests", "_fake_device_plumbing.py"), cname, str(B), str(prec)], env=env,
                        capture_output=True, text=True, timeout=600)
     m = re.search(r"dry: tickets (\d+) pool (\d+) prod (\d+) gn (\d+) \| real: tickets (\d+) pool (\d+) prod (\d+) gn (\d+) launches (\d+)", r.stderr)

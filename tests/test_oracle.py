@@ -1,6 +1,7 @@
 """The oracle (oracle/resshift_oracle.py) against the committed golden outputs of the reference itself
-(tests/golden/reference_outputs.npz, produced by oracle/make_golden.py from /root/reference), plus — where the
-reference tree is present — a live re-check against the unmodified reference modules."""
+(tests/golden/reference_outputs.npz, produced by oracle/make_golden.py from the reference tree; tests/golden/reference_checks.npz,
+oracle/make_golden_checks.py, for the checks of its modules, configs, tiler and respaced schedule), plus — where the reference
+modules can be imported — a live bit-exact re-check against the unmodified reference modules."""
 import numpy as np
 import pytest
 import torch
@@ -114,84 +115,99 @@ def test_oracle_offsize_full_network_and_tiles():
     assert (got - torch.from_numpy(g["tiled32/sample"])).abs().max().item() <= 2e-5
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="reference tree not present (GPU box)")
+def _checks():
+    """tests/golden/reference_checks.npz: what the unmodified reference produced for the tests below (oracle/make_golden_checks.py, which
+    also asserts the oracle bit-exact against every entry in the same run)"""
+    from oracle import make_golden_checks as mc
+
+    return np.load(mc.PATH)
+
+
 def test_oracle_offsize_live_against_reference_modules():
-    """live: the reference UNet at 48 x 32 and 32 x 16 on a network constructed for 16 x 16 (bit-exact)"""
-    U, _, _ = ref_import.load()
-    up, ap, dp, _ = H.CASES["tiny"]
-    usd, _ = H.weights(up, ap)
-    um = U(**up).eval()
-    um.load_state_dict(usd, strict=True)
-    g = torch.Generator().manual_seed(11)
-    for (h, w) in ((48, 32), (32, 16), (16, 48)):
-        x, y = torch.randn(2, 3, h, w, generator=g), torch.rand(2, 3, h, w, generator=g) * 2 - 1
-        assert torch.equal(oc.unet_forward(usd, up, x, torch.tensor([1, 1]), lq=y), um(x, torch.tensor([1, 1]), lq=y))
+    """the reference UNet at 48 x 32, 32 x 16 and 16 x 48 on a network constructed for 16 x 16: against its stored outputs, and bit-exact
+    against the live modules where they can be imported (equal bits need the host the stored outputs were made on: thread count and ISA
+    change the reduction order)"""
+    from oracle import make_golden_checks as mc
+
+    g = _checks()
+    up = mc.cases.TINY_UNET
+    usd, _ = mc.tiny_weights()
+    um = None
+    if ref_import.available():
+        U, _, _ = ref_import.load()
+        um = U(**up).eval()
+        um.load_state_dict(usd, strict=True)
+    for (h, w, x, y) in mc.offsize_inputs():
+        got = oc.unet_forward(usd, up, x, torch.tensor([1, 1]), lq=y)
+        assert H.rel_err(got, torch.from_numpy(g[f"offsize/{h}x{w}"])) < 2e-5, (h, w)
+        if um is not None:
+            assert torch.equal(got, um(x, torch.tensor([1, 1]), lq=y)), (h, w)
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="reference tree not present (GPU box)")
 def test_oracle_live_against_reference_modules():
-    U, V, create = ref_import.load()
-    up, ap, dp, _ = H.CASES["tiny"]
-    usd, asd = H.weights(up, ap)
-    um = U(**up).eval()
-    um.load_state_dict(usd, strict=True)
-    am = V(**ap).eval()
-    am.load_state_dict(asd, strict=True)
-    y, noises, _ = H.case_inputs(up, ap, dp, False)
-    x, t = noises[1] * 1.3, torch.tensor([3, 3])
-    assert torch.equal(oc.unet_forward(usd, up, x, t, lq=y), um(x, t, lq=y))
-    z = am.encode(torch.nn.functional.interpolate(y, scale_factor=4, mode="bicubic"))
-    assert H.rel_err(oc.vq_encode(asd, ap, torch.nn.functional.interpolate(y, scale_factor=4, mode="bicubic")), z) < 2e-5
+    """the tiny UNet forward and VQ-f4 encoder against the reference's stored outputs (and the UNet bit-exact against the live modules
+    where they can be imported)"""
+    from oracle import make_golden_checks as mc
+
+    g = _checks()
+    up, ap = mc.cases.TINY_UNET, mc.cases.TINY_AE
+    usd, asd = mc.tiny_weights()
+    x, t, y, img = mc.live_inputs()
+    got = oc.unet_forward(usd, up, x, t, lq=y)
+    assert H.rel_err(got, torch.from_numpy(g["live/unet"])) < 2e-5
+    assert H.rel_err(oc.vq_encode(asd, ap, img), torch.from_numpy(g["live/encode"])) < 2e-5
+    if ref_import.available():
+        U, _, _ = ref_import.load()
+        um = U(**up).eval()
+        um.load_state_dict(usd, strict=True)
+        assert torch.equal(got, um(x, t, lq=y))
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("cname", ["realsr_swinunet_realesrgan256", "faceir_gfpgan512_lpips", "inpaint_lama256_imagenet"])
 def test_spec_equals_reference_state_dict(cname):
-    """resshift_amd.spec must list exactly the reference's state_dict keys, shapes and order."""
-    import os
+    """resshift_amd.spec must list exactly the reference's state_dict keys, shapes and order (stored from the reference's own modules built
+    from its own configs/<cname>.yaml), and the config digest must equal that YAML."""
+    import json
 
-    U, V, _ = ref_import.load()
-    ref_cfg = H.to_plain(H.load_config(os.path.join(ref_import.REF, "configs", cname + ".yaml")))
+    ref = json.loads(str(_checks()[f"spec/{cname}"]))
     mine = H.to_plain(H.load_config(cname))
     for sec in ("model", "diffusion", "autoencoder"):
-        assert ref_cfg[sec] == mine[sec], f"config digest drifted from the reference YAML: {cname}/{sec}"
-    m = U(**ref_cfg["model"]["params"])
+        assert ref["config"][sec] == mine[sec], f"config digest drifted from the reference YAML: {cname}/{sec}"
     spec, _ = H.unet_param_spec(mine["model"]["params"])
-    assert [(k, tuple(v.shape)) for k, v in m.state_dict().items()] == list(spec.items())
-    a = V(**ref_cfg["autoencoder"]["params"])
-    assert [(k, tuple(v.shape)) for k, v in a.state_dict().items()] == list(H.ae_param_spec(mine["autoencoder"]["params"]).items())
+    assert [(k, tuple(s)) for k, s in ref["unet"]] == list(spec.items())
+    assert [(k, tuple(s)) for k, s in ref["ae"]] == list(H.ae_param_spec(mine["autoencoder"]["params"]).items())
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="reference tree not present (GPU box)")
 def test_tiling_restatements_against_reference_ImageSpliterTh():
-    """The reference tiler cannot be imported (utils/util_image.py pulls cv2 / skimage), so its class source is exec'd as
-    is; the oracle's and the product's tile origin lists, and the oracle's sum/count averaging, must reproduce it."""
-    import os
-    import re
+    """utils/util_image.py ImageSpliterTh, as stored by oracle/make_golden_checks.py: the oracle's and the product's tile origin lists must be
+    its lists, the patches cut at its canvas windows must be the patches it handed out, and the sum/count averaging of the deterministic
+    per-tile results must reproduce its gather() bit for bit."""
+    import hashlib
+    import json
 
+    from oracle import make_golden_checks as mc
     from resshift_amd.tiling import extract_starts
 
-    src = open(os.path.join(ref_import.REF, "utils", "util_image.py")).read()
-    m = re.search(r"^class ImageSpliterTh:.*?(?=^class |\Z)", src, re.S | re.M)
-    ns = {"torch": torch}
-    exec(m.group(0), ns)
-    Ref = ns["ImageSpliterTh"]
-    g = torch.Generator().manual_seed(0)
-    for (H, W, ps, st, sf, ebs) in [(96, 80, 64, 48, 4, 1), (130, 64, 64, 64, 2, 3), (64, 64, 64, 32, 4, 1), (200, 131, 64, 50, 1, 2)]:
-        im = torch.randn(2, 3, H, W, generator=g)
-        r = Ref(im, ps, st, sf=sf, extra_bs=ebs)
-        assert r.height_starts_list == oc.tile_starts(H, ps, st) == extract_starts(H, ps, st)
-        assert r.width_starts_list == oc.tile_starts(W, ps, st) == extract_starts(W, ps, st)
-        # feed a deterministic per-tile "result" through both accumulators
-        res = torch.zeros(2, 3, H * sf, W * sf)
+    g = _checks()
+    for k, (Hh, W, ps, st, sf, ebs) in enumerate(mc.TILING_CASES):
+        assert list(g[f"tiling/{k}/height_starts"]) == oc.tile_starts(Hh, ps, st) == extract_starts(Hh, ps, st)
+        assert list(g[f"tiling/{k}/width_starts"]) == oc.tile_starts(W, ps, st) == extract_starts(W, ps, st)
+        windows = json.loads(str(g[f"tiling/{k}/windows"]))
+        assert sum(len(c) for c in windows) == len(oc.tile_starts(Hh, ps, st)) * len(oc.tile_starts(W, ps, st))
+        assert all(len(c) == ebs for c in windows[:-1]) and 0 < len(windows[-1]) <= ebs
+        im = mc.tiling_image(k)
+        res = torch.zeros(2, 3, Hh * sf, W * sf)
         cnt = torch.zeros_like(res)
-        for pch, infos in r:
-            out = torch.nn.functional.interpolate(pch, scale_factor=sf, mode="nearest") * 1.5 + 0.25
-            r.update(out, infos)
+        pch_hash = hashlib.sha256()
+        for infos in windows:
+            pch = torch.cat([im[:, :, h0 // sf:h1 // sf, w0 // sf:w1 // sf] for (h0, h1, w0, w1) in infos])
+            pch_hash.update(pch.contiguous().numpy().tobytes())
+            out = mc.tiling_result(pch, sf)
             for t, (h0, h1, w0, w1) in enumerate(infos):
                 res[:, :, h0:h1, w0:w1] += out[t * 2:(t + 1) * 2]
                 cnt[:, :, h0:h1, w0:w1] += 1
-        assert torch.equal(r.gather(), res / cnt)
+        assert pch_hash.hexdigest() == str(g[f"tiling/{k}/pch_sha256"]), k
+        assert bool((cnt > 0).all()) and mc.digest(res / cnt) == str(g[f"tiling/{k}/gather_sha256"]), k
 
 
 def test_tiled_path_oracle_vs_reference_golden():
@@ -211,20 +227,19 @@ def test_tiled_path_oracle_vs_reference_golden():
     assert (got - torch.from_numpy(g["sample"])).abs().max().item() <= 2e-5
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="reference tree not present (GPU box)")
 def test_respaced_schedule_live_against_reference():
-    """timestep_respacing < steps (respace.py:23-70): the oracle's and the product's tables and timestep map against the
-    reference's own SpacedDiffusion object."""
+    """timestep_respacing < steps (respace.py:23-70): the oracle's and the product's tables and timestep map against the ones the
+    reference's own SpacedDiffusion object holds (stored by oracle/make_golden_checks.py)."""
+    from oracle import make_golden_checks as mc
     from resshift_amd import create_gaussian_diffusion
 
-    _, _, create = ref_import.load()
-    dp = dict(H.CASES["tiny"][2], steps=12, timestep_respacing=4)
-    ref = create(**dp)
+    g = _checks()
+    dp = dict(mc.RESPACE_DP)
     s = oc.Schedule(dp)
     mine = create_gaussian_diffusion(**dp)
-    assert list(ref.timestep_map) == s.timestep_map == mine.timestep_map == [0, 3, 6, 9]
-    for name in ("sqrt_etas", "etas", "posterior_mean_coef1", "posterior_mean_coef2", "posterior_log_variance_clipped"):
-        r = np.asarray(getattr(ref, name), dtype=np.float64)
+    assert list(g["respace/timestep_map"]) == s.timestep_map == mine.timestep_map == [0, 3, 6, 9]
+    for name in mc.RESPACE_TABLES:
+        r = g[f"respace/{name}"]
         assert np.array_equal(r, np.asarray(getattr(s, name), dtype=np.float64)), name
         assert np.array_equal(r, np.asarray(getattr(mine, name), dtype=np.float64)), name
 
