@@ -33,6 +33,9 @@ extern "C" {
 #define RS_PREC_SPLIT 2
 #define RS_MAX_LEVELS 8
 #define RS_MAX_STEPS 64
+/* most images one per-image call may carry (rs_sample_step with mixed step indices, rs_axpbypcz_rows, rs_unet_forward with unequal
+ * timesteps): their coefficients / FiLM row pointers travel as kernel arguments */
+#define RS_MAX_ROWS 64
 
 typedef struct rs_engine rs_engine;
 
@@ -91,6 +94,22 @@ typedef struct rs_sample_args {
     void* stream;                  /* hipStream_t */
 } rs_sample_args;
 
+/* Arguments of one step of a batch whose images may be at different steps (rs_sample_step; continuous batching): one p_sample
+ * (gaussian_diffusion.py:332-365) of image b at step index t[b] */
+typedef struct rs_step_args {
+    const rs_sample_args* sched;   /* the schedule: its inv_std / coef1 / coef2 / sigma / tmap tables, steps and the LR geometry h, w, sf
+                                      are read (its B, tensors and precisions are not) */
+    float* x;              /* dev, [B,Cz,hz,wz] x_t in, x_{t-1} out (in place)                        */
+    float* pred_xstart;    /* dev, optional [B,Cz,hz,wz] the UNet's prediction of x_0                 */
+    const float* y;        /* dev, [B,3,h,w] LR conditioning of each image                            */
+    const float* mask;     /* dev, [B,1,h,w] or NULL                                                  */
+    const float* noise;    /* dev, [B,Cz,hz,wz] this step's draw of each image (unused for t[b] = 0) */
+    const int* t;          /* HOST, [B] step indices into the schedule's tables (0 .. steps-1)        */
+    int B;                 /* images; unequal t[] allows at most RS_MAX_ROWS                         */
+    int prec;              /* UNet precision of this step                                             */
+    void* stream;          /* hipStream_t */
+} rs_step_args;
+
 /* ---- lifetime ------------------------------------------------------------------------------ */
 rs_engine* rs_create(const rs_config* cfg);
 void rs_destroy(rs_engine* e);
@@ -116,7 +135,8 @@ int rs_weights_ready(rs_engine* e);
 
 /* ---- network calls ------------------------------------------------------------------------- */
 /* models/unet.py:865-895 UNetModelSwin.forward(x, timesteps, lq, mask).  x [B,Cz,H,W], lq [B,3,Hl,Wl],
- * mask [B,1,Hl,Wl] or NULL, out [B,out_channels,H,W]; t_host = B timestep values on the host. */
+ * mask [B,1,Hl,Wl] or NULL, out [B,out_channels,H,W]; t_host = B timestep values on the host - any values (unequal ones: per-image
+ * FiLM rows, at most RS_MAX_ROWS images). */
 int rs_unet_forward(rs_engine* e, const float* x, const int* t_host, const float* lq, const float* mask, float* out,
                     int B, int H, int W, int Hl, int Wl, int prec, void* stream);
 /* ldm/models/autoencoder.py:28-31 VQModelTorch.encode: img [B,3,H,W] -> z [B,embed_dim,H/f,W/f] */
@@ -128,8 +148,27 @@ int rs_vq_decode(rs_engine* e, const float* z, float* img, int32_t* idx_out, int
 int rs_bicubic(rs_engine* e, const float* y, float* out, int B, int C, int H, int W, int sf, void* stream);
 /* the whole loop: encode_first_stage -> prior_sample -> steps x (UNet + posterior update) -> decode */
 int rs_sample(rs_engine* e, const rs_sample_args* a);
+/* the same loop in three parts, for a scheduler that admits and retires images at every step (continuous batching; rs_sample is
+ * begin + steps x step + end with the same launches):
+ *   rs_sample_begin: encode_first_stage(y, up_sample) -> * scale_factor -> prior_sample with a->noise = the prior draw [B,Cz,hz,wz]
+ *                    -> x_T [B,Cz,hz,wz] (reads y, noise, B, h, w, sf, prior_scale, scale_factor, prec_encode, stream);
+ *   rs_sample_step:  one step of every image at its own step index (rs_step_args).  Equal indices run the launches of rs_sample's
+ *                    step; unequal ones add one FiLM gather launch and take the elementwise coefficients per image - each image gets
+ *                    bit for bit what it gets in a homogeneous batch of the same size.  Feature-extractor configs compute the conditioning features per call;
+ *   rs_sample_end:   x_0 -> z_out, idx_out, out (reads out, z_out, idx_out, B, h, w, sf, scale_factor, prec_decode, stream). */
+int rs_sample_begin(rs_engine* e, const rs_sample_args* a, float* x_T);
+int rs_sample_step(rs_engine* e, const rs_step_args* s);
+int rs_sample_end(rs_engine* e, const rs_sample_args* a, const float* x_0);
+/* compute and cache the FiLM rows of these (network) timesteps now: the first call at a timestep otherwise builds its row and
+ * synchronises the stream once (a scheduler calls this with the schedule's tmap before its first step) */
+int rs_film_prewarm(rs_engine* e, const int* timesteps, int n, void* stream);
 /* fp32 y = a*x + b*z + c*n on device (posterior mean / prior sample for the step-wise API) */
 int rs_axpbypcz(const float* x, const float* z, const float* n, float* y, float a, float b, float c, long long count, void* stream);
+/* the same with one coefficient triple per image (host arrays a[B], b[B], c[B]; b / c may be NULL when z / n are): image r covers elements
+ * [r * per_image_count, (r + 1) * per_image_count); c[r] == 0 skips image r's noise term.  B <= RS_MAX_ROWS.  Per-sample
+ * _extract_into_tensor arithmetic of the host mirror (gaussian_diffusion.py:92-105): _scale_input, posterior mean, p_sample, q_sample */
+int rs_axpbypcz_rows(const float* x, const float* z, const float* n, float* y, const float* a, const float* b, const float* c,
+                     long long per_image_count, int B, void* stream);
 
 /* overlap-average tiling of large images (utils/util_image.py:889-979 ImageSpliterTh.update / .gather): NCHW fp32,
  * acc[b,c,h0:h0+th,w0:w0+tw] += tile, count[h0:h0+th,w0:w0+tw] += 1; finalize divides acc by count in place */

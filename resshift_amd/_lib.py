@@ -20,6 +20,7 @@ RS_PREC_F32 = 1
 RS_PREC_SPLIT = 2
 RS_MAX_LEVELS = 8
 RS_MAX_STEPS = 64
+RS_MAX_ROWS = 64   # most images of one per-image call (include/resshift_hip.h)
 
 
 class UNetConfig(C.Structure):
@@ -66,6 +67,13 @@ class SampleArgs(C.Structure):
     ]
 
 
+class StepArgs(C.Structure):
+    _fields_ = [
+        ("sched", C.POINTER(SampleArgs)), ("x", C.c_void_p), ("pred_xstart", C.c_void_p), ("y", C.c_void_p), ("mask", C.c_void_p),
+        ("noise", C.c_void_p), ("t", C.POINTER(C.c_int)), ("B", C.c_int), ("prec", C.c_int), ("stream", C.c_void_p),
+    ]
+
+
 _P, _I, _F, _LL, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t
 
 # name -> (restype, argtypes); every symbol declared in include/resshift_hip.h is listed here.
@@ -84,7 +92,12 @@ SIGNATURES = {
     "rs_vq_decode": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rs_bicubic": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rs_sample": (_I, [_P, C.POINTER(SampleArgs)]),
+    "rs_sample_begin": (_I, [_P, C.POINTER(SampleArgs), _P]),
+    "rs_sample_step": (_I, [_P, C.POINTER(StepArgs)]),
+    "rs_sample_end": (_I, [_P, C.POINTER(SampleArgs), _P]),
+    "rs_film_prewarm": (_I, [_P, C.POINTER(C.c_int), _I, _P]),
     "rs_axpbypcz": (_I, [_P, _P, _P, _P, _F, _F, _F, _LL, _P]),
+    "rs_axpbypcz_rows": (_I, [_P, _P, _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _LL, _I, _P]),
     "rs_tile_accumulate": (_I, [_P, _P, _P] + [_I] * 8 + [_P]),
     "rs_tile_finalize": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rs_window_copy": (_I, [_P, _P, _LL, _I, _I, _I, _I, _I, _I, _F, _P]),

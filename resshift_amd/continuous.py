@@ -1,0 +1,182 @@
+"""Continuous batching over a built `ResShiftSampler`: images are admitted at every step and retired at every step.
+
+In ResShift every image carries its own state (x_t, its LR conditioning, its mask, its noise draws) and nothing in the network mixes
+images (GroupNorm is per sample, attention per window), so one UNet call may hold images at different steps.  `ContinuousSampler`
+keeps a dense pool of active images and, per `step()`:
+
+  1. admits waiting images (up to `max_batch` active) as ONE `rs_sample_begin` batch (bicubic + encode + prior_sample);
+  2. runs ONE `rs_sample_step` over every active image, each at its own step index (per-image FiLM rows and elementwise coefficients
+     inside the engine; a pool whose images are all at one step runs the launches of `rs_sample`'s step);
+  3. retires the images that just finished t = 0 as ONE `rs_sample_end` batch (decode) and compacts the pool;
+  4. crops and clamps each result as `ResShiftSampler.sample_func` does.
+
+Same engine, precision policy and `padding_offset` as the sampler it wraps.  One LR size per instance.  Out of scope: per-step mixed
+precision policies, `noise_repeat`, tiling (`sample_tiled`), pixel-space models (no autoencoder).
+"""
+from __future__ import annotations
+
+import math
+from collections import deque
+from typing import Dict, List, Optional
+
+import torch
+
+from . import _lib, sharding
+
+
+class ContinuousSampler:
+    def __init__(self, sampler, max_batch: int = 32, keep_aux: bool = False):
+        """`keep_aux`: also keep each finished image's final latent and VQ indices in `self.aux[id]` ({"z_final", "indices"}, as
+        p_sample_loop's return_aux)"""
+        if getattr(sampler, "autoencoder", None) is None:
+            raise NotImplementedError("ContinuousSampler samples in the VQ latent space: the sampler needs an autoencoder")
+        if not 1 <= int(max_batch) <= _lib.RS_MAX_ROWS:
+            raise ValueError(f"max_batch must be 1 .. {_lib.RS_MAX_ROWS} (RS_MAX_ROWS), got {max_batch}")
+        d = sampler.base_diffusion
+        precs = d._unet_precisions()
+        if len(set(precs)) > 1:
+            raise NotImplementedError("ContinuousSampler needs one UNet precision for every step; this policy varies it by step (mixedK)")
+        self.sampler, self.diffusion, self.engine = sampler, d, sampler.engine
+        self.max_batch = int(max_batch)
+        self.tables = d.step_tables()
+        self.steps = int(d.num_timesteps)
+        self.prec_unet = precs[0]
+        self.prec_encode, self.prec_decode = d._prec(d.precision_encode), d._prec(d.precision_decode)
+        self.sf, self.scale_factor, self.offset = int(d.sf), float(d.scale_factor), int(sampler.padding_offset)
+        self.cond_mask = bool(sampler.configs["model"]["params"].get("cond_mask", False))
+        self.device = getattr(sampler, "device", None) or torch.device("cuda", torch.cuda.current_device())
+        # every step index of the schedule is used: build their FiLM rows now, so that no step pays film_row's synchronise
+        self.engine.film_prewarm([int(v) for v in self.tables["tmap"]])
+        self._waiting: deque = deque()   # (id, y [3,hp,wp], mask [1,hp,wp] | None, draws [steps+1,Cz,hz,wz])
+        self._next_id = 0
+        self.lr_size = None              # (h, w) of the first request: the one LR size of this instance
+        self._pad = (0, 0)
+        # the slot pool: active images are slots 0 .. n-1 (dense; compacted on retire)
+        self._n = 0
+        self._ids: List[int] = []
+        self._t: List[int] = []          # step index of each slot's next step (steps-1 .. 0)
+        self._X = self._Y = self._M = self._N = None
+        self.keep_aux = bool(keep_aux)
+        self.aux: Dict[int, Dict[str, torch.Tensor]] = {}
+
+    # ------------------------------------------------------------------ requests
+    def submit(self, lq, mask=None, noise=None, step_noises=None, noise_repeat=False) -> List[int]:
+        """Queue LR images lq [n,3,h,w] (or [3,h,w]) in [-1,1]; returns one id per image.  `noise` [n,Cz,hz,wz] and `step_noises`
+        (steps tensors [n,Cz,hz,wz], in loop order) inject the draws; otherwise they are drawn now, in the reference's order (prior
+        noise, then one per step: gaussian_diffusion.py:446,358)."""
+        if noise_repeat:
+            raise NotImplementedError("noise_repeat shares one draw across a batch; continuous batching has no fixed batch")
+        if lq.dim() == 3:
+            lq = lq.unsqueeze(0)
+            mask = mask.unsqueeze(0) if mask is not None and mask.dim() == 3 else mask
+        n, _, h, w = lq.shape
+        if self.lr_size is None:
+            self.lr_size = (h, w)
+            self._pad = ((math.ceil(h / self.offset)) * self.offset - h, (math.ceil(w / self.offset)) * self.offset - w)
+        elif (h, w) != self.lr_size:
+            raise ValueError(f"this ContinuousSampler serves {self.lr_size[0]}x{self.lr_size[1]} LR images; got {h}x{w} (one LR size per instance)")
+        if self.cond_mask and mask is None:
+            raise ValueError("this model is conditioned on a mask (cond_mask): submit(lq, mask=...)")
+        lq = lq.to(self.device, torch.float32)
+        mask = mask.to(self.device, torch.float32) if (mask is not None and self.cond_mask) else None
+        if self._pad != (0, 0):   # sample_func's reflect padding (sampler.py:130-138), the mask alike
+            lq = sharding.reflect_pad(lq, *self._pad)
+            mask = sharding.reflect_pad(mask, *self._pad) if mask is not None else None
+        zs = self.engine.latent_shape(n, lq.shape[2], lq.shape[3], self.sf)
+        if noise is None:
+            noise = torch.randn(zs, device=self.device, dtype=torch.float32)
+        if step_noises is None:
+            step_noises = [torch.randn(zs, device=self.device, dtype=torch.float32) for _ in range(self.steps)]
+        if len(step_noises) != self.steps:
+            raise ValueError(f"step_noises: {self.steps} draws expected, got {len(step_noises)}")
+        draws = torch.stack([noise.to(self.device, torch.float32)] + [s.to(self.device, torch.float32) for s in step_noises], 1)
+        if tuple(draws.shape) != (n, self.steps + 1) + tuple(zs[1:]):
+            raise ValueError(f"noise draws must be [{n},{zs[1]},{zs[2]},{zs[3]}] each, got {tuple(draws.shape)}")
+        ids = []
+        for i in range(n):
+            self._waiting.append((self._next_id, lq[i], mask[i] if mask is not None else None, draws[i]))
+            ids.append(self._next_id)
+            self._next_id += 1
+        return ids
+
+    def pending(self) -> int:
+        """images waiting or in flight"""
+        return len(self._waiting) + self._n
+
+    @property
+    def active(self) -> int:
+        return self._n
+
+    # ------------------------------------------------------------------ scheduling
+    def _alloc(self, y, m, draws):
+        B = self.max_batch
+        self._X = torch.empty((B,) + tuple(draws.shape[1:]), device=self.device, dtype=torch.float32)
+        self._Y = torch.empty((B,) + tuple(y.shape), device=self.device, dtype=torch.float32)
+        self._M = torch.empty((B,) + tuple(m.shape), device=self.device, dtype=torch.float32) if m is not None else None
+        self._N = torch.empty((B,) + tuple(draws.shape), device=self.device, dtype=torch.float32)
+
+    def _admit(self):
+        m = min(len(self._waiting), self.max_batch - self._n)
+        if m <= 0:
+            return
+        reqs = [self._waiting.popleft() for _ in range(m)]
+        if self._X is None:
+            self._alloc(reqs[0][1], reqs[0][2], reqs[0][3])
+        a, b = self._n, self._n + m
+        self._Y[a:b] = torch.stack([r[1] for r in reqs])
+        if self._M is not None:
+            self._M[a:b] = torch.stack([r[2] for r in reqs])
+        self._N[a:b] = torch.stack([r[3] for r in reqs])
+        self.engine.sample_begin(self._Y[a:b], self._N[a:b, 0].contiguous(), self.tables, self.sf, self.scale_factor,
+                                 prec_encode=self.prec_encode, out=self._X[a:b])
+        self._ids += [r[0] for r in reqs]
+        self._t += [self.steps - 1] * m
+        self._n = b
+
+    def _compact(self, keep: List[int]):
+        k = len(keep)
+        if k and keep != list(range(k)):
+            idx = torch.tensor(keep, device=self.device, dtype=torch.long)
+            for P in (self._X, self._Y, self._M, self._N):
+                if P is not None:
+                    P[:k] = P.index_select(0, idx)
+        self._ids = [self._ids[i] for i in keep]
+        self._t = [self._t[i] for i in keep]
+        self._n = k
+
+    def step(self) -> Dict[int, torch.Tensor]:
+        """admit -> one step of every active image -> retire; returns {id: image [3, h*sf, w*sf] in [-1,1]} of the images that finished"""
+        self._admit()
+        n = self._n
+        if n == 0:
+            return {}
+        # this step's draw of each slot: draw k = steps - t (draw 0 is the prior noise)
+        k = torch.tensor([self.steps - t for t in self._t], device=self.device, dtype=torch.long)
+        noise = self._N[torch.arange(n, device=self.device), k]
+        self.engine.sample_step(self._X[:n], self._Y[:n], list(self._t), noise, self.tables, self.sf,
+                                mask=self._M[:n] if self._M is not None else None, prec=self.prec_unet)
+        done = [i for i in range(n) if self._t[i] == 0]
+        self._t = [t - 1 for t in self._t]
+        out: Dict[int, torch.Tensor] = {}
+        if done:
+            x0 = self._X[:n].index_select(0, torch.tensor(done, device=self.device, dtype=torch.long))
+            hp, wp = self._Y.shape[2], self._Y.shape[3]
+            img = self.engine.sample_end(x0, hp, wp, self.sf, self.scale_factor, prec_decode=self.prec_decode, return_aux=self.keep_aux)
+            if self.keep_aux:
+                img, aux = img
+                per = aux["indices"].numel() // len(done)
+                for j, i in enumerate(done):
+                    self.aux[self._ids[i]] = {"z_final": aux["z_final"][j], "indices": aux["indices"][j * per:(j + 1) * per]}
+            h, w = self.lr_size
+            img = img[:, :, : h * self.sf, : w * self.sf].clamp_(-1.0, 1.0)   # sample_func's crop and clamp
+            for j, i in enumerate(done):
+                out[self._ids[i]] = img[j]
+            self._compact([i for i in range(n) if self._t[i] >= 0])
+        return out
+
+    def drain(self) -> Dict[int, torch.Tensor]:
+        """step until nothing is waiting or in flight"""
+        out: Dict[int, torch.Tensor] = {}
+        while self.pending():
+            out.update(self.step())
+        return out

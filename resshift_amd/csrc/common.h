@@ -196,6 +196,7 @@ template <> struct Vec8<h2s> {
 struct GNTail {
     const float* gamma; const float* beta;
     const float* film;        // optional [2 * C] FiLM row (scale then shift) of this timestep, or null
+    int film_ld;              // floats between the FiLM rows of consecutive images (0: one row shared by the batch)
     float* coef;              // out: [B][2][C] (scale row, shift row) - GNParams::coef / IGemmParams::xcoef / WinAttnParams::xcoef
     unsigned* ticket;         // [B] arrival counters of THIS tail, zero when the launch starts
     int expected;             // contributing workgroups per image
@@ -290,6 +291,7 @@ struct GNParams {
     const void* x; void* y;
     const float* gamma; const float* beta;
     const float* film;   // optional [2*C] (scale then shift) for this (timestep); null if none
+    int film_ld;         // floats between the FiLM rows of consecutive images (0: one row shared by the batch)
     float* partial;      // [B][S][32][2] partial sums
     int B, HW, C, ldx, ldy, S, groups;
     float eps; int act;

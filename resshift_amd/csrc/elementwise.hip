@@ -8,6 +8,7 @@
 //   VQ:       VectorQuantizer2.forward ldm/modules/vqvae/quantize.py:271-312 (expanded-form distance,
 //             first-minimum argmin, straight-through expression z + (z_q - z)).
 #include "common.h"
+#include "../../include/resshift_hip.h"
 #include <algorithm>
 
 namespace {
@@ -21,6 +22,21 @@ __global__ void nchw_to_nhwc_kernel(const float* in, TO* out, int B, int C, int 
         const long long b = bp / HW;
         const long long pix = bp - b * HW;
         rs_st<TO>(out + bp * ldo * Store<TO>::PM + coff + c, ldo, in[(b * C + c) * HW + pix] * scale);
+    }
+}
+
+// the same with one scale per image (by value: RS_MAX_ROWS images) - _scale_input of a batch whose images are at different steps, in the
+// same expression as the scalar kernel's (the split-storage store sees the same product)
+struct RowScale { float a[RS_MAX_ROWS]; };
+template <typename TO>
+__global__ void nchw_to_nhwc_rows_kernel(const float* in, TO* out, int B, int C, int HW, int ldo, int coff, RowScale s) {
+    const long long n = (long long)B * C * HW;
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(g % C);
+        const long long bp = g / C;  // b*HW + pix
+        const long long b = bp / HW;
+        const long long pix = bp - b * HW;
+        rs_st<TO>(out + bp * ldo * Store<TO>::PM + coff + c, ldo, in[(b * C + c) * HW + pix] * s.a[b]);
     }
 }
 
@@ -67,6 +83,30 @@ __global__ void axpbypcz_kernel(const float* x, const float* z, const float* n, 
         if (z) v += b * z[g];
         if (n) v += c * n[g];
         y[g] = v;
+    }
+}
+
+// the same with one (a, b, c) per image: image r = g / per covers elements [r * per, (r + 1) * per).  The coefficients travel by value
+// (kernel arguments, RS_MAX_ROWS images), so a mixed-timestep step needs no host round trip; the expressions are those of axpbypcz_kernel,
+// so an image gets bit for bit what the scalar kernel gives it.  c == 0 (t = 0, models/gaussian_diffusion.py:358-364) skips the noise
+// term, as the scalar path does with n == nullptr.
+struct RowCoefs { float a[RS_MAX_ROWS], b[RS_MAX_ROWS], c[RS_MAX_ROWS]; };
+__global__ void axpbypcz_rows_kernel(const float* x, const float* z, const float* n, float* y, RowCoefs k, long long per, long long cnt) {
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < cnt; g += (long long)gridDim.x * blockDim.x) {
+        const int r = (int)(g / per);
+        float v = k.a[r] * x[g];
+        if (z) v += k.b[r] * z[g];
+        if (n && k.c[r] != 0.f) v += k.c[r] * n[g];
+        y[g] = v;
+    }
+}
+
+// per-image FiLM table [B][total] gathered from cached per-timestep rows (one pointer per image, by value)
+struct FilmRows { const float* row[RS_MAX_ROWS]; };
+__global__ void film_gather_kernel(FilmRows s, float* out, int total, long long cnt) {
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < cnt; g += (long long)gridDim.x * blockDim.x) {
+        const long long b = g / total;
+        out[g] = s.row[b][g - b * total];
     }
 }
 
@@ -282,6 +322,17 @@ int rs_nchw_to_nhwc_launch(const float* in, void* out, int out_dt, int B, int C,
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int rs_nchw_to_nhwc_rows_launch(const float* in, void* out, int out_dt, int B, int C, int HW, int ldo, int coff, const float* scale, hipStream_t st) {
+    if (B < 1 || B > RS_MAX_ROWS || !scale) return -2;
+    RowScale s{};
+    for (int r = 0; r < B; ++r) s.a[r] = scale[r];
+    const long long n = (long long)B * C * HW;
+    if (out_dt == RS_F16) hipLaunchKernelGGL((nchw_to_nhwc_rows_kernel<f16>), dim3(nblk(n)), dim3(256), 0, st, in, (f16*)out, B, C, HW, ldo, coff, s);
+    else if (out_dt == RS_F16S) hipLaunchKernelGGL((nchw_to_nhwc_rows_kernel<h2s>), dim3(nblk(n)), dim3(256), 0, st, in, (h2s*)out, B, C, HW, ldo, coff, s);
+    else hipLaunchKernelGGL((nchw_to_nhwc_rows_kernel<float>), dim3(nblk(n)), dim3(256), 0, st, in, (float*)out, B, C, HW, ldo, coff, s);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int rs_nhwc_to_nchw_launch(const void* in, int in_dt, float* out, int B, int C, int HW, int ldi, int coff, hipStream_t st) {
     const long long n = (long long)B * C * HW;
     if (in_dt == RS_F16) hipLaunchKernelGGL((nhwc_to_nchw_kernel<f16>), dim3(nblk(n)), dim3(256), 0, st, (const f16*)in, out, B, C, HW, ldi, coff);
@@ -308,6 +359,25 @@ int rs_convert_launch(const void* src, int src_dt, void* dst, int dst_dt, int C,
 
 int rs_axpbypcz_launch(const float* x, const float* z, const float* n, float* y, float a, float b, float c, long long cnt, hipStream_t st) {
     hipLaunchKernelGGL(axpbypcz_kernel, dim3(nblk(cnt)), dim3(256), 0, st, x, z, n, y, a, b, c, cnt);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int rs_axpbypcz_rows_launch(const float* x, const float* z, const float* n, float* y, const float* a, const float* b, const float* c, long long per,
+                            int B, hipStream_t st) {
+    if (B < 1 || B > RS_MAX_ROWS || per < 1 || !x || !y || !a) return -2;
+    RowCoefs k{};
+    for (int r = 0; r < B; ++r) { k.a[r] = a[r]; k.b[r] = b ? b[r] : 0.f; k.c[r] = c ? c[r] : 0.f; }
+    const long long cnt = per * B;
+    hipLaunchKernelGGL(axpbypcz_rows_kernel, dim3(nblk(cnt)), dim3(256), 0, st, x, z, n, y, k, per, cnt);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int rs_film_gather_launch(const float* const* rows, int B, int total, float* out, hipStream_t st) {
+    if (B < 1 || B > RS_MAX_ROWS || total < 1) return -2;
+    FilmRows s{};
+    for (int r = 0; r < B; ++r) { if (!rows[r]) return -2; s.row[r] = rows[r]; }
+    const long long cnt = (long long)B * total;
+    hipLaunchKernelGGL(film_gather_kernel, dim3(nblk(cnt)), dim3(256), 0, st, s, out, total, cnt);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

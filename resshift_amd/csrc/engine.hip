@@ -54,6 +54,10 @@ int rs_softmax_rows_launch(const float* s, void* out, int out_dt, long long nrow
 int rs_nchw_to_nhwc_launch(const float* in, void* out, int out_dt, int B, int C, int HW, int ldo, int coff, float scale, hipStream_t st);
 int rs_nhwc_to_nchw_launch(const void* in, int in_dt, float* out, int B, int C, int HW, int ldi, int coff, hipStream_t st);
 int rs_axpbypcz_launch(const float* x, const float* z, const float* n, float* y, float a, float b, float c, long long cnt, hipStream_t st);
+int rs_axpbypcz_rows_launch(const float* x, const float* z, const float* n, float* y, const float* a, const float* b, const float* c, long long per,
+                            int B, hipStream_t st);
+int rs_film_gather_launch(const float* const* rows, int B, int total, float* out, hipStream_t st);
+int rs_nchw_to_nhwc_rows_launch(const float* in, void* out, int out_dt, int B, int C, int HW, int ldo, int coff, const float* scale, hipStream_t st);
 int rs_clamp_launch(float* x, float lo, float hi, long long cnt, hipStream_t st);
 int rs_win_attn_qkv_supported(int heads, int E);
 int rs_win_attn_qkv_launch(const WinAttnParams* p, hipStream_t st);
@@ -201,7 +205,9 @@ struct Arena {
 // producer, the real pass attaches the tail at the producer's launch and skips the coefficient launch at the consumer.
 struct TailPlan {
     bool on = false; int consumer = -1;
-    const float* gamma = nullptr; const float* beta = nullptr; const float* film = nullptr; float eps = 0.f;
+    const float* gamma = nullptr; const float* beta = nullptr; float eps = 0.f;
+    long long film_off = -1;   // the consumer's FiLM rows relative to Exec::film_base (-1: no FiLM); an offset because a per-image table
+                               // lives in the scratch arena, whose address the dry pass does not know yet
     int C = 0, HW = 0; size_t coef_off = 0;
     bool two = false; size_t st2_off = 0; int st2S = 0, st2ld = 0;   // the other half of a concatenation (statistics live in the pool)
     mutable bool drawn = false;   // (real pass: the producer's launch attached the tail - checked against the plan at the end of the call)
@@ -212,6 +218,8 @@ struct Exec {
     bool dbg = false;                        // debug trace requested (both passes): no statistics fusion, no tails
     std::vector<TailPlan>* plan = nullptr;   // by producer sequence number
     int prod_seq = 0, gn_seq = 0;
+    // FiLM rows of the network body being walked (unet_body): one row shared by the batch (film_ld 0) or a per-image table [B][film_ld]
+    const float* film_base = nullptr; int film_ld = 0;
     // coefficient pool ([B][2][C] affines; behind the scratch arena, reset per network body - stream order keeps reuse safe) and the
     // ticket pool of the tails (zeroed once per call)
     char* pool_base = nullptr; size_t pool_off = 0, pool_peak = 0;
@@ -231,7 +239,8 @@ struct Exec {
         const TailPlan* t = tail_of(prod);
         if (!t) return false;
         t->drawn = true;
-        g.gamma = t->gamma; g.beta = t->beta; g.film = t->film; g.eps = t->eps;
+        g.gamma = t->gamma; g.beta = t->beta; g.eps = t->eps;
+        g.film = t->film_off >= 0 ? film_base + t->film_off : nullptr; g.film_ld = g.film ? film_ld : 0;
         g.coef = (float*)(pool_base + t->coef_off); g.ticket = tickets(B);
         g.C = t->C; g.groups = 32; g.HW = t->HW;
         if (t->two) { g.st1 = (const float*)(pool_base + t->st2_off); g.S1 = t->st2S; g.ld1 = t->st2ld; }
@@ -1171,7 +1180,7 @@ struct rs_engine {
                 if ((int)pl.size() <= x.st_prod) pl.resize(x.st_prod + 1);
                 TailPlan& t = pl[x.st_prod];
                 if (!t.on) {
-                    t.on = true; t.consumer = me; t.gamma = g.gamma; t.beta = g.beta; t.film = film; t.eps = eps; t.C = x.C; t.HW = x.H * x.W;
+                    t.on = true; t.consumer = me; t.gamma = g.gamma; t.beta = g.beta; t.film_off = film ? (long long)(film - ex.film_base) : -1; t.eps = eps; t.C = x.C; t.HW = x.H * x.W;
                     t.coef_off = (size_t)((char*)coef - ex.pool_base);
                     if (x.st2) { t.two = true; t.st2_off = (size_t)((char*)x.st2 - ex.pool_base); t.st2S = x.st2S; t.st2ld = x.st2ld; }
                     ex.ticket_used += (size_t)x.B;   // (drawn by the producer's launch in the real pass)
@@ -1201,7 +1210,7 @@ struct rs_engine {
         if (ex.dry) return;
         GNParams p{};
         p.ticket = ticket;
-        p.x = x.p; p.y = y.p; p.gamma = g.gamma; p.beta = g.beta; p.film = film; p.partial = partial;
+        p.x = x.p; p.y = y.p; p.gamma = g.gamma; p.beta = g.beta; p.film = film; p.film_ld = film ? ex.film_ld : 0; p.partial = partial;
         p.B = x.B; p.HW = HW; p.C = x.C; p.ldx = x.ld; p.ldy = y.ld; p.S = S; p.groups = 32; p.eps = eps; p.act = act; p.coef = coef;
         if (x.st) { p.cpartial = x.st; p.cp_ld = x.stld; p.S = x.stS; }   // per-channel partials from the producing conv: no statistics pass
         if (x.st && x.st2) { p.cpartial2 = x.st2; p.cp2_ld = x.st2ld; p.cp2_S = x.st2S; p.cp_n0 = x.st_n0; }   // ... of both halves of a concatenation
@@ -1499,6 +1508,15 @@ struct rs_engine {
         film_cache[t] = row;
         return row;
     }
+    // per-image FiLM table [B][film_total] for a batch whose images are at different timesteps: ONE gather launch from the cached rows
+    // (rows[b] = film_row(t_b)), so that every image sees exactly the values the shared row of a homogeneous batch would give it.  Lives in
+    // the scratch arena; the dry pass gets a non-null stand-in (never dereferenced) so that "has FiLM" reads the same in both passes.
+    const float* film_table(Exec& ex, const float* const* rows, int B) {
+        float* tab = (float*)ex.raw((size_t)B * film_total * sizeof(float));
+        if (ex.dry) return (const float*)(uintptr_t)4096;
+        ex.check(rs_film_gather_launch(rows, B, film_total, tab, ex.st), "film gather");
+        return tab;
+    }
     void collect_film_blocks() {
         film_blocks.clear();
         if (!cfg.has_unet) return;
@@ -1511,8 +1529,9 @@ struct rs_engine {
     // x: NCHW fp32 [B,Cz,H,W] (already scaled by _scale_input when called through the drop-in API);
     // lq_feat: optional NHWC view of the (feature-extracted) conditioning; out: NCHW fp32.
     void unet_body(Exec& ex, const float* x, float xscale, const View* lq_feat, const float* lq_nchw, const float* mask_nchw, int Hl, int Wl,
-                   float* out, int B, int H, int W, int dt, const float* film) {
+                   float* out, int B, int H, int W, int dt, const float* film, int film_ld = 0, const float* xscale_rows = nullptr) {
         ex.enter_part("unet");
+        ex.film_base = film; ex.film_ld = film_ld;   // (film_ld > 0: `film` is a per-image table [B][film_ld], film_table())
         const rs_unet_config& u = cfg.unet;
         const int n_in = (int)in_blocks.size(), n_out = (int)out_blocks.size();
         const size_t mk0 = ex.mark();
@@ -1552,7 +1571,8 @@ struct rs_engine {
                 View in0 = ex.T(B, H, W, in_blocks[0].conv.CinP, dt);
                 if (!ex.dry) {
                     zero(ex, in0);
-                    ex.check(rs_nchw_to_nhwc_launch(x, in0.p, dt, B, Cz, H * W, in0.ld, 0, xscale, ex.st), "x->nhwc");
+                    if (xscale_rows) ex.check(rs_nchw_to_nhwc_rows_launch(x, in0.p, dt, B, Cz, H * W, in0.ld, 0, xscale_rows, ex.st), "x->nhwc (per image)");
+                    else ex.check(rs_nchw_to_nhwc_launch(x, in0.p, dt, B, Cz, H * W, in0.ld, 0, xscale, ex.st), "x->nhwc");
                     if (cl) ex.check(rs_nchw_to_nhwc_launch(lq_nchw, in0.p, dt, B, 3, H * W, in0.ld, Cz, 1.f, ex.st), "lq->nhwc");
                     if (cl == 4) ex.check(rs_nchw_to_nhwc_launch(mask_nchw, in0.p, dt, B, 1, H * W, in0.ld, Cz + 3, 1.f, ex.st), "mask->nhwc");
                 }
@@ -1561,7 +1581,10 @@ struct rs_engine {
             } else {
                 // conditioning goes through the strided-conv feature extractor (unet.py:693-702); lq_feat precomputed
                 View xin = ex.T(B, H, W, Cz, dt);
-                if (!ex.dry) ex.check(rs_nchw_to_nhwc_launch(x, xin.p, dt, B, Cz, H * W, xin.ld, 0, xscale, ex.st), "x->nhwc");
+                if (!ex.dry) {
+                    if (xscale_rows) ex.check(rs_nchw_to_nhwc_rows_launch(x, xin.p, dt, B, Cz, H * W, xin.ld, 0, xscale_rows, ex.st), "x->nhwc (per image)");
+                    else ex.check(rs_nchw_to_nhwc_launch(x, xin.p, dt, B, Cz, H * W, xin.ld, 0, xscale, ex.st), "x->nhwc");
+                }
                 conv(ex, in_blocks[0].conv, xin, lq_feat, y0, 1, 1, 1, 1, 0, nullptr);
             }
             ex.reset(mk);
@@ -1755,6 +1778,70 @@ struct rs_engine {
         head(ex, dec_norm, dec_out, h, o, 1e-6f);
         if (!ex.dry) ex.check(rs_nhwc_to_nchw_launch(o.p, RS_F32, img, B, a.out_ch, h.H * h.W, o.ld, 0, ex.st), "img->nchw");
         ex.reset(mk0);
+    }
+
+    // ---------------------------------------------------------------- the sampling loop in three parts
+    // (rs_sample runs them in one call; rs_sample_begin / rs_sample_step / rs_sample_end one at a time, for a scheduler that admits and
+    // retires images at every step)
+    int latent_div() const { return 1 << (cfg.ae.n_levels - 1); }
+    // encode_first_stage(y, up_sample=True) -> * scale_factor -> prior_sample (gaussian_diffusion.py:500-529): x_T = z_y + prior_scale * noise0
+    void sample_prologue(Exec& ex, const rs_sample_args* a, float* z_y, float* xt, const float* noise0) {
+        const rs_ae_config& ae = cfg.ae;
+        const int B = a->B, Hi = a->h * a->sf, Wi = a->w * a->sf, f = latent_div();
+        const long long zcount = (long long)B * ae.embed_dim * (Hi / f) * (Wi / f);
+        {
+            const size_t mk = ex.mark();
+            View in = ex.T(B, Hi, Wi, enc_in.CinP, a->prec_encode);  // RGB zero-padded to 8 channels
+            zero(ex, in);
+            if (!ex.dry) {
+                if (a->sf != 1) ex.check(rs_bicubic_launch(a->y, in.p, a->prec_encode, B, ae.in_channels, a->h, a->w, a->sf, in.ld, ex.st), "bicubic");
+                else ex.check(rs_nchw_to_nhwc_launch(a->y, in.p, a->prec_encode, B, ae.in_channels, Hi * Wi, in.ld, 0, 1.f, ex.st), "y->nhwc");
+            }
+            encode_body(ex, in, z_y, a->prec_encode);
+            ex.reset(mk);
+        }
+        if (!ex.dry) {
+            // z_y * scale_factor, then prior_sample: x_T = z_y + kappa*sqrt(eta_T)*noise (gaussian_diffusion.py:512,529)
+            if (a->scale_factor != 1.0f) ex.check(rs_axpbypcz_launch(z_y, nullptr, nullptr, z_y, a->scale_factor, 0.f, 0.f, zcount, ex.st), "scale z_y");
+            ex.check(rs_axpbypcz_launch(z_y, nullptr, noise0, xt, 1.f, 0.f, a->prior_scale, zcount, ex.st), "prior_sample");
+        }
+    }
+    // one p_sample (gaussian_diffusion.py:332-365) of every image b at its own step index t[b]: pred = model(_scale_input(x_t), tmap[t], lq),
+    // x_{t-1} = coef1 x_t + coef2 pred + [t > 0] sigma noise, in place.  Equal indices: exactly the scalar launches of rs_sample.  Otherwise
+    // the per-image FiLM table (+ one gather launch), _scale_input per image inside the UNet's input conversion and the per-image
+    // elementwise kernel: every image gets bit for bit what it would get in a homogeneous batch of the same size.  films[i]: cached FiLM row of step index i (rows not used may be null).
+    void sample_step(Exec& ex, float* xt, float* pred, const View* feat, const float* y, const float* mask, int h, int w, int B, int hz, int wz,
+                     int prec, const int* t, const rs_sample_args* a, const float* const* films, const float* noise) {
+        bool mixed = false;
+        for (int b = 1; b < B; ++b) mixed |= t[b] != t[0];
+        const long long zcount = (long long)B * cfg.unet.in_channels * hz * wz;
+        if (!mixed) {
+            const int i = t[0];
+            unet_body(ex, xt, a->inv_std[i], feat, y, mask, h, w, pred, B, hz, wz, prec, films[i]);
+            // mean = c1*x_t + c2*x0 (:218-221); sample = mean + [t>0]*sigma_t*eps (:358-364)
+            if (!ex.dry) ex.check(rs_axpbypcz_launch(xt, pred, i > 0 ? noise : nullptr, xt, a->coef1[i], a->coef2[i], a->sigma[i], zcount, ex.st), "posterior step");
+            return;
+        }
+        const size_t mk = ex.mark();
+        const float* rows[RS_MAX_ROWS];
+        float ca[RS_MAX_ROWS], cb[RS_MAX_ROWS], cc[RS_MAX_ROWS];
+        for (int b = 0; b < B; ++b) rows[b] = films[t[b]];
+        const float* tab = film_table(ex, rows, B);
+        const long long per = zcount / B;
+        for (int b = 0; b < B; ++b) ca[b] = a->inv_std[t[b]];   // _scale_input per image (:598-609)
+        unet_body(ex, xt, 1.0f, feat, y, mask, h, w, pred, B, hz, wz, prec, tab, film_total, ca);
+        if (!ex.dry) {
+            for (int b = 0; b < B; ++b) { ca[b] = a->coef1[t[b]]; cb[b] = a->coef2[t[b]]; cc[b] = t[b] > 0 ? a->sigma[t[b]] : 0.f; }
+            ex.check(rs_axpbypcz_rows_launch(xt, pred, noise, xt, ca, cb, cc, per, B, ex.st), "posterior step (per image)");
+        }
+        ex.reset(mk);
+    }
+    // z_out, then decode_first_stage: z / scale_factor -> VQ -> post_quant_conv -> Decoder (gaussian_diffusion.py:474-498)
+    void sample_epilogue(Exec& ex, const rs_sample_args* a, const float* xt) {
+        const int f = latent_div(), hz = a->h * a->sf / f, wz = a->w * a->sf / f;
+        const long long zcount = (long long)a->B * cfg.ae.embed_dim * hz * wz;
+        if (a->z_out && !ex.dry) (void)hipMemcpyAsync(a->z_out, xt, zcount * 4, hipMemcpyDeviceToDevice, ex.st);
+        decode_body(ex, xt, 1.0f / a->scale_factor, a->out, a->idx_out, a->B, hz, wz, 0, a->prec_decode);
     }
 
     // ---------------------------------------------------------------- run helper (dry sizing pass, then real pass)
@@ -2060,13 +2147,18 @@ int rs_unet_forward(rs_engine* e, const float* x, const int* t_host, const float
         return fail("rs_unet_forward: without a feature extractor lq must have the latent resolution");
     if (!e->fe_convs.empty() && ((Hl >> (int)e->fe_convs.size()) != H || (Wl >> (int)e->fe_convs.size()) != W))
         return fail("rs_unet_forward: lq resolution does not match the feature extractor's down-sampling");
-    for (int b = 1; b < B; ++b) if (t_host[b] != t_host[0]) return fail("rs_unet_forward: per-sample timesteps must be equal within a batch");
-    const float* film = e->film_row(t_host[0], st);
-    if (!film) return fail("FiLM table allocation failed");
+    bool mixed = false;
+    for (int b = 1; b < B; ++b) mixed |= t_host[b] != t_host[0];
+    if (mixed && B > RS_MAX_ROWS) return fail("rs_unet_forward: unequal timesteps in a batch of more than RS_MAX_ROWS (" + std::to_string(RS_MAX_ROWS) + ") images");
+    // FiLM: the cached row of the batch's timestep, or (unequal timesteps) one row per image gathered from the cached rows
+    std::vector<const float*> rows(mixed ? B : 1);
+    for (size_t b = 0; b < rows.size(); ++b)
+        if (!(rows[b] = e->film_row(t_host[b], st))) return fail("FiLM table allocation failed");
     return e->run(st, [&](Exec& ex) {
         View feat; const View* fp = nullptr;
         if (!e->fe_convs.empty()) { feat = e->feature_extract(ex, lq, mask, B, Hl, Wl, prec); fp = &feat; }
-        e->unet_body(ex, x, 1.0f, fp, lq, mask, Hl, Wl, out, B, H, W, prec, film);
+        if (!mixed) e->unet_body(ex, x, 1.0f, fp, lq, mask, Hl, Wl, out, B, H, W, prec, rows[0]);
+        else e->unet_body(ex, x, 1.0f, fp, lq, mask, Hl, Wl, out, B, H, W, prec, e->film_table(ex, rows.data(), B), e->film_total);
     });
 }
 
@@ -2107,37 +2199,54 @@ int rs_axpbypcz(const float* x, const float* z, const float* n, float* y, float 
     return rs_axpbypcz_launch(x, z, n, y, a, b, c, count, (hipStream_t)stream);
 }
 
+int rs_axpbypcz_rows(const float* x, const float* z, const float* n, float* y, const float* a, const float* b, const float* c, long long per_image_count,
+                     int B, void* stream) {
+    if (B < 1 || B > RS_MAX_ROWS) return fail("rs_axpbypcz_rows: B must be 1 .. RS_MAX_ROWS (" + std::to_string(RS_MAX_ROWS) + ")");
+    if (!x || !y || !a || per_image_count < 1) return fail("rs_axpbypcz_rows: null tensor / coefficients or empty image");
+    if ((z && !b) || (n && !c)) return fail("rs_axpbypcz_rows: a z / n operand needs its b / c coefficients");
+    const int rc = rs_axpbypcz_rows_launch(x, z, n, y, a, b, c, per_image_count, B, (hipStream_t)stream);
+    return rc ? fail("rs_axpbypcz_rows: launch failed") : 0;
+}
+
+// checks shared by rs_sample / rs_sample_begin / rs_sample_end: the batch geometry and the conditioning; "" when fine
+static std::string sample_args_error(rs_engine* e, const rs_sample_args* a, bool encode, bool decode) {
+    if (!e || !a) return "null argument";
+    if (!e->cfg.has_ae || !e->cfg.has_unet) return "the sampling loop needs both the UNet and the autoencoder";
+    auto bad = [](int p) { return p != RS_F16 && p != RS_F32 && p != RS_F16S; };
+    if ((encode && bad(a->prec_encode)) || (decode && bad(a->prec_decode))) return "bad precision";
+    if (!e->ready) return "weights are not ready";
+    const int f = e->latent_div(), Hi = a->h * a->sf, Wi = a->w * a->sf, hz = Hi / f, wz = Wi / f;
+    if (e->cfg.unet.in_channels != e->cfg.ae.embed_dim) return "UNet in_channels != AE embed_dim";
+    if (a->B < 1 || a->h < 1 || a->w < 1 || a->sf < 1) return "bad batch / size";
+    if ((Hi % f) || (Wi % f)) return "h*sf and w*sf must be multiples of the autoencoder's down-sampling factor";
+    const int sh = e->cfg.unet.n_levels - 1;
+    if ((hz % (8 << sh)) || (wz % (8 << sh))) return "latent H/W must be multiples of 8*2^(levels-1) (pad the input, sampler.py:130-138)";
+    if (e->cfg.unet.cond_lq && e->fe_convs.empty() && (a->h != hz || a->w != wz))
+        return "without a feature extractor the LQ image is concatenated at latent resolution: h*sf/f must equal h";
+    if (encode && !a->y) return "null tensor (y)";
+    if (decode && !a->out) return "null tensor (out)";
+    return "";
+}
+
 // gaussian_diffusion.py:367-472: encode_first_stage(up_sample) -> prior_sample -> T x p_sample -> decode_first_stage
 int rs_sample(rs_engine* e, const rs_sample_args* a) {
     if (!e || !a) return fail("null argument");
-    if (!e->cfg.has_ae || !e->cfg.has_unet) return fail("rs_sample needs both the UNet and the autoencoder");
     if (a->steps < 1 || a->steps > RS_MAX_STEPS) return fail("bad step count");
+    for (int i = 0; i < a->steps; ++i) if (a->prec_unet[i] != RS_F16 && a->prec_unet[i] != RS_F32 && a->prec_unet[i] != RS_F16S) return fail("bad precision");
     {
-        auto bad = [](int p) { return p != RS_F16 && p != RS_F32 && p != RS_F16S; };
-        if (bad(a->prec_encode) || bad(a->prec_decode)) return fail("bad precision");
-        for (int i = 0; i < a->steps; ++i) if (bad(a->prec_unet[i])) return fail("bad precision");
+        const std::string err = sample_args_error(e, a, true, true);
+        if (!err.empty()) return fail("rs_sample: " + err);
     }
-    hipStream_t st = (hipStream_t)a->stream;
-    if (!e->ready) return fail("weights are not ready");
-    const rs_ae_config& ae = e->cfg.ae;
-    const int f = 1 << (ae.n_levels - 1);
-    const int B = a->B, Hi = a->h * a->sf, Wi = a->w * a->sf, hz = Hi / f, wz = Wi / f, Cz = ae.embed_dim;
-    if (e->cfg.unet.in_channels != Cz) return fail("UNet in_channels != AE embed_dim");
-    if (B < 1 || a->h < 1 || a->w < 1 || a->sf < 1 || !a->y || !a->noise || !a->out) return fail("rs_sample: bad batch / size / null tensor");
-    if ((Hi % f) || (Wi % f)) return fail("rs_sample: h*sf and w*sf must be multiples of the autoencoder's down-sampling factor");
-    {
-        const int sh = e->cfg.unet.n_levels - 1;
-        if ((hz % (8 << sh)) || (wz % (8 << sh))) return fail("rs_sample: latent H/W must be multiples of 8*2^(levels-1) (pad the input, sampler.py:130-138)");
-    }
-    if (e->cfg.unet.cond_lq && e->fe_convs.empty() && (a->h != hz || a->w != wz))
-        return fail("rs_sample: without a feature extractor the LQ image is concatenated at latent resolution: h*sf/f must equal h");
+    if (!a->noise) return fail("rs_sample: bad batch / size / null tensor");
     if (e->cfg.unet.cond_mask && !a->mask) return fail("rs_sample: this UNet is conditioned on a mask (cond_mask) but mask is NULL");
+    hipStream_t st = (hipStream_t)a->stream;
+    const int B = a->B, f = e->latent_div(), hz = a->h * a->sf / f, wz = a->w * a->sf / f;
     std::vector<const float*> films(a->steps);
     for (int t = 0; t < a->steps; ++t) {
         films[t] = e->film_row(a->tmap[t], st);
         if (!films[t]) return fail("FiLM table allocation failed");
     }
-    const long long zcount = (long long)B * Cz * hz * wz;
+    const long long zcount = (long long)B * e->cfg.ae.embed_dim * hz * wz;
     return e->run(st, [&](Exec& ex) {
         float* z_y = (float*)ex.raw(zcount * 4);
         float* xt = (float*)ex.raw(zcount * 4);
@@ -2149,37 +2258,85 @@ int rs_sample(rs_engine* e, const rs_sample_args* a) {
                 const int pr = a->prec_unet[i];
                 if (!have_feat[pr]) { feat[pr] = e->feature_extract(ex, a->y, a->mask, B, a->h, a->w, pr); have_feat[pr] = true; }
             }
-        // encode_first_stage (gaussian_diffusion.py:500-515)
-        {
-            const size_t mk = ex.mark();
-            View in = ex.T(B, Hi, Wi, e->enc_in.CinP, a->prec_encode);  // RGB zero-padded to 8 channels
-            e->zero(ex, in);
-            if (!ex.dry) {
-                if (a->sf != 1) ex.check(rs_bicubic_launch(a->y, in.p, a->prec_encode, B, ae.in_channels, a->h, a->w, a->sf, in.ld, st), "bicubic");
-                else ex.check(rs_nchw_to_nhwc_launch(a->y, in.p, a->prec_encode, B, ae.in_channels, Hi * Wi, in.ld, 0, 1.f, st), "y->nhwc");
-            }
-            e->encode_body(ex, in, z_y, a->prec_encode);
-            ex.reset(mk);
-        }
-        if (!ex.dry) {
-            // z_y * scale_factor, then prior_sample: x_T = z_y + kappa*sqrt(eta_T)*noise (gaussian_diffusion.py:512,529)
-            if (a->scale_factor != 1.0f) ex.check(rs_axpbypcz_launch(z_y, nullptr, nullptr, z_y, a->scale_factor, 0.f, 0.f, zcount, st), "scale z_y");
-            ex.check(rs_axpbypcz_launch(z_y, nullptr, a->noise, xt, 1.f, 0.f, a->prior_scale, zcount, st), "prior_sample");
-        }
+        e->sample_prologue(ex, a, z_y, xt, a->noise);
+        std::vector<int> tb(B);
         for (int i = a->steps - 1, k = 1; i >= 0; --i, ++k) {
-            // model(_scale_input(x_t, t), t, lq) -> pred_xstart (gaussian_diffusion.py:266,278)
             const int pr = a->prec_unet[i];
-            e->unet_body(ex, xt, a->inv_std[i], e->fe_convs.empty() ? nullptr : &feat[pr], a->y, a->mask, a->h, a->w, pred, B, hz, wz, pr, films[i]);
-            if (!ex.dry) {
-                // mean = c1*x_t + c2*x0 (:218-221); sample = mean + [t>0]*sigma_t*eps (:358-364)
-                const float* nz = (i > 0) ? a->noise + (long long)k * zcount : nullptr;
-                ex.check(rs_axpbypcz_launch(xt, pred, nz, xt, a->coef1[i], a->coef2[i], a->sigma[i], zcount, st), "posterior step");
-            }
+            std::fill(tb.begin(), tb.end(), i);
+            e->sample_step(ex, xt, pred, e->fe_convs.empty() ? nullptr : &feat[pr], a->y, a->mask, a->h, a->w, B, hz, wz, pr, tb.data(), a, films.data(),
+                           a->noise + (long long)k * zcount);
         }
-        if (a->z_out && !ex.dry) (void)hipMemcpyAsync(a->z_out, xt, zcount * 4, hipMemcpyDeviceToDevice, st);
-        // decode_first_stage: z / scale_factor -> VQ -> post_quant_conv -> Decoder (gaussian_diffusion.py:474-498)
-        e->decode_body(ex, xt, 1.0f / a->scale_factor, a->out, a->idx_out, B, hz, wz, 0, a->prec_decode);
+        e->sample_epilogue(ex, a, xt);
     });
+}
+
+int rs_sample_begin(rs_engine* e, const rs_sample_args* a, float* x_T) {
+    const std::string err = sample_args_error(e, a, true, false);
+    if (!err.empty()) return fail("rs_sample_begin: " + err);
+    if (!a->noise || !x_T) return fail("rs_sample_begin: null tensor (noise / x_T)");
+    const int f = e->latent_div();
+    const long long zcount = (long long)a->B * e->cfg.ae.embed_dim * (a->h * a->sf / f) * (a->w * a->sf / f);
+    return e->run((hipStream_t)a->stream, [&](Exec& ex) {
+        float* z_y = (float*)ex.raw(zcount * 4);
+        e->sample_prologue(ex, a, z_y, x_T, a->noise);
+    });
+}
+
+int rs_sample_step(rs_engine* e, const rs_step_args* s) {
+    if (!e || !s || !s->sched) return fail("rs_sample_step: null argument");
+    const rs_sample_args* a = s->sched;
+    if (a->steps < 1 || a->steps > RS_MAX_STEPS) return fail("rs_sample_step: bad step count in the schedule");
+    if (s->prec != RS_F16 && s->prec != RS_F32 && s->prec != RS_F16S) return fail("rs_sample_step: bad precision");
+    rs_sample_args g = *a;   // (geometry checks with this call's batch)
+    g.B = s->B;
+    {
+        const std::string err = sample_args_error(e, &g, false, false);
+        if (!err.empty()) return fail("rs_sample_step: " + err);
+    }
+    if (!s->x || !s->t) return fail("rs_sample_step: null tensor (x) or step indices (t)");
+    if (e->cfg.unet.cond_lq && !s->y) return fail("rs_sample_step: this UNet is conditioned on lq (cond_lq) but y is NULL");
+    if (e->cfg.unet.cond_mask && !s->mask) return fail("rs_sample_step: this UNet is conditioned on a mask (cond_mask) but mask is NULL");
+    const int B = s->B;
+    bool mixed = false, noisy = false;
+    for (int b = 0; b < B; ++b) {
+        if (s->t[b] < 0 || s->t[b] >= a->steps)
+            return fail("rs_sample_step: step index t[" + std::to_string(b) + "] = " + std::to_string(s->t[b]) + " is outside [0, " + std::to_string(a->steps) + ")");
+        mixed |= s->t[b] != s->t[0];
+        noisy |= s->t[b] > 0;
+    }
+    if (mixed && B > RS_MAX_ROWS) return fail("rs_sample_step: mixed step indices in a batch of more than RS_MAX_ROWS (" + std::to_string(RS_MAX_ROWS) + ") images");
+    if (noisy && !s->noise) return fail("rs_sample_step: noise is NULL but an image is at t > 0");
+    hipStream_t st = (hipStream_t)s->stream;
+    std::vector<const float*> films(a->steps, nullptr);
+    for (int b = 0; b < B; ++b) {
+        const int i = s->t[b];
+        if (!films[i] && !(films[i] = e->film_row(a->tmap[i], st))) return fail("FiLM table allocation failed");
+    }
+    const int f = e->latent_div(), hz = a->h * a->sf / f, wz = a->w * a->sf / f;
+    const long long zcount = (long long)B * e->cfg.ae.embed_dim * hz * wz;
+    return e->run(st, [&](Exec& ex) {
+        float* pred = s->pred_xstart ? s->pred_xstart : (float*)ex.raw(zcount * 4);
+        // (feature-extractor configs: the conditioning features of this batch, per call)
+        View feat; const View* fp = nullptr;
+        if (!e->fe_convs.empty()) { feat = e->feature_extract(ex, s->y, s->mask, B, a->h, a->w, s->prec); fp = &feat; }
+        e->sample_step(ex, s->x, pred, fp, s->y, s->mask, a->h, a->w, B, hz, wz, s->prec, s->t, a, films.data(), s->noise);
+    });
+}
+
+int rs_film_prewarm(rs_engine* e, const int* timesteps, int n, void* stream) {
+    if (!e || !e->cfg.has_unet) return fail("engine has no UNet");
+    if (!e->ready) return fail("weights are not ready");
+    if (n < 0 || (n && !timesteps)) return fail("rs_film_prewarm: bad timestep list");
+    for (int i = 0; i < n; ++i)
+        if (!e->film_row(timesteps[i], (hipStream_t)stream)) return fail("FiLM table allocation failed");
+    return 0;
+}
+
+int rs_sample_end(rs_engine* e, const rs_sample_args* a, const float* x_0) {
+    const std::string err = sample_args_error(e, a, false, true);
+    if (!err.empty()) return fail("rs_sample_end: " + err);
+    if (!x_0) return fail("rs_sample_end: null tensor (x_0)");
+    return e->run((hipStream_t)a->stream, [&](Exec& ex) { e->sample_epilogue(ex, a, x_0); });
 }
 
 // -------------------------------------------------------------------- op-level test entry points

@@ -126,7 +126,7 @@ __device__ __forceinline__ void rs_gn_tail_finish(const GNTail& t, int img, floa
     for (int c = tid; c < C; c += NT) {
         const int g = c / cpg;
         float a, b;
-        rs_gn_channel(t.gamma[c], t.beta[c], gm[g], gr[g], t.film, c, C, a, b);
+        rs_gn_channel(t.gamma[c], t.beta[c], gm[g], gr[g], t.film ? t.film + (long long)img * t.film_ld : nullptr, c, C, a, b);
         t.coef[((long long)img * 2) * C + c] = a;
         t.coef[((long long)img * 2 + 1) * C + c] = b;
     }

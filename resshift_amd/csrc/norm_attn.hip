@@ -179,10 +179,11 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GNParams p) {
         rs_gn_group(a, q, n, p.eps, gm[tid], gr[tid]);   // (gn_tail.h: the tails use the same expressions)
     }
     __syncthreads();
+    const float* film = p.film ? p.film + (long long)b * p.film_ld : nullptr;   // (this image's FiLM row)
     for (int c = tid; c < p.C; c += 256) {
         const int g = c / cpg;
         float a, bb;
-        rs_gn_channel(p.gamma[c], p.beta[c], gm[g], gr[g], p.film, c, p.C, a, bb);
+        rs_gn_channel(p.gamma[c], p.beta[c], gm[g], gr[g], film, c, p.C, a, bb);
         ca[c] = a; cb[c] = bb;
     }
     __syncthreads();
@@ -253,9 +254,10 @@ __device__ __forceinline__ void gn_fused_body(const GNParams& p, int SC, float (
     }
     __syncthreads();                              // column sums consumed: ca / cb now take the affine coefficients
     if (tid < gps) {
+        const float* film = p.film ? p.film + (long long)b * p.film_ld : nullptr;   // (this image's FiLM row)
         for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) {
             float ga, be;
-            rs_gn_channel(p.gamma[cs + c], p.beta[cs + c], gmean, grstd, p.film, cs + c, p.C, ga, be);
+            rs_gn_channel(p.gamma[cs + c], p.beta[cs + c], gmean, grstd, film, cs + c, p.C, ga, be);
             ca[c] = ga; cb[c] = be;
         }
     }
@@ -348,7 +350,7 @@ extern "C" int rs_groupnorm_launch(const GNParams* pp, int dt, int apply_slabs, 
     // tree of 256 / groups lanes per group - ADVICE r4: enforce what the engine's groups = 32 satisfies by construction)
     const bool use_tail = tail_on && need_stats && p.coef && p.ticket && 2 * p.C + 2 * p.groups <= 4351 && p.groups > 0 && (256 % p.groups) == 0;
     if (use_tail) {
-        tail.gamma = p.gamma; tail.beta = p.beta; tail.film = p.film; tail.coef = p.coef; tail.ticket = p.ticket; tail.expected = p.S;
+        tail.gamma = p.gamma; tail.beta = p.beta; tail.film = p.film; tail.film_ld = p.film_ld; tail.coef = p.coef; tail.ticket = p.ticket; tail.expected = p.S;
         tail.C = p.C; tail.groups = p.groups; tail.HW = p.HW; tail.eps = p.eps; tail.stg = p.partial; tail.Sg = p.S;
     }
     if (dt == RS_F16) {

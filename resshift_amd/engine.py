@@ -208,6 +208,22 @@ class Engine:
         self._chk(rc, "rs_axpbypcz")
         return out
 
+    def axpbypcz_rows(self, x, z, n, a, b, c, out=None):
+        """out[i] = a[i]*x[i] + b[i]*z[i] + c[i]*n[i] per image i of fp32 [B,...] tensors (one coefficient triple per image, B <= RS_MAX_ROWS;
+        c[i] == 0 skips image i's noise term).  Uniform coefficients give bit for bit what `axpbypcz` gives."""
+        x = self._f32c(x)
+        B = x.shape[0]
+        if not (len(a) == len(b) == len(c) == B):
+            raise ValueError(f"axpbypcz_rows: {B} images but {len(a)} / {len(b)} / {len(c)} coefficients")
+        out = torch.empty_like(x) if out is None else out
+        zt = self._f32c(z) if z is not None else None
+        nt = self._f32c(n) if n is not None else None
+        arr = lambda v: (C.c_float * B)(*[float(q) for q in v])
+        rc = self.lib.rs_axpbypcz_rows(x.data_ptr(), zt.data_ptr() if zt is not None else None, nt.data_ptr() if nt is not None else None,
+                                       out.data_ptr(), arr(a), arr(b), arr(c), x.numel() // B, B, self._stream())
+        self._chk(rc, "rs_axpbypcz_rows")
+        return out
+
     def u8_to_input(self, img_u8):
         """uint8 [B,H,W,C] device tensor -> fp32 [B,C,H,W] in [-1,1] (datapipe/datasets.py:59-63 on the device)."""
         assert img_u8.dtype == torch.uint8 and img_u8.dim() == 4 and img_u8.is_cuda
@@ -228,6 +244,93 @@ class Engine:
         rc = self.lib.rs_output_to_u8(sr.data_ptr(), lq_t.data_ptr() if lq_t is not None else None, mk_t.data_ptr() if mk_t is not None else None,
                                       out.data_ptr(), B, H, W, Cc, int(bool(bgr)), self._stream())
         self._chk(rc, "rs_output_to_u8")
+        return out
+
+    def latent_shape(self, B: int, h: int, w: int, sf: int):
+        f = 2 ** (int(self.cfg.ae.n_levels) - 1)
+        return (B, int(self.cfg.ae.embed_dim), h * sf // f, w * sf // f)
+
+    @staticmethod
+    def _schedule(a: "_lib.SampleArgs", tables: Dict[str, np.ndarray], prec_unet=F16) -> None:
+        steps = int(len(tables["coef1"]))
+        pu = [prec_unet] * steps if isinstance(prec_unet, (int, str)) else list(prec_unet)
+        a.steps = steps
+        for t in range(steps):
+            a.inv_std[t] = float(tables["inv_std"][t])
+            a.coef1[t] = float(tables["coef1"][t])
+            a.coef2[t] = float(tables["coef2"][t])
+            a.sigma[t] = float(tables["sigma"][t])
+            a.tmap[t] = int(tables["tmap"][t])
+            a.prec_unet[t] = parse_precision(pu[t])
+        a.prior_scale = float(tables["prior_scale"])
+
+    def sample_begin(self, y, noise, tables: Dict[str, np.ndarray], sf: int, scale_factor: float, prec_encode=F16, out=None):
+        """encode_first_stage(y, up_sample=True) -> prior_sample with the prior draw `noise` [B,Cz,hz,wz]: x_T (rs_sample_begin)."""
+        y, noise = self._f32c(y), self._f32c(noise)
+        B, _, h, w = y.shape
+        zs = self.latent_shape(B, h, w, sf)
+        if tuple(noise.shape) != zs:
+            raise ValueError(f"sample_begin: noise must be {zs}, got {tuple(noise.shape)}")
+        x = torch.empty(zs, device=y.device, dtype=torch.float32) if out is None else out
+        a = _lib.SampleArgs()
+        self._schedule(a, tables)
+        a.y, a.noise, a.B, a.h, a.w, a.sf = y.data_ptr(), noise.data_ptr(), B, h, w, int(sf)
+        a.scale_factor, a.prec_encode, a.prec_decode, a.stream = float(scale_factor), parse_precision(prec_encode), F16, self._stream()
+        with torch.cuda.device(self.device):
+            rc = self.lib.rs_sample_begin(self._h, C.byref(a), x.data_ptr())
+        self._chk(rc, "rs_sample_begin")
+        return x
+
+    def sample_step(self, x, y, t: Sequence[int], noise, tables: Dict[str, np.ndarray], sf: int, mask=None, prec=F16, pred_xstart=None):
+        """One p_sample of every image b at its own step index t[b] (indices into `tables`), x [B,Cz,hz,wz] updated IN PLACE
+        (contiguous fp32); noise [B,Cz,hz,wz] this step's draws (may be None when every t[b] is 0).  Returns x (rs_sample_step)."""
+        if x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+            raise ValueError("sample_step updates x in place: it must be a contiguous float32 device tensor")
+        y = self._f32c(y)
+        B, _, h, w = y.shape
+        if x.shape[0] != B or len(t) != B:
+            raise ValueError(f"sample_step: x has {x.shape[0]} images, y {B}, t {len(t)}")
+        nt = self._f32c(noise) if noise is not None else None
+        mk = self._f32c(mask) if mask is not None else None
+        a = _lib.SampleArgs()
+        self._schedule(a, tables)
+        a.B, a.h, a.w, a.sf = B, h, w, int(sf)
+        s = _lib.StepArgs()
+        s.sched = C.pointer(a)
+        s.x, s.y = x.data_ptr(), y.data_ptr()
+        s.pred_xstart = pred_xstart.data_ptr() if pred_xstart is not None else None
+        s.mask = mk.data_ptr() if mk is not None else None
+        s.noise = nt.data_ptr() if nt is not None else None
+        ts = (C.c_int * B)(*[int(v) for v in t])
+        s.t, s.B, s.prec, s.stream = ts, B, parse_precision(prec), self._stream()
+        with torch.cuda.device(self.device):
+            rc = self.lib.rs_sample_step(self._h, C.byref(s))
+        self._chk(rc, "rs_sample_step")
+        return x
+
+    def film_prewarm(self, timesteps: Sequence[int]):
+        """build the FiLM rows of these network timesteps now (rs_film_prewarm): later steps at them pay no synchronise"""
+        ts = (C.c_int * max(1, len(timesteps)))(*[int(v) for v in timesteps])
+        with torch.cuda.device(self.device):
+            self._chk(self.lib.rs_film_prewarm(self._h, ts, len(timesteps), self._stream()), "rs_film_prewarm")
+
+    def sample_end(self, x0, h: int, w: int, sf: int, scale_factor: float, prec_decode=F16, return_aux=False):
+        """decode_first_stage of the final latents x0 [B,Cz,hz,wz] (LR size h x w): image [B,3,h*sf,w*sf] (rs_sample_end)."""
+        x0 = self._f32c(x0)
+        B = x0.shape[0]
+        out = torch.empty(B, int(self.cfg.ae.out_ch), h * sf, w * sf, device=x0.device, dtype=torch.float32)
+        z_out = torch.empty_like(x0) if return_aux else None
+        idx = torch.empty(x0.numel() // x0.shape[1], device=x0.device, dtype=torch.int32) if return_aux else None
+        a = _lib.SampleArgs()
+        a.out, a.B, a.h, a.w, a.sf = out.data_ptr(), B, h, w, int(sf)
+        a.z_out = z_out.data_ptr() if z_out is not None else None
+        a.idx_out = idx.data_ptr() if idx is not None else None
+        a.scale_factor, a.prec_encode, a.prec_decode, a.stream = float(scale_factor), F16, parse_precision(prec_decode), self._stream()
+        with torch.cuda.device(self.device):
+            rc = self.lib.rs_sample_end(self._h, C.byref(a), x0.data_ptr())
+        self._chk(rc, "rs_sample_end")
+        if return_aux:
+            return out, {"z_final": z_out, "indices": idx}
         return out
 
     def sample(self, y, noise, tables: Dict[str, np.ndarray], sf: int, scale_factor: float, mask=None, prec_unet=F16, prec_encode=F16,

@@ -7,7 +7,9 @@ API (`p_sample_loop`, `p_sample_loop_progressive`, `p_sample`, `p_mean_variance`
 Schedule constants are computed in float64 numpy exactly like the reference; all tensor work is done by
 the HIP engine.  When `model` / `first_stage_model` are the engine-backed `UNetModelSwin` /
 `VQModelTorch`, `p_sample_loop` runs the whole loop in ONE native call (`rs_sample`).
-Training-side methods (q_sample, training_losses) are out of scope.
+Per-sample timesteps are honoured as the reference's `_extract_into_tensor` does (gaussian_diffusion.py:92-105): a `t` whose entries
+differ runs the per-image elementwise kernel (`rs_axpbypcz_rows`) and a mixed-timestep UNet call; a uniform `t` keeps the scalar calls.
+`q_sample` (the forward process, :190-208) is provided; `training_losses` is out of scope.
 """
 from __future__ import annotations
 
@@ -130,6 +132,49 @@ class ResShiftDiffusion:
         for m in (model, ae):
             m._engine, m._engine_version = engine, params_version(m)
 
+    # ---- per-sample coefficient rows (_extract_into_tensor: the float64 table entry of each sample's t, as float32)
+    @staticmethod
+    def _t_list(t, B: int):
+        """`t` (int, sequence or tensor of step indices) -> one int per sample"""
+        if torch.is_tensor(t):
+            v = [int(q) for q in t.reshape(-1).tolist()]
+        elif isinstance(t, (list, tuple, np.ndarray)):
+            v = [int(q) for q in t]
+        else:
+            v = [int(t)]
+        if len(v) == 1:
+            v = v * B
+        if len(v) != B:
+            raise ValueError(f"{len(v)} timesteps for a batch of {B}")
+        return v
+
+    def scale_input_coefs(self, ts):
+        """per sample: 1 / std of _scale_input (:598-609)"""
+        return [float(self.step_tables()["inv_std"][i]) for i in ts]
+
+    def posterior_coefs(self, ts):
+        """per sample: (posterior_mean_coef1, posterior_mean_coef2, sqrt(posterior variance) or 0 at t = 0) (:210-221,358-364)"""
+        tab = self.step_tables()
+        return ([float(tab["coef1"][i]) for i in ts], [float(tab["coef2"][i]) for i in ts],
+                [float(tab["sigma"][i]) if i != 0 else 0.0 for i in ts])
+
+    def q_sample_coefs(self, ts):
+        """per sample: (1 - eta_t, eta_t, kappa * sqrt(eta_t)) of q_sample (:190-208)"""
+        f32 = lambda v: float(np.float32(v))
+        return ([f32(1.0 - self.etas[i]) for i in ts], [f32(self.etas[i]) for i in ts], [f32(self.kappa * self.sqrt_etas[i]) for i in ts])
+
+    @staticmethod
+    def _rows(x, z, n, a, b, c, engine=None):
+        """per-image a[i]*x[i] + b[i]*z[i] + c[i]*n[i] on the engine's kernel (rs_axpbypcz_rows); no CPU path, as _axpbypcz"""
+        if engine is None or not x.is_cuda:
+            raise RuntimeError("step-wise sampling needs the HIP engine (engine-backed UNetModelSwin on a GPU); no CPU fallback")
+        return engine.axpbypcz_rows(x, z, n, a, b, c).to(x.dtype)
+
+    def _any_engine(self):
+        for eng, _ in self._fused.values():
+            return eng
+        raise RuntimeError("q_sample needs the HIP engine: pass engine= or build the sampler's models first; no CPU fallback")
+
     # ---- reference API
     @staticmethod
     def _axpbypcz(x, z, n, a, b, c, engine=None):
@@ -140,9 +185,23 @@ class ResShiftDiffusion:
         return engine.axpbypcz(x, z, n, a, b, c).to(x.dtype)
 
     def _scale_input(self, inputs, t, engine=None):
+        ts = self._t_list(t, inputs.shape[0])
+        if len(set(ts)) > 1:
+            return self._rows(inputs, None, None, self.scale_input_coefs(ts), [0.0] * len(ts), [0.0] * len(ts), engine)
         tab = self.step_tables()["inv_std"]
-        ti = int(t[0]) if torch.is_tensor(t) else int(t)
+        ti = ts[0]
         return self._axpbypcz(inputs, None, None, float(tab[ti]), 0.0, 0.0, engine)
+
+    def q_sample(self, x_start, y, t, noise=None, engine=None):
+        """gaussian_diffusion.py:190-208: x_t = (1 - eta_t) x_0 + eta_t y + kappa sqrt(eta_t) noise, per sample"""
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        engine = engine if engine is not None else self._any_engine()
+        ts = self._t_list(t, x_start.shape[0])
+        a, b, c = self.q_sample_coefs(ts)
+        if len(set(ts)) > 1:
+            return self._rows(x_start, y, noise, a, b, c, engine)
+        return self._axpbypcz(x_start, y, noise, a[0], b[0], c[0], engine)
 
     def prior_sample(self, y, noise=None, engine=None):
         if noise is None:
@@ -150,7 +209,14 @@ class ResShiftDiffusion:
         return self._axpbypcz(y, None, noise, 1.0, 0.0, float(np.float32(self.kappa * self.sqrt_etas[-1])), engine)
 
     def q_posterior_mean_variance(self, x_start, x_t, t, engine=None):
-        ti = int(t[0]) if torch.is_tensor(t) else int(t)
+        ts = self._t_list(t, x_t.shape[0])
+        if len(set(ts)) > 1:
+            c1, c2, _ = self.posterior_coefs(ts)
+            mean = self._rows(x_t, x_start, None, c1, c2, [0.0] * len(ts), engine)
+            per = lambda arr: torch.tensor([float(np.float32(arr[i])) for i in ts], dtype=torch.float32,
+                                           device=x_t.device).view(-1, *[1] * (x_t.dim() - 1)).expand_as(x_t).clone()
+            return mean, per(self.posterior_variance), per(self.posterior_log_variance_clipped)
+        ti = ts[0]
         tab = self.step_tables()
         mean = self._axpbypcz(x_t, x_start, None, float(tab["coef1"][ti]), float(tab["coef2"][ti]), 0.0, engine)
         var = torch.full_like(x_t, float(np.float32(self.posterior_variance[ti])))
@@ -180,14 +246,18 @@ class ResShiftDiffusion:
         return first_stage_model.decode(z_sample, prec=self._prec(self.precision_decode))
 
     def p_mean_variance(self, model, x_t, y, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
-        """gaussian_diffusion.py:234-307 (START_X).  `t`: [B] tensor of equal indices."""
+        """gaussian_diffusion.py:234-307 (START_X).  `t`: [B] step indices, equal or not."""
         model_kwargs = model_kwargs or {}
-        ti = int(t[0])
-        prec = self._unet_precisions()[ti]
-        ts = [self.timestep_map[ti]] * x_t.shape[0]  # _WrappedModel (respace.py:67-70)
+        tl = self._t_list(t, x_t.shape[0])
+        precs = {self._unet_precisions()[i] for i in tl}
+        if len(precs) > 1:
+            raise NotImplementedError("a batch whose steps run the UNet at different precisions (per-step mixed precision policy)")
+        prec = precs.pop()
+        ts = [self.timestep_map[i] for i in tl]  # _WrappedModel (respace.py:67-70)
         if not isinstance(model, UNetModelSwin):
             raise NotImplementedError("p_mean_variance drives the engine-backed UNetModelSwin only")
         eng = model.engine()
+        ti = tl[0] if len(set(tl)) == 1 else tl
         pred = model(self._scale_input(x_t, ti, eng), ts, prec=prec, **model_kwargs)
         if denoised_fn is not None:
             pred = denoised_fn(pred)
@@ -203,9 +273,14 @@ class ResShiftDiffusion:
             noise = torch.randn_like(x)
         if noise_repeat:
             noise = noise[0,].repeat(x.shape[0], 1, 1, 1)
-        ti = int(t[0])
-        sigma = float(self.step_tables()["sigma"][ti]) if ti != 0 else 0.0
+        tl = self._t_list(t, x.shape[0])
         eng = model.engine() if isinstance(model, UNetModelSwin) else None
+        if len(set(tl)) > 1:
+            sig = self.posterior_coefs(tl)[2]   # (nonzero_mask: no noise at t = 0)
+            sample = self._rows(out["mean"], None, noise, [1.0] * len(tl), [0.0] * len(tl), sig, eng)
+            return {"sample": sample, "pred_xstart": out["pred_xstart"], "mean": out["mean"]}
+        ti = tl[0]
+        sigma = float(self.step_tables()["sigma"][ti]) if ti != 0 else 0.0
         sample = self._axpbypcz(out["mean"], None, noise, 1.0, 0.0, sigma, eng)
         return {"sample": sample, "pred_xstart": out["pred_xstart"], "mean": out["mean"]}
 
