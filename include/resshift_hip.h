@@ -192,7 +192,8 @@ int rs_output_to_u8(const float* sr_f32_nchw, const float* lq_f32_nchw, const fl
                     int W, int C, int bgr, void* stream);
 
 /* ---- introspection --------------------------------------------------------------------------- */
-/* bytes of scratch arena currently allocated; number of kernel launches issued by the last call */
+/* bytes of scratch arena currently allocated; number of kernel launches issued by the last call (the network's own: a debug
+ * trace's capture copies are not counted) */
 size_t rs_arena_bytes(rs_engine* e);
 long long rs_last_launch_count(rs_engine* e);
 /* profiling of the MFMA implicit-GEMM kernel family: when enabled every igemm launch of the next call is
@@ -209,8 +210,15 @@ int rs_profile_get(rs_engine* e, double* out9);
  * fused Swin MLP, and the split-storage variants of those two.  out[3 f + 0] = algorithmic FLOPs, [3 f + 1] = kernel milliseconds,
  * [3 f + 2] = launches; returns the number of families (9) or -1 when cap < 27. */
 int rs_profile_families(rs_engine* e, double* out, int cap);
-/* debug trace (tests only): when enabled, the next network call records named intermediate activations
- * (scratch is not recycled while enabled); fetch converts entry i to NCHW fp32 into caller memory. */
+/* debug trace (tests only): while enabled, every network call records named intermediate activations.  A record copies
+ * the tensor, on the call's stream at the point where it is produced, into a capture region of the trace (dense fp32 NCHW); the traced
+ * call runs the same kernels with the same parameters and scratch layout as an untraced one, and a fused path has no record for a tensor
+ * it never stores.  The capture region is allocated while tracing is on only (rs_debug_enable(e, 0) frees it), apart from the scratch
+ * arena.  UNet names: in.0, in.N, in.N.res (blocks with Swin), mid.res1, mid.swin, mid.res2, out.J, out.J.res (blocks with Swin or
+ * upsampling), out.J.swin (Swin followed by upsampling); inner records (conv1, embed, blkK.qkv / attn / proj / out) carry their block's
+ * name as prefix: in.N.res.conv1, mid.swin.embed, out.J.swin.blk1.out ...  rs_debug_count = records of the last call (= its capture
+ * copies); rs_last_launch_count counts the network's launches only, never the capture copies.  fetch copies record i into caller memory
+ * (B*C*H*W floats, stream-ordered after the call). */
 /* text table of the last profiled call: per (part, kernel family, M, N, K) launch shape of the MFMA family - launches, summed kernel ms
  * (hipEvents on the launch stream), algorithmic flops - and the wall ms of the encoder / UNet / decoder parts (measurement, d of SURVEY 8:
  * where a pass's time goes per reference module - ldm/modules/diffusionmodules/model.py Encoder / Decoder, models/unet.py UNetModelSwin).

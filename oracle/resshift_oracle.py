@@ -1,6 +1,6 @@
 """ORACLE — test infrastructure only.  Never imported by the product (resshift_amd/).
 
-A CPU, fp32, functional restatement of the reference's sampling hot path, driven directly by a
+A CPU, fp32 (float64 when given float64 inputs and a float64 ``state_dict``), functional restatement of the reference's sampling hot path, driven directly by a
 reference-format ``state_dict`` (plain dict name -> tensor) and the YAML ``params`` blocks.  Only
 ``tests/``, ``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of ``bench.py`` may import it.
 
@@ -17,7 +17,7 @@ reference itself has no tests or golden vectors for this path.
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -32,8 +32,8 @@ def _listify(v, n):
 
 
 def _gn(sd: SD, name: str, x: torch.Tensor, eps: float) -> torch.Tensor:
-    # models/basic_ops.py:15-17,96 (GroupNorm32, 32 groups, fp32) / model.py:46-47 (eps 1e-6)
-    return F.group_norm(x.float(), 32, sd[name + ".weight"], sd[name + ".bias"], eps)
+    # models/basic_ops.py:15-17,96 (GroupNorm32, 32 groups, fp32) / model.py:46-47 (eps 1e-6); a float64 input stays float64
+    return F.group_norm(x if x.dtype == torch.float64 else x.float(), 32, sd[name + ".weight"], sd[name + ".bias"], eps)
 
 
 def _conv(sd: SD, name: str, x: torch.Tensor, stride: int = 1, padding: int = 0) -> torch.Tensor:
@@ -44,11 +44,11 @@ def _linear(sd: SD, name: str, x: torch.Tensor) -> torch.Tensor:
     return F.linear(x, sd[name + ".weight"], sd[name + ".bias"])
 
 
-def timestep_embedding(t: torch.Tensor, dim: int, max_period: float = 10000.0) -> torch.Tensor:
+def timestep_embedding(t: torch.Tensor, dim: int, max_period: float = 10000.0, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     # models/basic_ops.py:99-117 — cos first, then sin
     half = dim // 2
-    freqs = torch.exp(-math.log(max_period) * torch.arange(0, half, dtype=torch.float32) / half).to(t.device)
-    args = t[:, None].float() * freqs[None]
+    freqs = torch.exp(-math.log(max_period) * torch.arange(0, half, dtype=dtype) / half).to(t.device)
+    args = t[:, None].to(dtype) * freqs[None]
     emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
     if dim % 2:
         emb = torch.cat([emb, torch.zeros_like(emb[:, :1])], dim=-1)
@@ -146,59 +146,110 @@ def res_block(sd: SD, name: str, x: torch.Tensor, emb: torch.Tensor) -> torch.Te
     return skip + h
 
 
-def unet_forward(sd: SD, p: dict, x: torch.Tensor, t: torch.Tensor, lq: Optional[torch.Tensor] = None,
-                 mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """models/unet.py:865-895 UNetModelSwin.forward; block plan re-derived as in :704-863."""
+class Step(NamedTuple):
+    """One step of the UNet's block plan: ``out = fn(*inputs)``.  ``name`` is the engine's debug-trace name of the step's output
+    (``emb`` and ``head`` are not traced: the FiLM embedding and the network output); ``inputs`` are names of earlier steps or of the
+    host inputs ``x``, ``t``, ``lq``, ``mask``."""
+    name: str
+    inputs: Tuple[str, ...]
+    fn: Callable[..., torch.Tensor]
+
+
+def unet_plan(sd: SD, p: dict, with_lq: bool = True, with_mask: bool = False) -> List[Step]:
+    """models/unet.py:865-895 UNetModelSwin.forward as a sequence of named blocks (construction order re-derived as in :704-863):
+    ``emb``, ``in.0`` (feature extractor and mask concat included), ``in.N`` (``in.N.res`` before the Swin layer of a block that has
+    one), ``mid.res1``, ``mid.swin``, ``mid.res2``, ``out.J`` (``out.J.res`` before the Swin layer or the upsampling conv, ``out.J.swin``
+    before the upsampling conv), ``head``.  The skip-stack order and the decoder-first concatenation live here only."""
     mc = int(p["model_channels"])
     mult = [int(m) for m in p.get("channel_mult", (1, 2, 4, 8))]
     nrb = _listify(p["num_res_blocks"], len(mult))
     attn_res = [int(a) for a in p["attention_resolutions"]]
-    emb = _linear(sd, "time_embed.2", F.silu(_linear(sd, "time_embed.0", timestep_embedding(t, mc))))
-    if lq is not None:
-        if mask is not None:
-            lq = torch.cat([lq, mask], dim=1)
-        ii = 0
-        while f"feature_extractor.{3 * ii}.weight" in sd:  # unet.py:693-702 (Identity when absent)
-            lq = F.silu(_conv(sd, f"feature_extractor.{3 * ii}", lq, padding=1))
-            lq = _conv(sd, f"feature_extractor.{3 * ii + 2}.op", lq, stride=2, padding=1)
-            ii += 1
-        x = torch.cat([x, lq], dim=1)
-    hs: List[torch.Tensor] = []
-    h = _conv(sd, "input_blocks.0.0", x, padding=1)
-    hs.append(h)
+    dt = sd["time_embed.0.weight"].dtype
+    plan: List[Step] = []
+
+    def emb_fn(t):
+        return _linear(sd, "time_embed.2", F.silu(_linear(sd, "time_embed.0", timestep_embedding(t, mc, dtype=dt))))
+
+    plan.append(Step("emb", ("t",), emb_fn))
+
+    def in0(x, lq=None, mask=None):
+        if lq is not None:
+            if mask is not None:
+                lq = torch.cat([lq, mask], dim=1)
+            ii = 0
+            while f"feature_extractor.{3 * ii}.weight" in sd:  # unet.py:693-702 (Identity when absent)
+                lq = F.silu(_conv(sd, f"feature_extractor.{3 * ii}", lq, padding=1))
+                lq = _conv(sd, f"feature_extractor.{3 * ii + 2}.op", lq, stride=2, padding=1)
+                ii += 1
+            x = torch.cat([x, lq], dim=1)
+        return _conv(sd, "input_blocks.0.0", x, padding=1)
+
+    plan.append(Step("in.0", ("x",) + (("lq",) if with_lq else ()) + (("mask",) if with_lq and with_mask else ()), in0))
+    hs = ["in.0"]   # the skip stack, by name
+    prev = "in.0"
     n = 1
     ds = int(p["image_size"])
     for level in range(len(mult)):
         for jj in range(nrb[level]):
-            h = res_block(sd, f"input_blocks.{n}.0", h, emb)
+            blk = f"input_blocks.{n}"
+            res = (lambda b: lambda h, emb: res_block(sd, b + ".0", h, emb))(blk)
             if ds in attn_res and jj == 0:
-                h = basic_layer(sd, f"input_blocks.{n}.1", h, p, ds)
-            hs.append(h)
+                plan.append(Step(f"in.{n}.res", (prev, "emb"), res))
+                plan.append(Step(f"in.{n}", (f"in.{n}.res",), (lambda b, d: lambda h: basic_layer(sd, b + ".1", h, p, d))(blk, ds)))
+            else:
+                plan.append(Step(f"in.{n}", (prev, "emb"), res))
+            prev = f"in.{n}"
+            hs.append(prev)
             n += 1
         if level != len(mult) - 1:
-            h = _conv(sd, f"input_blocks.{n}.0.op", h, stride=2, padding=1)  # unet.py:97-101
-            hs.append(h)
+            plan.append(Step(f"in.{n}", (prev,), (lambda b: lambda h: _conv(sd, b, h, stride=2, padding=1))(f"input_blocks.{n}.0.op")))  # unet.py:97-101
+            prev = f"in.{n}"
+            hs.append(prev)
             n += 1
             ds //= 2
-    h = res_block(sd, "middle_block.0", h, emb)
-    h = basic_layer(sd, "middle_block.1", h, p, ds)
-    h = res_block(sd, "middle_block.2", h, emb)
+    plan.append(Step("mid.res1", (prev, "emb"), lambda h, emb: res_block(sd, "middle_block.0", h, emb)))
+    plan.append(Step("mid.swin", ("mid.res1",), (lambda d: lambda h: basic_layer(sd, "middle_block.1", h, p, d))(ds)))
+    plan.append(Step("mid.res2", ("mid.swin", "emb"), lambda h, emb: res_block(sd, "middle_block.2", h, emb)))
+    prev = "mid.res2"
     n = 0
     for level in reversed(range(len(mult))):
         for i in range(nrb[level] + 1):
-            h = torch.cat([h, hs.pop()], dim=1)  # decoder features first (unet.py:891)
-            sub = 0
-            h = res_block(sd, f"output_blocks.{n}.{sub}", h, emb)
-            sub += 1
-            if ds in attn_res and i == 0:
-                h = basic_layer(sd, f"output_blocks.{n}.{sub}", h, p, ds)
+            blk, nm = f"output_blocks.{n}", f"out.{n}"
+            swin = ds in attn_res and i == 0
+            up = bool(level) and i == nrb[level]
+            # decoder features first (unet.py:891)
+            res = (lambda b: lambda h, skip, emb: res_block(sd, b + ".0", torch.cat([h, skip], dim=1), emb))(blk)
+            cur = nm if not (swin or up) else nm + ".res"
+            plan.append(Step(cur, (prev, hs.pop(), "emb"), res))
+            sub = 1
+            if swin:
+                nxt = nm + ".swin" if up else nm
+                plan.append(Step(nxt, (cur,), (lambda b, d: lambda h: basic_layer(sd, b, h, p, d))(f"{blk}.{sub}", ds)))
+                cur = nxt
                 sub += 1
-            if level and i == nrb[level]:
-                h = F.interpolate(h, scale_factor=2, mode="nearest")  # unet.py:78
-                h = _conv(sd, f"output_blocks.{n}.{sub}.conv", h, padding=1)
+            if up:
+                def upconv(h, b=f"{blk}.{sub}.conv"):
+                    return _conv(sd, b, F.interpolate(h, scale_factor=2, mode="nearest"), padding=1)  # unet.py:78
+                plan.append(Step(nm, (cur,), upconv))
                 ds *= 2
+            prev = nm
             n += 1
-    return _conv(sd, "out.2", F.silu(_gn(sd, "out.0", h, 1e-5)), padding=1)
+    plan.append(Step("head", (prev,), lambda h: _conv(sd, "out.2", F.silu(_gn(sd, "out.0", h, 1e-5)), padding=1)))
+    return plan
+
+
+def run_plan(plan: Sequence[Step], env: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Chain the steps of a plan from the host inputs in ``env``; returns ``env`` with every step's output added."""
+    for s in plan:
+        env[s.name] = s.fn(*[env[i] for i in s.inputs])
+    return env
+
+
+def unet_forward(sd: SD, p: dict, x: torch.Tensor, t: torch.Tensor, lq: Optional[torch.Tensor] = None,
+                 mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """models/unet.py:865-895 UNetModelSwin.forward: the block plan (unet_plan) chained."""
+    plan = unet_plan(sd, p, with_lq=lq is not None, with_mask=mask is not None)
+    return run_plan(plan, {"x": x, "t": t, "lq": lq, "mask": mask})["head"]
 
 
 # ----------------------------------------------------------------------------- VQModelTorch

@@ -213,9 +213,10 @@ struct TailPlan {
     mutable bool drawn = false;   // (real pass: the producer's launch attached the tail - checked against the plan at the end of the call)
 };
 
+struct TraceRec { std::string name; int B = 0, C = 0, H = 0, W = 0; size_t off = 0; };   // (one debug-trace record: Exec::tr)
+
 struct Exec {
     hipStream_t st = nullptr; Arena* arena = nullptr; bool dry = false; long long launches = 0; int err = 0;
-    bool dbg = false;                        // debug trace requested (both passes): no statistics fusion, no tails
     std::vector<TailPlan>* plan = nullptr;   // by producer sequence number
     int prod_seq = 0, gn_seq = 0;
     // FiLM rows of the network body being walked (unet_body): one row shared by the batch (film_ld 0) or a per-image table [B][film_ld]
@@ -255,11 +256,26 @@ struct Exec {
     }
     void* raw(size_t bytes) { return arena->alloc(bytes); }
     size_t mark() const { return arena->off; }
-    bool keep = false;  // debug trace: never recycle scratch so that every recorded view stays valid
-    std::vector<std::pair<std::string, View>>* trace = nullptr;
+    // Debug trace (rs_debug_enable): a record copies the view, on the pass's stream and at the point of the graph where it is recorded, into
+    // the trace's own capture region as dense fp32 NCHW.  The region is sized by the dry pass and lives outside the scratch arena, the
+    // coefficient pool and the tickets, so a traced pass runs exactly the kernels, parameters and scratch layout of an untraced one; the
+    // copies are counted in trace_copies, not in `launches`.  A fused path has no record for a tensor it never stores.
+    bool tracing = false;
+    std::vector<TraceRec>* trace = nullptr;
+    char* cap_base = nullptr; size_t cap_off = 0; long long trace_copies = 0;
     std::string prefix;
-    void reset(size_t m) { if (!keep) arena->off = m; }
-    void tr(const std::string& name, const View& v) { if (trace && !dry) trace->emplace_back(prefix + name, v); }
+    void reset(size_t m) { arena->off = m; }
+    void tr(const std::string& name, const View& v) {
+        if (!tracing) return;
+        cap_off = (cap_off + 255) & ~(size_t)255;
+        const size_t o = cap_off;
+        cap_off += (size_t)v.B * v.C * v.H * v.W * sizeof(float);
+        if (dry) return;
+        trace->push_back(TraceRec{prefix + name, v.B, v.C, v.H, v.W, o});
+        ++trace_copies;
+        const int rc = rs_nhwc_to_nchw_launch(v.p, v.dt, (float*)(cap_base + o), v.B, v.C, v.H * v.W, v.ld, 0, st);
+        if (rc != 0 && err == 0) { err = rc; g_err = "launch failed: debug trace copy of " + prefix + name; }
+    }
     void check(int rc, const char* what) {
         ++launches;
         if (rc != 0 && err == 0) { err = rc; g_err = std::string("launch failed: ") + what; }
@@ -458,7 +474,12 @@ struct rs_engine {
     std::string last_shapes;                  // rs_profile_shapes: one line per (part, family, M, N, K) and per part of the last profiled call
     long long last_igemm_launches = 0, last_gn_launches = 0;
     bool debug = false;
-    std::vector<std::pair<std::string, View>> trace;
+    std::vector<TraceRec> trace;                        // records of the last traced call (Exec::tr)
+    char* cap_base = nullptr; size_t cap_bytes = 0; bool cap_host = false;   // their capture region (run(); freed by rs_debug_enable(0))
+    void free_capture() {
+        if (cap_base) { if (cap_host) free(cap_base); else (void)hipFree(cap_base); }
+        cap_base = nullptr; cap_bytes = 0; trace.clear();
+    }
     std::vector<TailPlan> tail_plan;   // made by the dry pass of a call, read by its real pass (Exec::plan)
     // UNet
     std::vector<UBlock> in_blocks, out_blocks;
@@ -652,7 +673,7 @@ struct rs_engine {
     // the four launches of the sub-pixel form: x [B,H,W,C] -> y [B,2H,2W,C].  Taken when the low-resolution grid alone fills the chip
     // (the 8 x 8 -> 16 x 16 and 16 x 16 -> 32 x 32 steps at batch 32 do not: they keep the folded-address form).
     bool upfold_ok(const Exec& ex, const ConvW (&upf)[4], const View& x, const View& y) const {
-        if (ex.dbg || x.dt != y.dt || (x.dt != RS_F16 && x.dt != RS_F16S) || y.H != 2 * x.H || y.W != 2 * x.W || x.C != upf[0].CinP) return false;
+        if (x.dt != y.dt || (x.dt != RS_F16 && x.dt != RS_F16S) || y.H != 2 * x.H || y.W != 2 * x.W || x.C != upf[0].CinP) return false;
         if (!upf[0].w_for(x.dt) || (x.ld % 8) || (y.ld % 8)) return false;   // (the scattered-row launches' alignment preconditions)
         // (measured, profiles/r5_upfold_ab.txt: with the 16 -> 32 and 8 -> 16 steps as well - 8192 / 2048 low-resolution pixels at batch 32, four
         // launches that cannot fill the chip each - the pass is 0.9 ms slower than with the 32 -> 64 step alone)
@@ -664,7 +685,7 @@ struct rs_engine {
         static const bool on = []() { const char* e = getenv("RS_GN_EPI_STATS"); return !(e && e[0] == '0'); }();
         static const bool gen = []() { const char* e = getenv("RS_GN_GEN_STATS"); return !(e && e[0] == '0'); }();
         y.st = nullptr; y.st2 = nullptr; y.st_prod = -1;
-        if (!on || !gen || ex.dbg || x.dt != RS_F16S || y.dt != RS_F16S) return;
+        if (!on || !gen || x.dt != RS_F16S || y.dt != RS_F16S) return;
         View yl = y; yl.H = x.H; yl.W = x.W;
         const IGemmParams pp = conv_params(upf[0], x, nullptr, yl, 1, 1, 1, 1, 0, nullptr, 1.f);
         const int spx = rs_igemm_split_stats_px(&pp, 1);
@@ -1103,7 +1124,7 @@ struct rs_engine {
         static const bool on = []() { const char* e = getenv("RS_SKIP_FOLD"); return !(e && e[0] == '0'); }();
         static const bool fold = []() { const char* e = getenv("RS_GN_CONV_FOLD"); return !(e && e[0] == '0'); }();
         static const bool on16 = []() { const char* e = getenv("RS_SKIP_FOLD_F16"); return !(e && e[0] == '0'); }();   // (fp16 storage: the decoder's nin_shortcuts, the fp16 policy's UNet)
-        if (!on || !fold || ex.dbg || !r.has_skip || (X.dt != RS_F16S && !(X.dt == RS_F16 && on16)) || Y.dt != X.dt) return false;
+        if (!on || !fold || !r.has_skip || (X.dt != RS_F16S && !(X.dt == RS_F16 && on16)) || Y.dt != X.dt) return false;
         if (X.dt == RS_F16S && (big(r.skip) || big(r.c2))) return false;
         if (!r.skip.w_for(X.dt) || r.skip.KH != 1 || X.C != r.skip.CinP || (X.C % 32) || (X.ld % 8) || X.H != Y.H || X.W != Y.W) return false;
         int sk = 1, seg = 0;
@@ -1119,7 +1140,7 @@ struct rs_engine {
         static const bool gen = []() { const char* e = getenv("RS_GN_GEN_STATS"); return !(e && e[0] == '0'); }();
         const int HW = y.H * y.W;
         y.st = nullptr; y.st2 = nullptr; y.st_prod = -1;
-        if (!on || ex.dbg || w.direct) return;
+        if (!on || w.direct) return;
         const IGemmParams pp = conv_params(w, x, nullptr, y, stride, pad, pad, up, 0, res, 1.f);
         int spx = 0;
         bool wino = false;
@@ -1137,7 +1158,7 @@ struct rs_engine {
     void gn_silu_conv3(Exec& ex, const GNW& g, const ConvW& w, const View& X, const View& Y, float eps, const float* film, const View* res,
                        const ConvW* skw = nullptr, const View* skx = nullptr) {
         static const bool fold = []() { const char* e = getenv("RS_GN_CONV_FOLD"); return !(e && e[0] == '0'); }();
-        if (fold && !ex.dbg && halo_conv(w, X, Y, res, nullptr, nullptr, skw != nullptr)) {
+        if (fold && halo_conv(w, X, Y, res, nullptr, nullptr, skw != nullptr)) {
             const float* coef = gn_coef(ex, g, X, eps, film);
             conv3(ex, w, X, Y, res, 0, coef, RS_ACT_SILU, skw, skx);
             return;
@@ -1148,11 +1169,11 @@ struct rs_engine {
         conv3(ex, w, t, Y, res);
     }
     // GroupNorm + SiLU + conv3x3 to <= 4 channels (the UNet's `out`, Encoder / Decoder norm_out + conv_out) -> fp32 NHWC `o`: one fused pass
-    // (gn_silu_head_conv_kernel) over the raw tensor with the GroupNorm as coefficients; RS_HEAD_FUSED=0 or a debug trace: normalise, then
+    // (gn_silu_head_conv_kernel) over the raw tensor with the GroupNorm as coefficients; RS_HEAD_FUSED=0: normalise, then
     // the implicit-GEMM conv (the round-3 path)
     void head(Exec& ex, const GNW& g, const ConvW& w, const View& X, const View& o, float eps) {
         static const bool fused = []() { const char* e = getenv("RS_HEAD_FUSED"); return !(e && e[0] == '0'); }();
-        if (fused && !ex.dbg && w.wd && !w.direct && o.dt == RS_F32 && X.C == w.Cin && (X.C % 8) == 0 && (X.ld % 8) == 0 && w.Cout <= 4) {
+        if (fused && w.wd && !w.direct && o.dt == RS_F32 && X.C == w.Cin && (X.C % 8) == 0 && (X.ld % 8) == 0 && w.Cout <= 4) {
             const float* coef = gn_coef(ex, g, X, eps, nullptr);
             if (!ex.dry) ex.check(rs_head_conv_launch(X.p, X.dt, coef, w.wd, w.bias, (float*)o.p, X.B, X.H, X.W, X.C, X.ld, w.Cout, o.ld, ex.st), "head conv");
             return;
@@ -1174,7 +1195,7 @@ struct rs_engine {
         static const bool tails = []() { const char* e = getenv("RS_GN_TAIL"); return !(e && e[0] == '0'); }();
         float* coef = ex.pool((size_t)x.B * 2 * x.C * sizeof(float));
         const int me = ex.gn_seq++;
-        if (tails && !ex.dbg && x.st && x.st_prod >= 0 && ex.plan && x.C <= 1280) {
+        if (tails && x.st && x.st_prod >= 0 && ex.plan && x.C <= 1280) {
             std::vector<TailPlan>& pl = *ex.plan;
             if (ex.dry) {
                 if ((int)pl.size() <= x.st_prod) pl.resize(x.st_prod + 1);
@@ -1281,14 +1302,14 @@ struct rs_engine {
         for (const SwinBlockW& s : b.blocks) {
             const std::string bp = "blk" + std::to_string(bi++) + ".";
             // fp16 storage: qkv projection fused into the attention kernel (the [M][3E] tensor never reaches HBM); RS_ATTN_FUSED=0
-            // and the debug trace (which records qkv) keep the two launches.  RS_GN_FOLD (default on): the fused consumer kernels
+            // keeps the two launches.  RS_GN_FOLD (default on): the fused consumer kernels
             // also apply the GroupNorm affine while they load their input, so norm1 / norm2 only produce [B][2][E] coefficients.
             static const int attn_fused = []() { const char* v = getenv("RS_ATTN_FUSED"); return v ? atoi(v) : 2; }();
             static const int gn_fold = []() { const char* v = getenv("RS_GN_FOLD"); return v ? atoi(v) : 1; }();
             // split storage: the same fusion in win_attn_split.hip (RS_ATTN_FUSED_SPLIT=0: separate qkv GEMM, attention, projection GEMM)
             static const int attn_fused_split = []() { const char* v = getenv("RS_ATTN_FUSED_SPLIT"); return v ? atoi(v) : 1; }();
             const bool big_attn = X.dt == RS_F16S && (big(s.qkv) || big(s.proj)), big_mlp = X.dt == RS_F16S && (big(s.fc1) || big(s.fc2));   // (|w| >= 30: unfused path)
-            const bool fuse_qkv = rs_win_attn_qkv_supported(heads, E) && s.bias_n && !ex.dbg && !big_attn &&
+            const bool fuse_qkv = rs_win_attn_qkv_supported(heads, E) && s.bias_n && !big_attn &&
                                   ((attn_fused && X.dt == RS_F16 && s.qkv.wh_frag) || (attn_fused_split && X.dt == RS_F16S && s.qkv.ws_frag && s.proj.ws_frag));
             const bool fold1 = fuse_qkv && gn_fold;
             View n;
@@ -1311,7 +1332,7 @@ struct rs_engine {
             const int Mtok = X.B * X.H * X.W, HWt = X.H * X.W;
             const bool fuse_mlp = mlp_fused && !big_mlp && (X.dt == RS_F16 || (X.dt == RS_F16S && (mlp_fused & 2))) && rs_swin_mlp_supported(E, s.fc1.Cout) &&
                                   s.fc2.Cout == E && Mtok >= mlp_minm && s.fc1.w_for(X.dt) && s.fc2.w_for(X.dt);
-            const bool fold2 = fuse_mlp && gn_fold && !ex.dbg && HWt % 128 == 0;
+            const bool fold2 = fuse_mlp && gn_fold && HWt % 128 == 0;
             // The fused kernels' epilogues leave the statistics of their outputs for the GroupNorm that reads them (attention -> norm2: one
             // partial set per window; MLP -> the next block's norm1: one per 128-token tile) and - round 4 - the launch that completes an
             // image's statistics writes that GroupNorm's coefficients (tail): no pass over those tensors, no coefficient launch.
@@ -1319,7 +1340,7 @@ struct rs_engine {
             //   fp16 storage: never (round 3's form - statistics only, coefficient kernel - measured slower than the passes it removes,
             //   profiles/r3_negative_results.txt; its knob left the tree in round 5).
             static const bool swin_stats_split = []() { const char* v = getenv("RS_GN_SWIN_STATS_SPLIT"); return !(v && v[0] == '0'); }();
-            const bool sstats = X.dt == RS_F16S && swin_stats_split && !ex.dbg;
+            const bool sstats = X.dt == RS_F16S && swin_stats_split;
             if (fuse_proj && sstats && fold2) {   // (only where norm2 is a coefficient-only GroupNorm: the fused MLP applies it)
                 e2.stS = (X.H / 8) * (X.W / 8); e2.stld = E;
                 e2.st = ex.pool((size_t)X.B * e2.stS * e2.stld * 2 * sizeof(float));
@@ -1605,10 +1626,11 @@ struct rs_engine {
                 View r = ex.T(B, h.H, h.W, b.out_ch, dt);
                 ex.prefix = "in." + std::to_string(i) + ".res.";
                 resblock(ex, b.res, h, r, film, /*out_stats=*/false);   // (r feeds patch_embed, not a GroupNorm)
+                ex.prefix.clear();
+                ex.tr("in." + std::to_string(i) + ".res", r);
                 ex.prefix = "in." + std::to_string(i) + ".swin.";
                 basiclayer(ex, b.swin, r, y);
                 ex.prefix.clear();
-                ex.tr("in." + std::to_string(i) + ".res", r);
                 ex.tr("in." + std::to_string(i), y);
             } else {
                 ex.prefix = "in." + std::to_string(i) + ".res.";
@@ -1624,12 +1646,18 @@ struct rs_engine {
         {
             const size_t mk = ex.mark();
             View r1 = ex.T(B, h.H, h.W, h.C, dt), r2 = ex.T(B, h.H, h.W, h.C, dt);
+            ex.prefix = "mid.res1.";
             resblock(ex, mid_res1, h, r1, film, /*out_stats=*/false);
+            ex.prefix.clear();
             ex.tr("mid.res1", r1);
+            ex.prefix = "mid.swin.";
             basiclayer(ex, mid_swin, r1, r2);
+            ex.prefix.clear();
             ex.tr("mid.swin", r2);
             View y = cat[0].slice(0, h_ch[0]);
+            ex.prefix = "mid.res2.";
             resblock(ex, mid_res2, r2, y, film);
+            ex.prefix.clear();
             note(cat_lo[0], y);
             ex.tr("mid.res2", y);
             ex.reset(mk);
@@ -1647,18 +1675,27 @@ struct rs_engine {
                 y = last;
             }
             const size_t mk = ex.mark();
+            const std::string nm = "out." + std::to_string(j);
+            ex.prefix = nm + ".res.";
             if (!b.has_swin && !b.has_up) {
                 resblock(ex, b.res, X, y, film);
+                ex.prefix.clear();
             } else {
                 View cur = ex.T(B, X.H, X.W, b.out_ch, dt);
                 resblock(ex, b.res, X, cur, film, /*out_stats=*/false);   // (feeds patch_embed or the upsampling conv)
+                ex.prefix.clear();
+                ex.tr(nm + ".res", cur);
                 if (b.has_swin) {
+                    ex.prefix = nm + ".swin.";
                     if (b.has_up) {
                         View r2 = ex.T(B, X.H, X.W, b.out_ch, dt);
                         basiclayer(ex, b.swin, cur, r2, /*out_stats=*/false);
                         cur = r2;
+                        ex.prefix.clear();
+                        ex.tr(nm + ".swin", cur);
                     } else {
                         basiclayer(ex, b.swin, cur, y);
+                        ex.prefix.clear();
                     }
                 }
                 if (b.has_up) {
@@ -1672,7 +1709,7 @@ struct rs_engine {
                 }
             }
             if (j + 1 < n_out) note(cat_lo[j + 1], y); else last = y;
-            ex.tr("out." + std::to_string(j), y);
+            ex.tr(nm, y);
             ex.reset(mk);
         }
         // ---- out head (unet.py:893-894)
@@ -1847,7 +1884,7 @@ struct rs_engine {
     // ---------------------------------------------------------------- run helper (dry sizing pass, then real pass)
     int run(hipStream_t st, const std::function<void(Exec&)>& fn) {
         if (!ready) return fail("weights are not ready (rs_pack_weights / rs_weights_ready not called)");
-        Exec d; d.st = st; d.arena = &arena; d.dry = true; d.keep = debug; d.dbg = debug;
+        Exec d; d.st = st; d.arena = &arena; d.dry = true; d.tracing = debug;
         tail_plan.clear();
         d.plan = &tail_plan;
         d.pool_base = (char*)4096;   // never dereferenced; non-null so that "has statistics" (View::st != nullptr) reads the same in both passes
@@ -1874,8 +1911,22 @@ struct rs_engine {
             if (hipMalloc((void**)&arena.base, want) != hipSuccess) return fail("hipMalloc of scratch arena failed (" + std::to_string(want) + " bytes)");
             arena.cap = want;
         }
-        Exec r; r.st = st; r.arena = &arena; r.dry = false; r.keep = debug; r.dbg = debug;
-        if (debug) { trace.clear(); r.trace = &trace; }
+        // the debug trace's capture region (sized by the dry pass; allocated only while tracing is on, apart from everything above)
+        trace.clear();
+        if (debug && d.cap_off > cap_bytes) {
+            if (cap_base) {
+                (void)hipStreamSynchronize(st);
+                if (cap_host) free(cap_base); else (void)hipFree(cap_base);
+            }
+            cap_base = nullptr; cap_bytes = 0;
+            cap_host = fake;   // (RS_FAKE_DEVICE: host memory, as the arena there)
+            if (fake) cap_base = (char*)malloc(d.cap_off);
+            else if (hipMalloc((void**)&cap_base, d.cap_off) != hipSuccess) cap_base = nullptr;
+            if (!cap_base) return fail("allocation of the debug trace's capture region failed (" + std::to_string(d.cap_off) + " bytes)");
+            cap_bytes = d.cap_off;
+        }
+        Exec r; r.st = st; r.arena = &arena; r.dry = false; r.tracing = debug;
+        if (debug) { r.trace = &trace; r.cap_base = cap_base; }
         r.plan = &tail_plan;
         r.pool_base = arena.base + scratch_end;
         r.ticket_base = (unsigned*)(arena.base + scratch_end + pool_bytes);
@@ -1892,7 +1943,8 @@ struct rs_engine {
                 r.err = -4; g_err = "internal: a planned GroupNorm tail was never attached to its producer";
             }
         if (r.ticket_used != d.ticket_used || r.pool_peak != d.pool_peak) { r.err = -4; g_err = "internal: dry and real pass disagree about the GroupNorm tail plan"; }
-        last_launches = r.launches + (ticket_bytes ? 1 : 0);
+        if (r.cap_off != d.cap_off) { r.err = -4; g_err = "internal: dry and real pass disagree about the debug trace's capture region"; }
+        last_launches = r.launches + (ticket_bytes ? 1 : 0);   // (the network's launches: the trace's capture copies are not counted here)
         last_flops[0] = r.igemm_flops[0]; last_flops[1] = r.igemm_flops[1]; last_flops[2] = r.igemm_flops[2]; last_igemm_launches = r.igemm_launches;
         last_igemm_bytes = r.igemm_bytes;
         last_igemm_ms = 0.0;
@@ -1994,6 +2046,7 @@ void rs_destroy(rs_engine* e) {
         for (auto& kv : e->film_cache) (void)hipFree(kv.second);
         if (e->arena.base) (void)hipFree(e->arena.base);
     }
+    e->free_capture();
     delete e;
 }
 
@@ -2114,20 +2167,30 @@ int rs_profile_shapes(rs_engine* e, char* buf, int cap) {
     return need;
 }
 
-// ---- debug trace (tests only): record named intermediate activations of the next network call
-int rs_debug_enable(rs_engine* e, int on) { if (!e) return -1; e->debug = on != 0; e->trace.clear(); return 0; }
+// ---- debug trace (tests only): named intermediate activations of the next network calls, copied as they are produced (Exec::tr)
+int rs_debug_enable(rs_engine* e, int on) {
+    if (!e) return -1;
+    e->debug = on != 0;
+    if (!e->debug) {
+        if (e->cap_base && !e->cap_host) (void)hipDeviceSynchronize();   // (copies of the last traced call may still be in flight)
+        e->free_capture();
+    }
+    e->trace.clear();
+    return 0;
+}
 int rs_debug_count(rs_engine* e) { return e ? (int)e->trace.size() : 0; }
 int rs_debug_info(rs_engine* e, int i, char* name, int cap, int* dims /* B,C,H,W */) {
     if (!e || i < 0 || i >= (int)e->trace.size()) return -1;
-    const auto& t = e->trace[i];
-    snprintf(name, cap, "%s", t.first.c_str());
-    dims[0] = t.second.B; dims[1] = t.second.C; dims[2] = t.second.H; dims[3] = t.second.W;
+    const TraceRec& t = e->trace[i];
+    snprintf(name, cap, "%s", t.name.c_str());
+    dims[0] = t.B; dims[1] = t.C; dims[2] = t.H; dims[3] = t.W;
     return 0;
 }
 int rs_debug_fetch(rs_engine* e, int i, float* out_nchw, void* stream) {
-    if (!e || i < 0 || i >= (int)e->trace.size()) return -1;
-    const View& v = e->trace[i].second;
-    return rs_nhwc_to_nchw_launch(v.p, v.dt, out_nchw, v.B, v.C, v.H * v.W, v.ld, 0, (hipStream_t)stream);
+    if (!e || i < 0 || i >= (int)e->trace.size() || !e->cap_base) return -1;
+    const TraceRec& t = e->trace[i];
+    const size_t bytes = (size_t)t.B * t.C * t.H * t.W * sizeof(float);
+    return hipMemcpyAsync(out_nchw, e->cap_base + t.off, bytes, hipMemcpyDefault, (hipStream_t)stream) == hipSuccess ? 0 : -1;
 }
 long long rs_last_launch_count(rs_engine* e) { return e ? e->last_launches : 0; }
 

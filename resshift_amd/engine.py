@@ -416,10 +416,16 @@ class Engine:
         return shapes, parts
 
     def debug_enable(self, on: bool = True):
-        self.lib.rs_debug_enable(self._h, int(on))
+        """Trace every following network call (on) / stop tracing and free the trace's capture region (off).  A traced call runs the
+        same kernels, parameters and scratch layout as an untraced one: each record is a copy of the tensor, made on the call's stream
+        where the production graph stores it, into a capture region of its own.  The copies are not counted by last_launch_count()."""
+        self._chk(self.lib.rs_debug_enable(self._h, int(on)), "rs_debug_enable")
 
     def debug_trace(self):
-        """name -> NCHW fp32 tensor for every activation recorded by the last call (debug_enable(True) first)."""
+        """name -> NCHW fp32 tensor for every activation recorded by the last call (debug_enable(True) first).  UNet names: in.0, in.N,
+        in.N.res, mid.res1, mid.swin, mid.res2, out.J, out.J.res, out.J.swin (block boundaries; oracle.resshift_oracle.unet_plan), and
+        inner records under their block's prefix (in.N.res.conv1, mid.swin.embed, out.J.swin.blk1.out, ...) wherever the production graph
+        stores that tensor - a fused path has none for a tensor it never writes."""
         out = {}
         for i in range(self.lib.rs_debug_count(self._h)):
             name = C.create_string_buffer(128)

@@ -1,0 +1,132 @@
+"""The UNet's block plan (oracle/resshift_oracle.py: unet_plan) and the engine's debug trace, without a GPU.
+
+tests/test_unet_blocks_gpu.py checks every block of the production kernel graph against a float64 reference, teacher-forced: each block of
+the plan is fed the engine's own recorded inputs.  That rests on three things checked here: the plan chained is the oracle's forward, the
+plan runs in float64 when given float64 weights and inputs, and the engine records exactly the plan's block names, once each, with the
+plan's dims - without changing the launches of the pass it observes."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import helpers as H
+from oracle import resshift_oracle as oc
+from resshift_amd.config import load_config, to_plain
+from resshift_amd.spec import unet_param_spec
+
+torch.set_grad_enabled(False)
+
+NO_GPU = {"HIP_VISIBLE_DEVICES": "-1"}
+
+
+def _inputs(tag):
+    """(params, fp32 state_dict, host inputs) of a tiny case or of the realsr config at B=1"""
+    if tag == "realsr":
+        up, ap, dp = H.realsr_params()
+        usd, _ = H.weights(up, ap)
+        y, noises, _ = H.synth.synthetic_inputs(H.SEED_X, 1, 64, 64, 3, 64, 64, dp["steps"])
+        return up, usd, {"x": noises[1] * 1.3, "t": torch.tensor([7]), "lq": y, "mask": None}, "realsr/unet"
+    up, ap, dp, with_mask = H.CASES[tag]
+    usd, _ = H.weights(up, ap)
+    y, noises, mask = H.case_inputs(up, ap, dp, with_mask)
+    return up, usd, {"x": noises[1] * 1.3, "t": torch.tensor([2, 2]), "lq": y, "mask": mask if with_mask else None}, f"{tag}/unet"
+
+
+def _teacher_forced(plan, env):
+    """every step of the plan on its own, fed clones of the stored outputs of the steps it reads (the GPU test's pattern)"""
+    out = {}
+    for s in plan:
+        out[s.name] = s.fn(*[env[i].clone() for i in s.inputs])
+    return out
+
+
+@pytest.mark.parametrize("tag", ["tiny", "tiny_fe", "tiny_fe8", "realsr"])
+def test_plan_reproduces_unet_forward_bit_for_bit(tag):
+    up, usd, inp, golden = _inputs(tag)
+    ref = oc.unet_forward(usd, up, **inp)
+    plan = oc.unet_plan(usd, up, with_lq=True, with_mask=inp["mask"] is not None)
+    names = [s.name for s in plan]
+    assert len(set(names)) == len(names) and names[0] == "emb" and names[-1] == "head", names
+    env = oc.run_plan(plan, {k: v for k, v in inp.items() if v is not None})
+    assert torch.equal(env["head"], ref)
+    # each block alone, from the stored outputs of its inputs: the same bits (a step reads nothing but its declared inputs)
+    tf = _teacher_forced(plan, env)
+    for n in names:
+        assert torch.equal(tf[n], env[n]), n
+    # and the chain is still the reference's forward (the fixture of test_oracle.py)
+    assert H.rel_err(ref, torch.from_numpy(H.golden()[golden])) < 2e-5
+
+
+@pytest.mark.parametrize("tag", ["tiny_fe", "realsr"])
+def test_plan_in_float64(tag):
+    """float64 weights and inputs keep every step in float64 (GroupNorm and the timestep embedding included), and the result agrees
+    with the fp32 oracle to fp32 round-off"""
+    up, usd, inp, _ = _inputs(tag)
+    sd64 = {k: (v.double() if torch.is_floating_point(v) else v) for k, v in usd.items()}
+    in64 = {k: (v.double() if v is not None and torch.is_floating_point(v) else v) for k, v in inp.items()}
+    plan64 = oc.unet_plan(sd64, up, with_lq=True, with_mask=inp["mask"] is not None)
+    env64 = oc.run_plan(plan64, {k: v for k, v in in64.items() if v is not None})
+    env32 = oc.run_plan(oc.unet_plan(usd, up, with_lq=True, with_mask=inp["mask"] is not None), {k: v for k, v in inp.items() if v is not None})
+    worst = 0.0
+    for s in plan64:
+        a, b = env64[s.name], env32[s.name]
+        assert a.dtype == torch.float64, (s.name, a.dtype)
+        e = ((a - b.double()).abs().max() / a.abs().max()).item()
+        worst = max(worst, e)
+        assert e < 2e-5, (s.name, e)
+    # really float64 arithmetic, not float32 values in a float64 container: the result does not round-trip through float32
+    out = env64["head"]
+    assert (out.float().double() != out).float().mean().item() > 0.9
+    assert worst > 0.0
+    print(f"{tag}: float64 plan vs fp32 oracle, worst step {worst:.2e}")
+
+
+def _plan_dims(cname, B):
+    """name -> (B, C, H, W) of every traced step of the plan (fp32 oracle at batch 1, synthetic weights)"""
+    up = to_plain(load_config(cname))["model"]["params"]
+    uspec, _ = unet_param_spec(up)
+    usd = H.synth.synthetic_state_dict(uspec, H.SEED_W, image_size=up["image_size"])
+    hz, hl = int(up["image_size"]), int(up["lq_size"])
+    g = torch.Generator().manual_seed(5)
+    env = {"x": torch.randn(1, int(up["in_channels"]), hz, hz, generator=g), "t": torch.tensor([3]),
+           "lq": torch.rand(1, 3, hl, hl, generator=g) * 2 - 1}
+    if up.get("cond_mask"):
+        env["mask"] = (torch.rand(1, 1, hl, hl, generator=g) > 0.5).float() * 2 - 1
+    plan = oc.unet_plan(usd, up, with_lq=True, with_mask="mask" in env)
+    env = oc.run_plan(plan, env)
+    return {s.name: (B,) + tuple(env[s.name].shape[1:]) for s in plan if s.name not in ("emb", "head")}
+
+
+@pytest.mark.parametrize("cname,B,prec", [("realsr_swinunet_realesrgan256", 32, 2), ("realsr_swinunet_realesrgan256", 3, 0),
+                                          ("faceir_gfpgan512_lpips", 2, 2), ("inpaint_lama256_imagenet", 4, 1)])
+def test_trace_names_are_the_plan_blocks_without_a_gpu(cname, B, prec):
+    """RS_FAKE_DEVICE=1 (test-hooks library, see _fake_device_plumbing.py): a traced rs_unet_forward at mixed timesteps records every
+    block of the plan exactly once, with the plan's dims, plus inner records under a block's prefix; and tracing leaves the pass alone -
+    the same launch count, pool, tickets and sequence numbers as the untraced call."""
+    from resshift_amd import build as _b
+
+    env = dict(os.environ, RS_FAKE_DEVICE="1", RESSHIFT_HIP_LIB=_b.build_testhooks(), **NO_GPU)
+    r = subprocess.run([sys.executable, os.path.join(H.ROOT, "tests", "_fake_device_trace.py"), cname, str(B), str(prec)], env=env,
+                       capture_output=True, text=True, timeout=600)
+    fake = re.findall(r"\[fake device\] (dry: .*)", r.stderr)
+    calls = re.findall(r"CALL (\w+) rc -?\d+ launches (\d+) records (\d+)", r.stdout)
+    assert len(fake) == 2 and len(calls) == 2, (r.stdout[-800:], r.stderr[-1500:])
+    assert fake[0] == fake[1], fake                                  # dry / real bookkeeping of the two calls
+    assert calls[0][1] == calls[1][1] and int(calls[0][2]) == 0, calls   # network launches; no records untraced
+    recs = [ln.split()[1:] for ln in r.stdout.splitlines() if ln.startswith("REC ")]
+    assert len(recs) == int(calls[1][2]) and recs, calls
+    names = [n for n, *_ in recs]
+    assert len(set(names)) == len(names), [n for n in names if names.count(n) > 1]
+    dims = _plan_dims(cname, B)
+    blocks = {n: tuple(int(v) for v in d) for n, *d in recs if n in dims}
+    assert set(blocks) == set(dims), (sorted(set(dims) - set(blocks)), sorted(set(blocks) - set(dims)))
+    for n, d in dims.items():
+        assert blocks[n] == d, (n, blocks[n], d)
+    # every other record is an inner one, named under the prefix of a block of the plan
+    for n in names:
+        if n not in dims:
+            parts = n.split(".")
+            assert any(".".join(parts[:k]) in dims for k in range(1, len(parts))), n
