@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the ResShift sampling hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision POLICY] [--config NAME] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision POLICY] [--config NAME] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1], the default): realsr_swinunet_realesrgan256, 64x64 -> 256x256, 15 diffusion steps,
 batch 32 per GPU, random-init weights, synthetic inputs already resident in HBM.  One "step" of this benchmark = one
@@ -25,7 +25,11 @@ elements is written instead, with their flat indices in DIR/image_index.npy (flo
 Rank 0 prints ONE JSON line with the contract fields.  EVERYTHING at the top level of the line - `value`, `ms_per_step`, `dtype`,
 `roofline` (+ `per_kernel`, `groupnorm`, `traffic`), `cpu_baseline.gpu_vs_cpu_psnr_db` - describes ONE precision policy, the one
 `--precision` names.  The default is `parity` (split-precision encoder + UNet, fp16 decoder): the fastest policy that meets
-north_star's tolerance (image PSNR >= 60 dB against the reference CPU path).  Beside it:
+north_star's tolerance (image PSNR >= 60 dB against the reference CPU path).
+
+A plain run does only what the headline needs: it packs the weights of the headline policy, warms up, times the steps, writes
+`--dump-outputs` and prints `value`, `ms_per_step`, `dtype` and the bookkeeping beside them (`config`, `ranks`).  Everything below
+runs with `--full` only (the `--no-...` options leave single legs out of a `--full` run):
   * `roofline`      MFMA implicit-GEMM kernel family of the headline pass (hipEvent timed on the launch stream in a dedicated pass):
                     `frac` = algorithmic flops / time / 2.5 PFLOP/s (`frac_whole_path` the same for the whole pass),
                     `mfma_issue_frac` = matrix-pipe utilisation (split storage issues three MFMAs per product); `roofline.per_kernel` per
@@ -39,6 +43,8 @@ north_star's tolerance (image PSNR >= 60 dB against the reference CPU path).  Be
   * `parity_vs_cpu_oracle`  image PSNR, latent PSNR and VQ code agreement of the headline policy against that CPU run on up to
                     `--parity-images` (default: all 32) images of the batch, per-image minimum included;
   * `value_fp16_unqualified`  the all-fp16 policy (BASELINE.json's dtype) timed the same way, with ITS parity: fast, and below the tolerance;
+                    `value_at_parity` the fastest policy of the run that meets the tolerance (`--mixed-leg`, `--exact-leg`: more policies);
+  * `other_policy_all_ranks`  N > 1: that other policy timed across all ranks like the headline;
   * `torch_rocm_autocast_baseline`  the reference's own modules moved to this GPU and run with stock PyTorch-ROCm ops under
                     torch.autocast(fp16) (what sampler.py:185 does) at the bench batch: images/sec and ITS parity against the fp32 CPU path
                     (`torch_rocm_autocast_restatement_baseline`: the oracle's restatement instead, when oracle/_ref is absent).
@@ -297,9 +303,13 @@ def main():
     ap.add_argument("--chop-size", type=int, default=128, help="--tiled: LR tile side (the reference's default for x4 models is 512)")
     ap.add_argument("--chop-bs", type=int, default=8, help="--tiled: tiles per sampler call of the batched leg (chop_bs = 1 is always timed too)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the images of the last timed step to DIR/image.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline: roofline pass, ms_per_unet_step, CPU baseline + "
+                                                        "parity, secondary policies, PyTorch-ROCm baseline (a plain run times the headline only)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    if (args.mixed_leg or args.exact_leg) and not args.full:
+        ap.error("--mixed-leg and --exact-leg are legs of a --full run")
 
     if args.tiled:
         if args.gpus != 1:
@@ -341,10 +351,10 @@ def main():
     def load_fn():
         return random_state_dict(uspec, seed=1), random_state_dict(ae_param_spec(aep), seed=2)
 
-    # the engine packs (and broadcasts) only the weight forms this run will ask for: the headline policy's, the secondary policy's, fp32
-    # only with --exact-leg
+    # the engine packs (and broadcasts) only the weight forms this run will ask for: the headline policy's, the secondary policy's (--full),
+    # fp32 only with --exact-leg
     forms = set(policy_args(args.precision, steps)[0]) | set(policy_args(args.precision, steps)[1:])
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         forms |= {"fp16", "split"}
     if args.mixed_leg:
         forms |= {"fp16", "split"}
@@ -415,7 +425,7 @@ def main():
     # ---- N > 1: the OTHER reference policy (fp16 when the headline is parity, parity otherwise) timed across all ranks exactly like the
     # headline (barriers, max over ranks), so that the scaling curve exists for both.  Parity against the CPU oracle is an N = 1 matter.
     other_policy_all_ranks = None
-    if world > 1 and not args.no_secondary:
+    if world > 1 and args.full and not args.no_secondary:
         oname = "fp16" if args.precision == PARITY_POLICY else PARITY_POLICY
         el_p, _ = timed_all_ranks(policy_args(oname, steps), args.steps, max(1, args.warmup))
         el_p = sharding.allreduce_max(el_p, dev)
@@ -503,14 +513,14 @@ def main():
         return roof
 
     roofline = None
-    if rank == 0 and not args.no_profile_pass:
+    if rank == 0 and args.full and not args.no_profile_pass:
         roofline = profile_pass(headline, args.precision)
         log(f"roofline ({args.precision}): {roofline['achieved']} of {roofline['peak']} TFLOP/s (MFMA issue: of {roofline['mfma_issue_peak']})")
 
     # ---- ms/step as SURVEY.md 8(d) defines it: ONE UNet forward + sampler update (models/unet.py:865-895 + gaussian_diffusion.py:332-365) at
     # batch B under the headline policy, through the step-wise API (`p_sample`), hipEvent-bracketed on the launch stream
     unet_step = None
-    if rank == 0 and not args.no_unet_step:
+    if rank == 0 and args.full and not args.no_unet_step:
         ti = steps // 2
         xs = noise[1].contiguous()
         nz = noise[2].contiguous()
@@ -536,7 +546,7 @@ def main():
     cpu_baseline = parity = value_at_parity = value_fp16 = torch_baseline = None
     torch_key = "torch_rocm_autocast_baseline"
     extra = {}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import ref_baseline, resshift_oracle as oc  # checker / baseline only; never on the measured GPU path
 
         # use the cores this process may actually run on (cgroup/affinity aware), never more than torch's own default
@@ -732,9 +742,7 @@ def main():
         line = {
             "metric": f"images/sec ({cdesc.split(',')[0]}, {steps}-step ResShift sampling loop incl. VQ encode/decode)",
             "value": round(value, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "ms_per_diffusion_step": round(ms_per_step / steps, 3), "ms_per_unet_step": unet_step,
-            "ms_per_unet_step_note": f"SURVEY.md 8(d)'s ms/step: ONE UNet forward + sampler update at batch {B} under the headline policy (step-wise API, "
-                                     "hipEvents on the launch stream); ms_per_step is one whole pass of the path over a batch, ms_per_diffusion_step that / steps (autoencoder smeared in)",
+            "ms_per_step": round(ms_per_step, 3), "ms_per_diffusion_step": round(ms_per_step / steps, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": names.get(dtypes[0], dtypes[0]) if len(dtypes) == 1 else
                      f"f16x2 encoder + UNet (hi+lo fp16 pairs, 3 MFMAs per product: fp32-class) + f16 decoder ({args.precision} policy)" if args.precision == PARITY_POLICY
@@ -751,11 +759,18 @@ def main():
                       "per_rank": [{"rank": r, "device": int(v[1]), "images_per_sec": round(B * args.steps / v[0], 3)} for r, v in enumerate(per_rank)],
                       "weight_broadcast_bytes": int(getattr(eng, "broadcast_bytes", 0)),
                       "weight_broadcast_ms": round(1e3 * float(getattr(eng, "broadcast_s", 0.0)), 3)},
-            "roofline": roofline, "cpu_baseline": cpu_baseline, "parity_vs_cpu_oracle": parity,
-            "value_at_parity": value_at_parity, "value_fp16_unqualified": value_fp16, "other_policy_all_ranks": other_policy_all_ranks,
-            torch_key: torch_baseline, "dumped_outputs": dumped,
+            "dumped_outputs": dumped,
         }
-        line.update(extra)
+        if args.full:
+            line.update({
+                "ms_per_unet_step": unet_step,
+                "ms_per_unet_step_note": f"SURVEY.md 8(d)'s ms/step: ONE UNet forward + sampler update at batch {B} under the headline policy (step-wise API, "
+                                         "hipEvents on the launch stream); ms_per_step is one whole pass of the path over a batch, ms_per_diffusion_step that / steps (autoencoder smeared in)",
+                "roofline": roofline, "cpu_baseline": cpu_baseline, "parity_vs_cpu_oracle": parity,
+                "value_at_parity": value_at_parity, "value_fp16_unqualified": value_fp16, "other_policy_all_ranks": other_policy_all_ranks,
+                torch_key: torch_baseline,
+            })
+            line.update(extra)
         print(json.dumps(line), flush=True)
     if dist.is_initialized():
         sharding.barrier()

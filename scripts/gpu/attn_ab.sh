@@ -6,7 +6,7 @@ RESSHIFT_HIP_LIB=${NEW_LIB:+$R/$NEW_LIB} timeout 600 python -m pytest tests/test
 for v in base new; do
   RESSHIFT_HIP_LIB=$R/resshift_amd/lib_ab_abl_$v.so timeout 300 python scripts/attn_phases.py split > $O/phases_$v.txt 2>&1; echo "phases $v rc=$?"; grep -A1 "64x64 shift 0" $O/phases_$v.txt | cut -c1-420
 done
-B="--steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-torch-baseline --no-unet-step"
+B="--steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary --no-torch-baseline --no-unet-step"
 for v in base new base new; do
   if [ $v = base ]; then export RESSHIFT_HIP_LIB=$R/resshift_amd/lib_ab_base.so; elif [ -n "$NEW_LIB" ]; then export RESSHIFT_HIP_LIB=$R/$NEW_LIB; else unset RESSHIFT_HIP_LIB; fi
   timeout 600 python bench.py $B > $O/bench_$v.json 2> $O/bench_$v.err

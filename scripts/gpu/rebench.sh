@@ -1,5 +1,5 @@
 R=$(pwd); O=$R/gpurun_out/r6g; mkdir -p $O
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_parity_final.json 2> $O/bench_parity_final.err; echo "bench rc=$?"
+timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_parity_final.json 2> $O/bench_parity_final.err; echo "bench rc=$?"
 RS_WINO=0 timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-torch-baseline --no-unet-step > $O/bench_parity_wino_off.json 2> $O/wo.err
 timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-torch-baseline --no-unet-step > $O/bench_parity_wino_on.json 2> $O/won.err
 python -c "

@@ -1021,7 +1021,7 @@ def test_bench_launches_its_own_ranks(gpu):
     env = dict(os.environ, RESSHIFT_DIST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "16", "--steps", "2", "--warmup", "1", "--no-profile-pass"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "16", "--steps", "2", "--warmup", "1", "--full", "--no-profile-pass"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1038,6 +1038,34 @@ def test_bench_launches_its_own_ranks(gpu):
         env.pop("RESSHIFT_DIST_BACKEND")
         r2 = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
         assert r2.returncode != 0 and "refused" in (r2.stderr + r2.stdout)
+
+
+def test_bench_plain_run_times_the_headline_only(gpu, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: set-up, warm-up, the timed steps, --dump-outputs and ONE line with the
+    contract fields - and none of the legs that --full adds (roofline pass, ms_per_unet_step, CPU baseline + parity, secondary policies,
+    PyTorch-ROCm baseline)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RESSHIFT_PRECISION")}
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "4", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["unit"] == "images/sec" and line["higher_is_better"] is True and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] > 0 and abs(line["value"] - 4 * 1e3 / line["ms_per_step"]) <= 1e-2 * line["value"]
+    assert "parity policy" in line["dtype"] and line["config"]["precision_policy"] == "parity"
+    full_only = {"ms_per_unet_step", "roofline", "cpu_baseline", "parity_vs_cpu_oracle", "value_at_parity", "value_fp16_unqualified",
+                 "other_policy_all_ranks", "torch_rocm_autocast_baseline", "torch_rocm_autocast_restatement_baseline"}
+    assert not full_only & set(line), sorted(full_only & set(line))
+    img = np.load(tmp_path / "image.npy")
+    assert img.shape == (4, 3, 256, 256) and np.isfinite(img).all()
 
 
 def test_rs_bcast_weights_over_a_one_rank_rccl_communicator(gpu):
