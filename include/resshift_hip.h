@@ -218,7 +218,11 @@ int rs_profile_families(rs_engine* e, double* out, int cap);
  * upsampling), out.J.swin (Swin followed by upsampling); inner records (conv1, embed, blkK.qkv / attn / proj / out) carry their block's
  * name as prefix: in.N.res.conv1, mid.swin.embed, out.J.swin.blk1.out ...  rs_debug_count = records of the last call (= its capture
  * copies); rs_last_launch_count counts the network's launches only, never the capture copies.  fetch copies record i into caller memory
- * (B*C*H*W floats, stream-ordered after the call). */
+ * (B*C*H*W floats, stream-ordered after the call); fetch_rows copies images b0 .. b0 + nb - 1 of it only (nb*C*H*W floats), so that a
+ * caller that looks at a few images of a large batch never holds a whole record.  Autoencoder names (rs_vq_encode / rs_vq_decode): enc.in,
+ * enc.down.L.block.I, enc.down.L.ds, enc.mid.block_1, enc.mid.attn, enc.mid.block_2, enc.out (conv_out; the quant_conv is the call's
+ * output); dec.zq (not with force_not_quantize), dec.pq, dec.in, dec.mid.block_1, dec.mid.attn, dec.mid.block_2, dec.up.L.block.I,
+ * dec.up.L.us (the image is the call's output); inner records: <block>.conv1, <attn>.norm / q / k / o, dec.zq.z. */
 /* text table of the last profiled call: per (part, kernel family, M, N, K) launch shape of the MFMA family - launches, summed kernel ms
  * (hipEvents on the launch stream), algorithmic flops - and the wall ms of the encoder / UNet / decoder parts (measurement, d of SURVEY 8:
  * where a pass's time goes per reference module - ldm/modules/diffusionmodules/model.py Encoder / Decoder, models/unet.py UNetModelSwin).
@@ -228,6 +232,7 @@ int rs_debug_enable(rs_engine* e, int on);
 int rs_debug_count(rs_engine* e);
 int rs_debug_info(rs_engine* e, int i, char* name, int name_cap, int* dims_bchw);
 int rs_debug_fetch(rs_engine* e, int i, float* out_nchw_dev, void* stream);
+int rs_debug_fetch_rows(rs_engine* e, int i, int b0, int nb, float* out_nchw_dev, void* stream);
 
 /* ---- op-level entry points (used by tests/ to check each kernel against torch on its own) ---- */
 /* NHWC conv / linear through the MFMA implicit GEMM or the direct kernels (auto-selected).

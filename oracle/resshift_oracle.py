@@ -147,9 +147,9 @@ def res_block(sd: SD, name: str, x: torch.Tensor, emb: torch.Tensor) -> torch.Te
 
 
 class Step(NamedTuple):
-    """One step of the UNet's block plan: ``out = fn(*inputs)``.  ``name`` is the engine's debug-trace name of the step's output
-    (``emb`` and ``head`` are not traced: the FiLM embedding and the network output); ``inputs`` are names of earlier steps or of the
-    host inputs ``x``, ``t``, ``lq``, ``mask``."""
+    """One step of a block plan (unet_plan, ae_encode_plan, ae_decode_plan): ``out = fn(*inputs)``.  ``name`` is the engine's debug-trace
+    name of the step's output (the UNet's ``emb`` and ``head`` are not traced: the FiLM embedding and the network output); ``inputs`` are
+    names of earlier steps or of the host inputs ``x``, ``t``, ``lq``, ``mask`` (the autoencoder's: ``x`` / ``z``)."""
     name: str
     inputs: Tuple[str, ...]
     fn: Callable[..., torch.Tensor]
@@ -275,56 +275,99 @@ def _attn_block(sd: SD, name: str, x: torch.Tensor) -> torch.Tensor:
     return x + _conv(sd, name + ".proj_out", o)
 
 
-def vq_encode(sd: SD, p: dict, x: torch.Tensor) -> torch.Tensor:
-    """ldm/models/autoencoder.py:28-31 + Encoder.forward model.py:522-547."""
+def _ae_dims(p: dict):
     dd = p["ddconfig"]
     mult = [int(m) for m in dd["ch_mult"]]
-    nrb = _listify(dd["num_res_blocks"], len(mult))
-    h = _conv(sd, "encoder.conv_in", x, padding=1)
+    return mult, _listify(dd["num_res_blocks"], len(mult))
+
+
+def ae_encode_plan(sd: SD, p: dict) -> List[Step]:
+    """ldm/models/autoencoder.py:28-31 + Encoder.forward model.py:522-547 as a sequence of named blocks, from the host input ``x``:
+    ``enc.in``, ``enc.down.L.block.I``, ``enc.down.L.ds``, ``enc.mid.block_1``, ``enc.mid.attn``, ``enc.mid.block_2``, ``enc.out`` (norm_out
+    + SiLU + conv_out) and ``enc.z`` (quant_conv: the function's output, not traced by the engine)."""
+    mult, nrb = _ae_dims(p)
+    plan: List[Step] = [Step("enc.in", ("x",), lambda x: _conv(sd, "encoder.conv_in", x, padding=1))]
+    prev = "enc.in"
     for l in range(len(mult)):
         for i in range(nrb[l]):
-            h = _resnet(sd, f"encoder.down.{l}.block.{i}", h)
+            nm = f"enc.down.{l}.block.{i}"
+            plan.append(Step(nm, (prev,), (lambda b: lambda h: _resnet(sd, b, h))(f"encoder.down.{l}.block.{i}")))
+            prev = nm
         if l != len(mult) - 1:
-            h = _conv(sd, f"encoder.down.{l}.downsample.conv", F.pad(h, (0, 1, 0, 1)), stride=2)  # model.py:80-84
-    h = _resnet(sd, "encoder.mid.block_1", h)
-    h = _attn_block(sd, "encoder.mid.attn_1", h)
-    h = _resnet(sd, "encoder.mid.block_2", h)
-    h = _conv(sd, "encoder.conv_out", F.silu(_gn(sd, "encoder.norm_out", h, 1e-6)), padding=1)
-    return _conv(sd, "quant_conv", h)
+            nm = f"enc.down.{l}.ds"
+            plan.append(Step(nm, (prev,), (lambda b: lambda h: _conv(sd, b, F.pad(h, (0, 1, 0, 1)), stride=2))(f"encoder.down.{l}.downsample.conv")))  # model.py:80-84
+            prev = nm
+    plan.append(Step("enc.mid.block_1", (prev,), lambda h: _resnet(sd, "encoder.mid.block_1", h)))
+    plan.append(Step("enc.mid.attn", ("enc.mid.block_1",), lambda h: _attn_block(sd, "encoder.mid.attn_1", h)))
+    plan.append(Step("enc.mid.block_2", ("enc.mid.attn",), lambda h: _resnet(sd, "encoder.mid.block_2", h)))
+    plan.append(Step("enc.out", ("enc.mid.block_2",), lambda h: _conv(sd, "encoder.conv_out", F.silu(_gn(sd, "encoder.norm_out", h, 1e-6)), padding=1)))
+    plan.append(Step("enc.z", ("enc.out",), lambda h: _conv(sd, "quant_conv", h)))
+    return plan
+
+
+def vq_encode(sd: SD, p: dict, x: torch.Tensor) -> torch.Tensor:
+    """ldm/models/autoencoder.py:28-31 + Encoder.forward model.py:522-547: the block plan (ae_encode_plan) chained."""
+    return run_plan(ae_encode_plan(sd, p), {"x": x})["enc.z"]
+
+
+def vq_distances(sd: SD, z: torch.Tensor) -> torch.Tensor:
+    """ldm/modules/vqvae/quantize.py:276-285: the three-term squared distance [B*H*W, n_embed] of every latent position to every code."""
+    e = sd["quantize.embedding.weight"]
+    zf = z.permute(0, 2, 3, 1).contiguous().view(-1, e.shape[1])
+    return torch.sum(zf ** 2, dim=1, keepdim=True) + torch.sum(e ** 2, dim=1) - 2 * torch.einsum("bd,dn->bn", zf, e.t())
+
+
+def vq_lookup(sd: SD, z: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """ldm/modules/vqvae/quantize.py:287-312: the codebook rows of ``idx`` [B*H*W] as z_q [B,C,H,W]."""
+    zp = z.permute(0, 2, 3, 1).contiguous()
+    zq = sd["quantize.embedding.weight"][idx].view(zp.shape)
+    zq = zp + (zq - zp)  # straight-through expression kept for bit parity (quantize.py:298)
+    return zq.permute(0, 3, 1, 2).contiguous()
 
 
 def vq_quantize(sd: SD, z: torch.Tensor):
     """ldm/modules/vqvae/quantize.py:271-312 — returns (z_q [B,C,H,W], indices [B*H*W])."""
-    e = sd["quantize.embedding.weight"]
-    zp = z.permute(0, 2, 3, 1).contiguous()
-    zf = zp.view(-1, e.shape[1])
-    d = torch.sum(zf ** 2, dim=1, keepdim=True) + torch.sum(e ** 2, dim=1) - 2 * torch.einsum("bd,dn->bn", zf, e.t())
-    idx = torch.argmin(d, dim=1)
-    zq = e[idx].view(zp.shape)
-    zq = zp + (zq - zp)  # straight-through expression kept for bit parity (quantize.py:298)
-    return zq.permute(0, 3, 1, 2).contiguous(), idx
+    idx = torch.argmin(vq_distances(sd, z), dim=1)
+    return vq_lookup(sd, z, idx), idx
+
+
+def ae_decode_plan(sd: SD, p: dict, force_not_quantize: bool = False) -> List[Step]:
+    """ldm/models/autoencoder.py:33-40 + Decoder.forward model.py:627-660 as a sequence of named blocks, from the host input ``z``:
+    ``dec.idx`` and ``dec.zq`` (the VQ argmin - int64 [B*H*W], the engine hands it out beside the image - and the lookup; neither with
+    ``force_not_quantize``), ``dec.pq`` (post_quant_conv), ``dec.in``, ``dec.mid.block_1``, ``dec.mid.attn``, ``dec.mid.block_2``,
+    ``dec.up.L.block.I``, ``dec.up.L.us`` (nearest x2 + conv) and ``dec.head`` (norm_out + SiLU + conv_out: the function's output, not
+    traced by the engine)."""
+    mult, nrb = _ae_dims(p)
+    plan: List[Step] = []
+    prev = "z"
+    if not force_not_quantize:
+        plan.append(Step("dec.idx", ("z",), lambda z: torch.argmin(vq_distances(sd, z), dim=1)))
+        plan.append(Step("dec.zq", ("z", "dec.idx"), lambda z, idx: vq_lookup(sd, z, idx)))
+        prev = "dec.zq"
+    plan.append(Step("dec.pq", (prev,), lambda h: _conv(sd, "post_quant_conv", h)))
+    plan.append(Step("dec.in", ("dec.pq",), lambda h: _conv(sd, "decoder.conv_in", h, padding=1)))
+    plan.append(Step("dec.mid.block_1", ("dec.in",), lambda h: _resnet(sd, "decoder.mid.block_1", h)))
+    plan.append(Step("dec.mid.attn", ("dec.mid.block_1",), lambda h: _attn_block(sd, "decoder.mid.attn_1", h)))
+    plan.append(Step("dec.mid.block_2", ("dec.mid.attn",), lambda h: _resnet(sd, "decoder.mid.block_2", h)))
+    prev = "dec.mid.block_2"
+    for l in reversed(range(len(mult))):
+        for i in range(nrb[l] + 1):
+            nm = f"dec.up.{l}.block.{i}"
+            plan.append(Step(nm, (prev,), (lambda b: lambda h: _resnet(sd, b, h))(f"decoder.up.{l}.block.{i}")))
+            prev = nm
+        if l != 0:
+            nm = f"dec.up.{l}.us"
+            plan.append(Step(nm, (prev,), (lambda b: lambda h: _conv(sd, b, F.interpolate(h, scale_factor=2.0, mode="nearest"), padding=1))(
+                f"decoder.up.{l}.upsample.conv")))
+            prev = nm
+    plan.append(Step("dec.head", (prev,), lambda h: _conv(sd, "decoder.conv_out", F.silu(_gn(sd, "decoder.norm_out", h, 1e-6)), padding=1)))
+    return plan
 
 
 def vq_decode(sd: SD, p: dict, h: torch.Tensor, force_not_quantize: bool = False, return_indices: bool = False):
-    """ldm/models/autoencoder.py:33-40 + Decoder.forward model.py:627-660."""
-    dd = p["ddconfig"]
-    mult = [int(m) for m in dd["ch_mult"]]
-    nrb = _listify(dd["num_res_blocks"], len(mult))
-    idx = None
-    if not force_not_quantize:
-        h, idx = vq_quantize(sd, h)
-    h = _conv(sd, "post_quant_conv", h)
-    h = _conv(sd, "decoder.conv_in", h, padding=1)
-    h = _resnet(sd, "decoder.mid.block_1", h)
-    h = _attn_block(sd, "decoder.mid.attn_1", h)
-    h = _resnet(sd, "decoder.mid.block_2", h)
-    for l in reversed(range(len(mult))):
-        for i in range(nrb[l] + 1):
-            h = _resnet(sd, f"decoder.up.{l}.block.{i}", h)
-        if l != 0:
-            h = _conv(sd, f"decoder.up.{l}.upsample.conv", F.interpolate(h, scale_factor=2.0, mode="nearest"), padding=1)
-    out = _conv(sd, "decoder.conv_out", F.silu(_gn(sd, "decoder.norm_out", h, 1e-6)), padding=1)
-    return (out, idx) if return_indices else out
+    """ldm/models/autoencoder.py:33-40 + Decoder.forward model.py:627-660: the block plan (ae_decode_plan) chained."""
+    env = run_plan(ae_decode_plan(sd, p, force_not_quantize), {"z": h})
+    return (env["dec.head"], env.get("dec.idx")) if return_indices else env["dec.head"]
 
 
 # ----------------------------------------------------------------------------- diffusion

@@ -113,6 +113,7 @@ SIGNATURES = {
     "rs_debug_count": (_I, [_P]),
     "rs_debug_info": (_I, [_P, _I, C.c_char_p, _I, C.POINTER(C.c_int)]),
     "rs_debug_fetch": (_I, [_P, _I, _P, _P]),
+    "rs_debug_fetch_rows": (_I, [_P, _I, _I, _I, _P, _P]),
     "rs_op_conv2d": (_I, [_P, _P, _P, _P, _P, _P] + [_I] * 18 + [_P]),
     "rs_op_conv2d_bench": (_I, [_P, _P, _P, _P, _P] + [_I] * 16 + [C.POINTER(C.c_float), _P]),
     "rs_op_conv3x3_halo_stats_px": (_I, [_I, _I, _I, _I, _I, _I]),

@@ -1276,6 +1276,7 @@ struct rs_engine {
         View h1 = ex.T(X.B, X.H, X.W, r.Cout, X.dt);
         want_stats(ex, r.c1, X, h1, nullptr);
         gn_silu_conv3(ex, r.n1, r.c1, X, h1, 1e-6f, nullptr, nullptr);
+        ex.tr("conv1", h1);
         if (skip_fold(ex, r, X, h1, Y)) {
             if (out_stats) want_stats(ex, r.c2, h1, Y, nullptr, 1, 1, 1, true);
             gn_silu_conv3(ex, r.n2, r.c2, h1, Y, 1e-6f, nullptr, nullptr, &r.skip, &X);
@@ -1435,6 +1436,7 @@ struct rs_engine {
         View q = ex.T(X.B, X.H, X.W, C, dt), k = ex.T(X.B, X.H, X.W, C, dt);
         conv1(ex, a.q, n, q);
         conv1(ex, a.k, n, k);
+        ex.tr("norm", n); ex.tr("q", q); ex.tr("k", k);
         View o = ex.T(X.B, X.H, X.W, C, dt);
         // fp16 storage: streaming attention (ae_attn.hip) - S never reaches HBM; RS_AE_FLASH=0 keeps the row-block path below (A/B runs),
         // which also serves fp32 / split storage and token counts that are not multiples of 128
@@ -1449,6 +1451,7 @@ struct rs_engine {
                 gemm_nt(ex, a.v.w_for(dt), 0, n.p, (long long)T * C, nullptr, vTa, (long long)C * T, X.B, C, T, C, 1.f, dt, dt);
                 ex.ae_flash(q.p, q.ld, k.p, k.ld, vTa, a.v.bias, o.p, o.ld, X.B, T, C, 1.0f / std::sqrt((float)C), dt);
             }
+            ex.tr("o", o);
             want_stats(ex, a.proj, o, Y, &X, 1, 0, 1);
             conv1(ex, a.proj, o, Y, &X);
             ex.reset(mk);
@@ -1486,6 +1489,7 @@ struct rs_engine {
                 }
             }
         }
+        ex.tr("o", o);
         want_stats(ex, a.proj, o, Y, &X, 1, 0, 1);
         conv1(ex, a.proj, o, Y, &X);
         ex.reset(mk);
@@ -1750,11 +1754,21 @@ struct rs_engine {
         View h = ex.T(B, in_nhwc.H, in_nhwc.W, a.ch, dt);
         want_stats(ex, enc_in, in_nhwc, h, nullptr);
         conv(ex, enc_in, in_nhwc, nullptr, h, 1, 1, 1, 1, 0, nullptr);
+        // debug-trace names: the blocks of oracle.resshift_oracle.ae_encode_plan, inner records under their block's prefix
+        ex.tr("enc.in", h);
+        auto block = [&](const std::string& nm, const ResBlockW& r, const View& x, View& y) {
+            ex.prefix = nm + ".";
+            resnet(ex, r, x, y);
+            ex.prefix.clear();
+            ex.tr(nm, y);
+        };
         for (int l = 0; l < a.n_levels; ++l) {
             const AELevel& L = enc_levels[l];
+            const std::string lv = "enc.down." + std::to_string(l);
+            int bi = 0;
             for (const ResBlockW& r : L.blocks) {
                 View y = ex.T(B, h.H, h.W, r.Cout, dt);
-                resnet(ex, r, h, y);
+                block(lv + ".block." + std::to_string(bi++), r, h, y);
                 h = y;
             }
             if (L.has_resample) {
@@ -1762,14 +1776,20 @@ struct rs_engine {
                 View y = ex.T(B, h.H / 2, h.W / 2, h.C, dt);
                 want_stats(ex, L.resample, h, y, nullptr, 2, 0, 1);
                 conv(ex, L.resample, h, nullptr, y, 2, 0, 0, 1, 0, nullptr);
+                ex.tr(lv + ".ds", y);
                 h = y;
             }
         }
-        View m1 = ex.T(B, h.H, h.W, h.C, dt); resnet(ex, enc_mid1, h, m1);
-        View m2 = ex.T(B, h.H, h.W, h.C, dt); attnblock(ex, enc_attn, m1, m2);
-        View m3 = ex.T(B, h.H, h.W, h.C, dt); resnet(ex, enc_mid2, m2, m3);
+        View m1 = ex.T(B, h.H, h.W, h.C, dt); block("enc.mid.block_1", enc_mid1, h, m1);
+        View m2 = ex.T(B, h.H, h.W, h.C, dt);
+        ex.prefix = "enc.mid.attn.";
+        attnblock(ex, enc_attn, m1, m2);
+        ex.prefix.clear();
+        ex.tr("enc.mid.attn", m2);
+        View m3 = ex.T(B, h.H, h.W, h.C, dt); block("enc.mid.block_2", enc_mid2, m2, m3);
         View zc = ex.T(B, h.H, h.W, a.z_channels, RS_F32);
         head(ex, enc_norm, enc_out, m3, zc, 1e-6f);
+        ex.tr("enc.out", zc);   // (enc.z, the quant_conv, is the call's output)
         View zq = ex.T(B, h.H, h.W, a.embed_dim, RS_F32);
         conv(ex, quant_conv, zc, nullptr, zq, 1, 0, 0, 1, 0, nullptr);
         if (!ex.dry) ex.check(rs_nhwc_to_nchw_launch(zq.p, RS_F32, z_nchw, B, a.embed_dim, h.H * h.W, zq.ld, 0, ex.st), "z->nchw");
@@ -1787,27 +1807,45 @@ struct rs_engine {
         if (!force_nq) {
             q = ex.T(B, h_, w_, a.embed_dim, RS_F32);
             if (!ex.dry) ex.check(rs_vq_launch((const float*)z.p, codebook, (float*)q.p, idx_out, (long long)B * h_ * w_, a.n_embed, a.embed_dim, ex.st), "vq");
+            // debug-trace names: the blocks of oracle.resshift_oracle.ae_decode_plan, inner records under their block's prefix
+            ex.tr("dec.zq.z", z);   // (the latents the argmin saw: the call's input times zscale)
+            ex.tr("dec.zq", q);
         }
         View pq = ex.T(B, h_, w_, dec_in.CinP, dt);  // z_channels zero-padded to the decoder conv_in's chunk size
         zero(ex, pq);
         conv(ex, post_quant_conv, q, nullptr, pq.slice(0, a.z_channels), 1, 0, 0, 1, 0, nullptr);
+        ex.tr("dec.pq", pq.slice(0, a.z_channels));
         View h = ex.T(B, h_, w_, dec_in.Cout, dt);
         conv(ex, dec_in, pq, nullptr, h, 1, 1, 1, 1, 0, nullptr);
-        View m1 = ex.T(B, h.H, h.W, h.C, dt); resnet(ex, dec_mid1, h, m1);
-        View m2 = ex.T(B, h.H, h.W, h.C, dt); attnblock(ex, dec_attn, m1, m2);
-        View m3 = ex.T(B, h.H, h.W, h.C, dt); resnet(ex, dec_mid2, m2, m3);
+        ex.tr("dec.in", h);
+        auto block = [&](const std::string& nm, const ResBlockW& r, const View& x, View& y) {
+            ex.prefix = nm + ".";
+            resnet(ex, r, x, y);
+            ex.prefix.clear();
+            ex.tr(nm, y);
+        };
+        View m1 = ex.T(B, h.H, h.W, h.C, dt); block("dec.mid.block_1", dec_mid1, h, m1);
+        View m2 = ex.T(B, h.H, h.W, h.C, dt);
+        ex.prefix = "dec.mid.attn.";
+        attnblock(ex, dec_attn, m1, m2);
+        ex.prefix.clear();
+        ex.tr("dec.mid.attn", m2);
+        View m3 = ex.T(B, h.H, h.W, h.C, dt); block("dec.mid.block_2", dec_mid2, m2, m3);
         h = m3;
         for (int l = a.n_levels - 1; l >= 0; --l) {
             const AELevel& L = dec_levels[l];
+            const std::string lv = "dec.up." + std::to_string(l);
+            int bi = 0;
             for (const ResBlockW& r : L.blocks) {
                 View y = ex.T(B, h.H, h.W, r.Cout, dt);
-                resnet(ex, r, h, y);
+                block(lv + ".block." + std::to_string(bi++), r, h, y);
                 h = y;
             }
             if (L.has_resample) {
                 View y = ex.T(B, h.H * 2, h.W * 2, h.C, dt);
                 if (L.has_upf && upfold_ok(ex, L.upf, h, y)) upfold_conv(ex, L.upf, h, y);
                 else conv(ex, L.resample, h, nullptr, y, 1, 1, 1, 2, 0, nullptr);
+                ex.tr(lv + ".us", y);
                 h = y;
             }
         }
@@ -2191,6 +2229,13 @@ int rs_debug_fetch(rs_engine* e, int i, float* out_nchw, void* stream) {
     const TraceRec& t = e->trace[i];
     const size_t bytes = (size_t)t.B * t.C * t.H * t.W * sizeof(float);
     return hipMemcpyAsync(out_nchw, e->cap_base + t.off, bytes, hipMemcpyDefault, (hipStream_t)stream) == hipSuccess ? 0 : -1;
+}
+int rs_debug_fetch_rows(rs_engine* e, int i, int b0, int nb, float* out_nchw, void* stream) {
+    if (!e || i < 0 || i >= (int)e->trace.size() || !e->cap_base) return -1;
+    const TraceRec& t = e->trace[i];
+    if (b0 < 0 || nb < 1 || b0 > t.B - nb) return -2;
+    const size_t per = (size_t)t.C * t.H * t.W * sizeof(float);
+    return hipMemcpyAsync(out_nchw, e->cap_base + t.off + (size_t)b0 * per, (size_t)nb * per, hipMemcpyDefault, (hipStream_t)stream) == hipSuccess ? 0 : -1;
 }
 long long rs_last_launch_count(rs_engine* e) { return e ? e->last_launches : 0; }
 

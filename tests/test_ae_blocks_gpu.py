@@ -1,0 +1,261 @@
+"""Every autoencoder block of the production kernel graph against float64, teacher-forced, per image.
+
+The autoencoder's kernel choice depends on batch, shape and storage: the sub-pixel form of the upsampling conv (four 2x2 convs with summed
+weights, fp16 / split storage, only when the low-resolution grid has >= 16384 pixels over the batch) or the folded-address 3x3 conv, the
+1x1 shortcut folded into conv2's K loop, streaming attention (fp16: T % 128 == 0, split: T % 64 == 0) or the row-block path with a
+materialised softmax, GroupNorm tails and epilogue statistics, the fused head, the asymmetric-pad stride-2 conv, the 3- / 8-channel ends
+padded to 8.  A traced Engine.vq_encode / vq_decode (Engine.debug_enable) runs that same graph - the test asserts it: same output bits, same
+launch count - and records every block boundary.  Each block of the plan (oracle/resshift_oracle.py: ae_encode_plan / ae_decode_plan) is
+then fed the engine's own recorded inputs in float64 and compared with the engine's output of that block, per image: max |engine - ref| /
+max |ref| over the image's block output, for up to 8 images spread over the batch.  Every case also asserts, from the families of the traced
+pass and the launch shapes of a profiled pass, that it ran the kernels it is there for.  Run with -s for the table of the worst error per
+block and precision.
+
+The VQ step: the engine's indices are checked against float64 distances recomputed from the recorded latents (helpers.vq_check: the float64
+argmin, or within 8 * 2^-23 * (|z|^2 + max |e|^2) of it; at most 0.1 % of an image's positions may differ from the float64 argmin at all -
+tests/test_ae_blocks_cpu.py shows that the fp32 CPU oracle meets this on the same latents).  dec.zq must be, bit for bit, the codebook row
+of the engine's index passed through the reference's fp32 straight-through expression z + (e[idx] - z) (quantize.py:298; that expression is
+within an fp32 rounding or two of the row but not always the row itself, in the reference as in the engine), and dec.pq is teacher-forced
+from the engine's dec.zq, so a legitimately tied index does not propagate.
+
+Memory: the engine's capture region, in device memory, holds every record of the whole batch - 16.0 GiB for the largest case (realsr
+decode at batch 32; faceir decode at batch 16: 15.0 GiB, realsr encode at batch 32: 10.6 GiB, faceir encode at batch 16: 9.1 GiB; printed
+per case).  Only the plan's blocks of the picked images are copied out of it (Engine.debug_trace(names, images)), so the host holds 8
+images per block: 2.9 GiB of fp32 for that largest case."""
+import numpy as np
+import pytest
+import torch
+
+import helpers as H
+from oracle import resshift_oracle as oc
+from resshift_amd.config import load_config, to_plain
+from resshift_amd.engine import Engine, parse_precision
+from resshift_amd.spec import ae_param_spec
+
+pytestmark = pytest.mark.gpu
+torch.set_grad_enabled(False)
+
+CONFIGS = {"realsr": "realsr_swinunet_realesrgan256", "faceir": "faceir_gfpgan512_lpips"}
+# what a case is there for.  attn: the streaming kernel of that storage ("flash16" / "flash_split") or the row-block path with the
+# materialised softmax ("rows"); subpixel / folded: the decoder levels whose upsampling step must run as four 2x2 launches / as one
+# folded-address 3x3 conv.
+#        net      call      B   H    W    prec     attn           subpixel    folded
+CASES = [("realsr", "encode", 32, 256, 256, "split", "flash_split", (), ()),
+         ("realsr", "encode", 32, 256, 256, "fp16", "flash16", (), ()),
+         ("realsr", "encode", 32, 256, 256, "fp32", "rows", (), ()),
+         ("realsr", "decode", 32, 64, 64, "fp16", "flash16", (2, 1), ()),
+         ("realsr", "decode", 32, 64, 64, "split", "flash_split", (2, 1), ()),
+         ("realsr", "decode", 32, 64, 64, "fp32", "rows", (), (2, 1)),
+         ("realsr", "encode", 3, 256, 256, "fp16", "flash16", (), ()),
+         ("realsr", "encode", 3, 256, 256, "split", "flash_split", (), ()),
+         ("realsr", "decode", 3, 64, 64, "fp16", "flash16", (1,), (2,)),
+         ("realsr", "decode", 3, 64, 64, "split", "flash_split", (1,), (2,)),
+         ("faceir", "encode", 16, 512, 512, "split", "flash_split", (), ()),
+         ("faceir", "decode", 16, 64, 64, "fp16", "flash16", (3, 2, 1), ()),
+         ("realsr", "decode", 2, 40, 24, "fp16", "rows", (), (2, 1)),
+         ("realsr", "decode", 2, 40, 24, "split", "flash_split", (), (2, 1)),
+         ("realsr", "decode_nq", 2, 64, 64, "fp16", "flash16", (1,), (2,))]
+# Per-image tolerance of every block, per precision: the per-block tolerances of tests/test_unet_blocks_gpu.py (the same kernel families;
+# the longest reduction here is 9 x 512 products against 9 x 640 there).  For scale, on the CPU (one realsr decoder pass, every block
+# teacher-forced): the fp32 oracle is within 3.4e-7 of float64 on every block, a model of fp16 storage (float64 arithmetic; weights, conv1
+# output and block output rounded to fp16) within 2.1e-4 .. 4.8e-4.
+# Measured on the MI355X, worst image over all CASES (the margin; it does not define the bound; the whole table is in DESIGN 4.4):
+# split 3.57e-6 (enc.out, the fused head: 9 x 512 products in one fp32 sum, 3.1e-6 in fp16 and fp32 storage as well; dec.mid.block_1 1.9e-6,
+# dec.head 1.6e-6, every other block <= 1.21e-6), fp16 6.85e-4 (dec.up.0.block.0; dec.mid.block_1 6.3e-4, dec.up.1.block.0 6.2e-4, every
+# block 4.0e-4 .. 6.9e-4 except the fp32-output heads), fp32 3.25e-6 (the upsampling and stride-2 convs dec.up.2.us / dec.up.1.us /
+# enc.down.1.ds: 3.2e-6 / 2.9e-6 / 2.9e-6, dec.mid.block_1 2.7e-6, every other block <= 2.0e-6).  VQ: at most 1 position of an image's
+# 4096 (2.4e-4) differs from the float64 argmin, within the fp32-rounding slack, in split and fp16 decodes alike - the worst image of the
+# fp32 CPU oracle differs in one position too.
+TOL = {"split": 5e-6, "fp16": 2.5e-3, "fp32": 1e-5}
+F_AEFLASH, F_AEFLASH_S = 9, 10   # Engine.FAMILIES
+
+_models = {}
+_worst = {}   # (block, prec) -> worst per-image error over the cases run so far
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _table():
+    """after the module: the table of the worst per-image error per block and precision over every case that ran (-s)"""
+    yield
+    if not _worst:
+        return
+    precs = [p for p in TOL if any(pp == p for _, pp in _worst)]
+    names = list(dict.fromkeys(n for n, _ in _worst))
+    print("\nworst per-image error per block (max |engine - float64| / max |float64|, teacher-forced):")
+    print(f"{'block':<20}" + "".join(f"{p:>12}" for p in precs))
+    for n in names:
+        print(f"{n:<20}" + "".join(f"{_worst.get((n, p), float('nan')):>12.3e}" for p in precs))
+    print(f"{'worst block':<20}" + "".join(f"{max(v for (n, pp), v in _worst.items() if pp == p and not n.startswith('dec.idx')):>12.3e}" for p in precs))
+    print(f"{'tolerance':<20}" + "".join(f"{TOL[p]:>12.1e}" for p in precs))
+    _models.clear()
+
+
+def _model(key, gpu):
+    if key not in _models:
+        ap = to_plain(load_config(CONFIGS[key]))["autoencoder"]["params"]
+        asd = H.synth.synthetic_state_dict(ae_param_spec(ap), H.SEED_W)
+        sd64 = {k: v.double() for k, v in asd.items()}
+        eng = Engine(unet_params=None, ae_params=ap, device=gpu)
+        eng.load_state_dicts(ae_sd=asd)
+        eng.mark_weights_ready()
+        _models[key] = (ap, asd, sd64, eng)
+    return _models[key]
+
+
+def _pick(B):
+    """8 images spread over the batch, the first and the last included (all of a smaller batch)"""
+    return sorted(set(int(v) for v in np.linspace(0, B - 1, min(8, B)).round()))
+
+
+def _launches(shapes, part, M, N, K):
+    """launches of the implicit-GEMM families (not the streaming attention kernels, which are noted as T x T x C) with this shape"""
+    return sum(s["launches"] for s in shapes
+               if s["part"] == part and s["family"] not in (F_AEFLASH, F_AEFLASH_S) and (s["M"], s["N"], s["K"]) == (M, N, K))
+
+
+def check_kernels(ap, call, B, h, w, attn, subpixel, folded, fam, shapes):
+    """the case ran what it is there for: `fam` = launches per kernel family of the traced pass (Engine.profile_families), `shapes` = the
+    launch shapes of the profiled pass (Engine.profile_shapes)"""
+    dd = ap["ddconfig"]
+    mult = [int(m) for m in dd["ch_mult"]]
+    part = "encoder" if call == "encode" else "decoder"
+    f = 2 ** (len(mult) - 1)
+    hl, wl = (h // f, w // f) if call == "encode" else (h, w)    # the mid block's plane
+    C, T = int(dd["ch"]) * mult[-1], hl * wl
+    want = {"flash16": (1, 0), "flash_split": (0, 1), "rows": (0, 0)}[attn]
+    assert (fam[F_AEFLASH], fam[F_AEFLASH_S]) == want, (attn, fam)
+    s_gemm = _launches(shapes, part, T, T, C)
+    if attn == "rows":   # Q K^T into the materialised score matrix (the softmax kernel reads it): [T, T] with K = C, once per image chunk
+        assert s_gemm >= 1, shapes
+    else:
+        assert s_gemm == 0, shapes
+    assert set(subpixel) | set(folded) == (set(range(1, len(mult))) if call != "encode" else set()), (subpixel, folded)
+    for l in range(len(mult) - 1, 0, -1):
+        c = int(dd["ch"]) * mult[l]
+        s = 2 ** (len(mult) - 1 - l)
+        m_lo = B * hl * s * wl * s
+        n_sub, n_fold = _launches(shapes, part, m_lo, c, 4 * c), _launches(shapes, part, 4 * m_lo, c, 9 * c)
+        if l in subpixel:
+            assert (n_sub, n_fold) == (4, 0), (l, n_sub, n_fold, shapes)
+        if l in folded:
+            assert (n_sub, n_fold) == (0, 1), (l, n_sub, n_fold, shapes)
+
+
+def check_blocks(plan, host, trace, out, idx, asd, sd64, pick, prec, tol, worst):
+    """every block of the plan, teacher-forced, in float64, per image.  `host`: the plan's host inputs (fp32, the picked images),
+    `trace`: name -> fp32 [picked, C, H, W] of the engine's records, `out`: the call's output, `idx`: the engine's VQ indices [picked, h*w]
+    (or None), `asd` / `sd64`: the fp32 / float64 weights; returns (failures, missing)"""
+    last = plan[-1].name
+    failures, missing = [], []
+
+    def engine(name):
+        if name in host:
+            return host[name]
+        return out if name == last else trace.get(name)
+
+    for s in plan:
+        if s.name == "dec.idx":
+            if "dec.zq.z" not in trace:
+                missing.append("dec.zq.z")
+                continue
+            if not torch.equal(trace["dec.zq.z"], host["z"]):
+                failures.append("dec.zq.z: the latents the VQ kernel saw are not the call's input")
+            e64 = sd64["quantize.embedding.weight"]
+            for k, b in enumerate(pick):
+                differ, bad, _ = H.vq_check(trace["dec.zq.z"][k:k + 1].double(), e64, idx[k])
+                worst[("dec.idx (differ)", prec)] = max(worst.get(("dec.idx (differ)", prec), 0.0), differ)
+                if bad or differ > H.VQ_CAP:
+                    failures.append(f"dec.idx: image {b}: {bad} wrong indices, {differ:.2e} of the positions differ from the float64 argmin (cap {H.VQ_CAP:.0e})")
+            continue
+        got = engine(s.name)
+        if got is None:
+            missing.append(s.name)
+            continue
+        if s.name == "dec.zq":
+            # the codebook row of the ENGINE's index through the reference's fp32 expression: bit for bit
+            ref = oc.vq_lookup(asd, host["z"], idx.reshape(-1).long())
+            row = asd["quantize.embedding.weight"][idx.reshape(-1).long()].view(len(pick), host["z"].shape[2], host["z"].shape[3], -1).permute(0, 3, 1, 2)
+            if not torch.equal(got, ref):
+                failures.append(f"dec.zq: not the codebook row of the engine's index ({(got != ref).sum().item()} elements differ)")
+            if not bool(((got - row).abs() <= 2.0 ** -23 * (host["z"].abs() + row.abs())).all()):
+                failures.append("dec.zq: further from the codebook row than the roundings of z + (e - z)")
+            continue
+        ins = [engine(i) for i in s.inputs]
+        if any(v is None for v in ins):
+            continue   # (an input block is missing: reported above)
+        ref = s.fn(*[v.double() for v in ins])
+        assert ref.dtype == torch.float64 and got.shape == ref.shape, (s.name, ref.dtype, got.shape, ref.shape)
+        got = got.double()
+        for k, b in enumerate(pick):
+            e = ((got[k] - ref[k]).abs().max() / ref[k].abs().max().clamp_min(1e-30)).item()
+            worst[(s.name, prec)] = max(worst.get((s.name, prec), 0.0), e)
+            if not np.isfinite(e) or e > tol:
+                failures.append(f"{s.name}: image {b} error {e:.3e} > {tol:.1e}")
+        del ref, got, ins
+    return failures, missing
+
+
+@pytest.mark.parametrize("key,call,B,h,w,prec,attn,subpixel,folded", CASES, ids=[f"{c[0]}-{c[1]}-B{c[2]}-{c[3]}x{c[4]}-{c[5]}" for c in CASES])
+def test_every_autoencoder_block_against_float64(gpu, key, call, B, h, w, prec, attn, subpixel, folded):
+    ap, asd, sd64, eng = _model(key, gpu)
+    p = parse_precision(prec)
+    if call == "encode":
+        x = torch.rand(B, 3, h, w, generator=torch.Generator().manual_seed(1000 + B)) * 2 - 1
+        plan, hname = oc.ae_encode_plan(sd64, ap), "x"
+        run = lambda: (eng.vq_encode(x.to(gpu), prec=p), None)
+    else:
+        x = H.vq_latents(B, int(ap["embed_dim"]), h, w, 2000 + B)
+        plan, hname = oc.ae_decode_plan(sd64, ap, force_not_quantize=call == "decode_nq"), "z"
+        if call == "decode":
+            run = lambda: eng.vq_decode(x.to(gpu), prec=p, return_indices=True)
+        else:
+            run = lambda: (eng.vq_decode(x.to(gpu), force_not_quantize=True, prec=p), None)
+    pick = _pick(B)
+    want = [s.name for s in plan] + ["dec.zq.z"]
+
+    # the same pass untraced and traced: same bits, same network launches
+    eng.debug_enable(False)
+    out, idx = run()
+    torch.cuda.synchronize()
+    n_plain = eng.last_launch_count()
+    eng.debug_enable(True)
+    try:
+        out_tr, idx_tr = run()
+        n_traced = eng.last_launch_count()
+        fam = [n for name, fl, ms, n in eng.profile_families()]
+        recs = eng.debug_records()
+        trace = {k: v.cpu() for k, v in eng.debug_trace(names=want, images=pick).items()}
+    finally:
+        eng.debug_enable(False)
+    assert torch.equal(out, out_tr) and (idx is None or torch.equal(idx, idx_tr)), "a traced pass computes something else than an untraced one"
+    assert n_plain == n_traced, (n_plain, n_traced)
+    names = [n for n, _ in recs]
+    assert len(set(names)) == len(names), names
+    if call == "decode_nq":
+        assert not any(n.startswith("dec.zq") for n in names), names
+    cap = sum(-(-int(np.prod(d)) * 4 // 256) * 256 for _, d in recs)
+    # ... and once more with the profiler's brackets, for the launch shapes: still the same bits
+    eng.profile_enable(True)
+    try:
+        out_pr, _ = run()
+        torch.cuda.synchronize()
+        shapes, _ = eng.profile_shapes()
+    finally:
+        eng.profile_enable(False)
+    assert torch.equal(out, out_pr)
+    kernels = None
+    try:
+        check_kernels(ap, call, B, h, w, attn, subpixel, folded, fam, shapes)
+    except AssertionError as err:   # (reported after the blocks, so that one run shows both)
+        kernels = err
+
+    host = {hname: x[pick]}
+    idx_p = idx.view(B, -1)[pick].cpu() if call == "decode" else None
+    failures, missing = check_blocks(plan, host, trace, out[pick].cpu(), idx_p, asd, sd64, pick, prec, TOL[prec], _worst)
+    worst = max((v for (n, pp), v in _worst.items() if pp == prec and not n.startswith("dec.idx")), default=0.0)
+    print(f"\n{key} {call} B={B} {h}x{w} {prec}: {len(plan)} blocks x {len(pick)} images, {n_traced} launches, {len(recs)} records, capture region "
+          f"{cap / 2 ** 30:.2f} GiB, worst {prec} error so far {worst:.3e}")
+    assert not missing, f"blocks of the plan missing from the trace: {missing}"
+    assert not failures, "\n".join(failures[:40])
+    if kernels is not None:
+        raise kernels
