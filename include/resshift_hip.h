@@ -181,6 +181,28 @@ int rs_tile_finalize(float* acc, const float* count, int B, int C, int H, int W,
  * encode_first_stage (models/gaussian_diffusion.py:514).  -2 when the window overhangs the plane by a full plane size or more. */
 int rs_window_copy(const float* in, float* out, long long planes, int H, int W, int h0, int w0, int Ho, int Wo, float scale, void* stream);
 
+/* ---- tile pool (resshift_amd/tilepool.py): tiles of DIFFERENT images in one launch -------------------------------
+ * One descriptor per tile, passed by value to the kernels (host array, at most RS_MAX_ROWS per call).  (H, W) is the LR plane of the
+ * tile's image, (h0, w0, th, tw) the tile's window in it (utils/util_image.py:946-952; th = min(pch_size, H), likewise tw). */
+typedef struct rs_tile_desc {
+    const float* src;      /* gather:  dev, [C_src,H,W] LR planes of the tile's image (the mask, if any, as last plane) */
+    float* acc;            /* scatter: dev, [C,H*sf,W*sf] running sum of the tile's image                              */
+    float* count;          /* scatter: dev, [H*sf,W*sf] tiles that covered each pixel so far                           */
+    int H, W, h0, w0, th, tw;
+} rs_tile_desc;
+/* for tile k < n: out_lq[k] [3,Hp,Wp] (and out_mask[k] [1,Hp,Wp] when C_src == 4, else out_mask is NULL) = the window of desc[k].src,
+ * reflect-padded on the bottom / right edge RELATIVE TO THE WINDOW (row i reads window row i < th ? i : 2(th-1) - i), which is
+ * F.pad(mode='reflect') of the cropped tile (sampler.py:130-138 after util_image.py:946-952).  One launch instead of a crop, the
+ * channel split and two paddings per tile.  -2: n outside 1 .. RS_MAX_ROWS, C_src not 3 / 4, a null pointer, a window that leaves its
+ * plane, th > Hp or tw > Wp, a reflect pad of a full tile side or more. */
+int rs_tile_gather(const rs_tile_desc* desc, int n, int C_src, float* out_lq, float* out_mask, int Hp, int Wp, void* stream);
+/* for tile k < n: desc[k].acc[:, h0*sf : (h0+th)*sf, w0*sf : (w0+tw)*sf] += tiles[k][:, :th*sf, :tw*sf] (tiles [n,C,Hp_out,Wp_out]) and
+ * desc[k].count += 1 there: ImageSpliterTh.update (util_image.py:954-970) for tiles of several images at once.  Tiles of one call may
+ * overlap in one canvas: every canvas element is written by ONE thread, which adds the covering tiles in index order onto the value
+ * already there - the bits of n successive rs_tile_accumulate calls in index order, no atomics.  Descriptors with the same `acc` must
+ * agree in count, H and W; distinct canvases must not alias.  -2: as rs_tile_gather, sf < 1, th*sf > Hp_out or tw*sf > Wp_out. */
+int rs_tile_scatter(const rs_tile_desc* desc, int n, int C, int sf, const float* tiles, int Hp_out, int Wp_out, void* stream);
+
 /* uint8 pre / post processing on the device.
  * rs_u8_to_input:  interleaved uint8 [B,H,W,C] -> planar fp32 [B,C,H,W] in [-1,1]  ((v/255 - 0.5)/0.5; replaces
  *                  datapipe/datasets.py:59-63 ToTensor + Normalize on the host)

@@ -1,7 +1,7 @@
 """resshift_amd — MI355X-native ResShift sampling hot path (HIP kernels behind a C ABI, drop-in Python host)."""
 from .config import load_config  # noqa: F401
 
-__all__ = ["load_config", "UNetModelSwin", "VQModelTorch", "create_gaussian_diffusion", "ResShiftSampler", "Engine"]
+__all__ = ["load_config", "UNetModelSwin", "VQModelTorch", "create_gaussian_diffusion", "ResShiftSampler", "Engine", "TilePool"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch/HIP until a class is used
@@ -15,6 +15,8 @@ def __getattr__(name):  # lazy: importing the package must not require torch/HIP
         from .sampler import ResShiftSampler as v
     elif name == "Engine":
         from .engine import Engine as v
+    elif name == "TilePool":
+        from .tilepool import TilePool as v
     else:
         raise AttributeError(name)
     return v

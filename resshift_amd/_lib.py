@@ -74,6 +74,12 @@ class StepArgs(C.Structure):
     ]
 
 
+class TileDesc(C.Structure):
+    """rs_tile_desc: one tile of the tile pool's gather / scatter launches"""
+    _fields_ = [("src", C.c_void_p), ("acc", C.c_void_p), ("count", C.c_void_p),
+                ("H", C.c_int), ("W", C.c_int), ("h0", C.c_int), ("w0", C.c_int), ("th", C.c_int), ("tw", C.c_int)]
+
+
 _P, _I, _F, _LL, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t
 
 # name -> (restype, argtypes); every symbol declared in include/resshift_hip.h is listed here.
@@ -101,6 +107,8 @@ SIGNATURES = {
     "rs_tile_accumulate": (_I, [_P, _P, _P] + [_I] * 8 + [_P]),
     "rs_tile_finalize": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rs_window_copy": (_I, [_P, _P, _LL, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "rs_tile_gather": (_I, [C.POINTER(TileDesc), _I, _I, _P, _P, _I, _I, _P]),
+    "rs_tile_scatter": (_I, [C.POINTER(TileDesc), _I, _I, _I, _P, _I, _I, _P]),
     "rs_u8_to_input": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rs_output_to_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rs_arena_bytes": (_SZ, [_P]),
@@ -199,3 +207,50 @@ def window_copy(x, h0=0, w0=0, ho=None, wo=None, scale=1.0, out=None):
                          f"(got {out.dtype}, {tuple(out.shape)}, contiguous={out.is_contiguous()}, {out.device})")
     check(load().rs_window_copy(x.data_ptr(), out.data_ptr(), planes, H, W, h0, w0, ho, wo, float(scale), current_stream_ptr()), "rs_window_copy")
     return out
+
+
+def _tile_descs(rows):
+    arr = (TileDesc * len(rows))()
+    for d, r in zip(arr, rows):
+        d.src, d.acc, d.count, d.H, d.W, d.h0, d.w0, d.th, d.tw = r
+    return arr
+
+
+def tile_gather(tiles, out_lq, out_mask=None):
+    """rs_tile_gather: `tiles` = [(src [C_src,H,W] fp32 device tensor, h0, w0, th, tw)], at most RS_MAX_ROWS, possibly of different images
+    (one C_src); writes their windows, reflect-padded on the bottom / right to out_lq's [n,3,Hp,Wp] (and out_mask's [n,1,Hp,Wp] from
+    plane 3 when C_src is 4).  One launch, no allocation: the outputs are the caller's (contiguous fp32, e.g. rows of a dense pool)."""
+    n = len(tiles)
+    Hp, Wp = out_lq.shape[-2:]
+    for t in (out_lq, out_mask):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == n):
+            raise ValueError(f"tile_gather: outputs must be contiguous float32 device tensors with {n} rows")
+    for src, *_ in tiles:
+        if not (src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 3 and src.shape[0] == tiles[0][0].shape[0]):
+            raise ValueError("tile_gather: every source must be a contiguous float32 device tensor [C_src,H,W] with the same C_src")
+    descs = _tile_descs([(src.data_ptr(), None, None, src.shape[1], src.shape[2], h0, w0, th, tw) for src, h0, w0, th, tw in tiles])
+    check(load().rs_tile_gather(descs, n, int(tiles[0][0].shape[0]) if n else 0, out_lq.data_ptr(), out_mask.data_ptr() if out_mask is not None else None,
+                                Hp, Wp, current_stream_ptr()), "rs_tile_gather")
+
+
+def tile_scatter(tiles, batch, sf):
+    """rs_tile_scatter: `tiles` = [(acc [C,H*sf,W*sf], count [H*sf,W*sf], H, W, h0, w0, th, tw)] for the rows of `batch` [n,C,Hp_out,Wp_out]:
+    adds each row's top-left (th*sf) x (tw*sf) crop into its canvas window and 1 into the count there - one launch, the bits of
+    rs_tile_accumulate called tile by tile in index order (tiles of one launch may overlap)."""
+    n = len(tiles)
+    if not (batch.is_cuda and batch.dtype == torch.float32 and batch.is_contiguous() and batch.dim() == 4 and batch.shape[0] == n):
+        raise ValueError(f"tile_scatter: the tiles must be one contiguous float32 device tensor [{n},C,Hp,Wp]")
+    Cc = int(batch.shape[1])
+    for acc, cnt, H, W, *_ in tiles:
+        if not (acc.is_cuda and acc.dtype == cnt.dtype == torch.float32 and acc.is_contiguous() and cnt.is_contiguous()
+                and tuple(acc.shape) == (Cc, H * sf, W * sf) and tuple(cnt.shape) == (H * sf, W * sf)):
+            raise ValueError(f"tile_scatter: a canvas must be contiguous float32 [{Cc},H*sf,W*sf] with its count plane [H*sf,W*sf]")
+    descs = _tile_descs([(None, acc.data_ptr(), cnt.data_ptr(), H, W, h0, w0, th, tw) for acc, cnt, H, W, h0, w0, th, tw in tiles])
+    check(load().rs_tile_scatter(descs, n, Cc, int(sf), batch.data_ptr(), int(batch.shape[2]), int(batch.shape[3]), current_stream_ptr()), "rs_tile_scatter")
+
+
+def tile_finalize(acc, count):
+    """rs_tile_finalize on one image's canvas [C,H,W] and its count plane [H,W] (contiguous fp32 device tensors): acc /= count in place"""
+    Cc, H, W = acc.shape
+    check(load().rs_tile_finalize(acc.data_ptr(), count.data_ptr(), 1, Cc, H, W, current_stream_ptr()), "rs_tile_finalize")
+    return acc

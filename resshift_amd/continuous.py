@@ -10,8 +10,9 @@ keeps a dense pool of active images and, per `step()`:
   3. retires the images that just finished t = 0 as ONE `rs_sample_end` batch (decode) and compacts the pool;
   4. crops and clamps each result as `ResShiftSampler.sample_func` does.
 
-Same engine, precision policy and `padding_offset` as the sampler it wraps.  One LR size per instance.  Out of scope: per-step mixed
-precision policies, `noise_repeat`, tiling (`sample_tiled`), pixel-space models (no autoencoder).
+Same engine, precision policy and `padding_offset` as the sampler it wraps.  One LR size per instance: images of any size, cut into
+tiles that share such pools, are `tilepool.TilePool`'s business (it drives one ContinuousSampler per padded tile shape).  Out of scope:
+per-step mixed precision policies, `noise_repeat`, pixel-space models (no autoencoder).
 """
 from __future__ import annotations
 
@@ -24,18 +25,24 @@ import torch
 from . import _lib, sharding
 
 
+def check_sampler(sampler, max_batch, who: str = "ContinuousSampler"):
+    """what a pool of images at different steps asks of the sampler it wraps; returns the per-step UNet precisions"""
+    if getattr(sampler, "autoencoder", None) is None:
+        raise NotImplementedError(f"{who} samples in the VQ latent space: the sampler needs an autoencoder")
+    if max_batch is not None and not 1 <= int(max_batch) <= _lib.RS_MAX_ROWS:
+        raise ValueError(f"max_batch must be 1 .. {_lib.RS_MAX_ROWS} (RS_MAX_ROWS), got {max_batch}")
+    precs = sampler.base_diffusion._unet_precisions()
+    if len(set(precs)) > 1:
+        raise NotImplementedError(f"{who} needs one UNet precision for every step; this policy varies it by step (mixedK)")
+    return precs
+
+
 class ContinuousSampler:
     def __init__(self, sampler, max_batch: int = 32, keep_aux: bool = False):
         """`keep_aux`: also keep each finished image's final latent and VQ indices in `self.aux[id]` ({"z_final", "indices"}, as
         p_sample_loop's return_aux)"""
-        if getattr(sampler, "autoencoder", None) is None:
-            raise NotImplementedError("ContinuousSampler samples in the VQ latent space: the sampler needs an autoencoder")
-        if not 1 <= int(max_batch) <= _lib.RS_MAX_ROWS:
-            raise ValueError(f"max_batch must be 1 .. {_lib.RS_MAX_ROWS} (RS_MAX_ROWS), got {max_batch}")
+        precs = check_sampler(sampler, max_batch)
         d = sampler.base_diffusion
-        precs = d._unet_precisions()
-        if len(set(precs)) > 1:
-            raise NotImplementedError("ContinuousSampler needs one UNet precision for every step; this policy varies it by step (mixedK)")
         self.sampler, self.diffusion, self.engine = sampler, d, sampler.engine
         self.max_batch = int(max_batch)
         self.tables = d.step_tables()
@@ -127,11 +134,29 @@ class ContinuousSampler:
         if self._M is not None:
             self._M[a:b] = torch.stack([r[2] for r in reqs])
         self._N[a:b] = torch.stack([r[3] for r in reqs])
+        self._begin(a, b, [r[0] for r in reqs])
+
+    def _begin(self, a: int, b: int, ids: List[int]):
+        """slots a .. b-1 hold new images (LR planes, mask, draws): ONE rs_sample_begin batch makes their x_T"""
         self.engine.sample_begin(self._Y[a:b], self._N[a:b, 0].contiguous(), self.tables, self.sf, self.scale_factor,
                                  prec_encode=self.prec_encode, out=self._X[a:b])
-        self._ids += [r[0] for r in reqs]
-        self._t += [self.steps - 1] * m
+        self._ids += ids
+        self._t += [self.steps - 1] * (b - a)
         self._n = b
+
+    def _admit_rows(self, ids: List[int], draws: List[torch.Tensor], shape, fill):
+        """(private: tilepool.py)  Admit len(ids) <= max_batch - active images whose LR planes are ALREADY of the padded shape `shape`
+        (hp, wp) and are written in place by `fill(Y_rows [m,3,hp,wp], M_rows [m,1,hp,wp] | None)` - straight into the pool, no staging
+        copy; draws[i] [steps+1,Cz,hz,wz] as submit() stacks them.  Nothing waits in this instance's own queue then."""
+        m = len(ids)
+        assert 0 < m <= self.max_batch - self._n and not self._waiting
+        if self._X is None:
+            hp, wp = shape
+            self._alloc(torch.empty(3, hp, wp, device="meta"), torch.empty(1, hp, wp, device="meta") if self.cond_mask else None, draws[0])
+        a, b = self._n, self._n + m
+        fill(self._Y[a:b], self._M[a:b] if self._M is not None else None)
+        self._N[a:b] = torch.stack(draws)
+        self._begin(a, b, list(ids))
 
     def _compact(self, keep: List[int]):
         k = len(keep)
@@ -147,9 +172,21 @@ class ContinuousSampler:
     def step(self) -> Dict[int, torch.Tensor]:
         """admit -> one step of every active image -> retire; returns {id: image [3, h*sf, w*sf] in [-1,1]} of the images that finished"""
         self._admit()
+        ids, img = self._step_batch()
+        out: Dict[int, torch.Tensor] = {}
+        if ids:
+            h, w = self.lr_size
+            img = img[:, :, : h * self.sf, : w * self.sf].clamp_(-1.0, 1.0)   # sample_func's crop and clamp
+            for j, i in enumerate(ids):
+                out[i] = img[j]
+        return out
+
+    def _step_batch(self):
+        """one step of every active image -> retire: (ids, decoded batch [len(ids),3,hp*sf,wp*sf] of the PADDED shape, not yet clamped) of
+        the images that finished, or ([], None)"""
         n = self._n
         if n == 0:
-            return {}
+            return [], None
         # this step's draw of each slot: draw k = steps - t (draw 0 is the prior noise)
         k = torch.tensor([self.steps - t for t in self._t], device=self.device, dtype=torch.long)
         noise = self._N[torch.arange(n, device=self.device), k]
@@ -157,7 +194,7 @@ class ContinuousSampler:
                                 mask=self._M[:n] if self._M is not None else None, prec=self.prec_unet)
         done = [i for i in range(n) if self._t[i] == 0]
         self._t = [t - 1 for t in self._t]
-        out: Dict[int, torch.Tensor] = {}
+        ids, img = [], None
         if done:
             x0 = self._X[:n].index_select(0, torch.tensor(done, device=self.device, dtype=torch.long))
             hp, wp = self._Y.shape[2], self._Y.shape[3]
@@ -167,12 +204,9 @@ class ContinuousSampler:
                 per = aux["indices"].numel() // len(done)
                 for j, i in enumerate(done):
                     self.aux[self._ids[i]] = {"z_final": aux["z_final"][j], "indices": aux["indices"][j * per:(j + 1) * per]}
-            h, w = self.lr_size
-            img = img[:, :, : h * self.sf, : w * self.sf].clamp_(-1.0, 1.0)   # sample_func's crop and clamp
-            for j, i in enumerate(done):
-                out[self._ids[i]] = img[j]
+            ids = [self._ids[i] for i in done]
             self._compact([i for i in range(n) if self._t[i] >= 0])
-        return out
+        return ids, img
 
     def drain(self) -> Dict[int, torch.Tensor]:
         """step until nothing is waiting or in flight"""

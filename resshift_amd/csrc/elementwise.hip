@@ -10,6 +10,7 @@
 #include "common.h"
 #include "../../include/resshift_hip.h"
 #include <algorithm>
+#include <string>
 
 namespace {
 
@@ -246,6 +247,80 @@ __global__ void tile_finalize_kernel(float* acc, const float* count, long long B
         acc[g] = acc[g] / count[g % HW];
 }
 
+// ---- tile pool (resshift_amd/tilepool.py): the same data movement for tiles of DIFFERENT images in one launch --------
+// The descriptors travel by value (64 x 48 B = 3 KB of the 4 KB kernel-argument segment).  blockIdx.y is the tile, so a workgroup's
+// descriptor - and every descriptor the scatter kernel walks - is wave-uniform: the compiler reads them with scalar loads.
+// V = 4: every row group is four consecutive floats, 16-byte aligned on the output side (the launcher checks widths and pointers).
+struct TileDescs { rs_tile_desc d[RS_MAX_ROWS]; };
+
+// out_lq[k][c][i][j] = src_k[c][h0 + refl(i, th)][w0 + refl(j, tw)] (c < 3), out_mask[k][0][i][j] likewise from plane 3;
+// refl(i, n) = i < n ? i : 2 (n - 1) - i as in window_copy_kernel, but relative to the tile's window: F.pad(mode='reflect') of the CROP
+template <int V>
+__global__ __launch_bounds__(256) void tile_gather_kernel(TileDescs ds, int C, float* out_lq, float* out_mask, int Hp, int Wp) {
+    const int k = blockIdx.y;
+    const float* src = ds.d[k].src;
+    const int H = ds.d[k].H, W = ds.d[k].W, h0 = ds.d[k].h0, w0 = ds.d[k].w0, th = ds.d[k].th, tw = ds.d[k].tw;
+    const int Wv = Wp / V, n = C * Hp * Wv;
+    // a group that lies inside the window is one 16-byte load when the plane's rows and the window's origin keep the alignment
+    const bool al = V > 1 && ((W | w0) % V) == 0 && ((uintptr_t)src % (V * sizeof(float))) == 0;
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < n; g += gridDim.x * blockDim.x) {
+        const int j = (g % Wv) * V, r = g / Wv;
+        const int i = r % Hp, c = r / Hp;
+        const int yi = i < th ? i : 2 * (th - 1) - i;
+        const float* row = src + ((long long)c * H + h0 + yi) * W + w0;
+        float* dst = c < 3 ? out_lq + (((long long)k * 3 + c) * Hp + i) * Wp + j : out_mask + ((long long)k * Hp + i) * Wp + j;
+        if constexpr (V == 4) {
+            f32x4 v;
+            if (al && j + V <= tw) {
+                v = *(const f32x4*)(row + j);
+            } else {
+#pragma unroll
+                for (int e = 0; e < V; ++e) { const int x = j + e; v[e] = row[x < tw ? x : 2 * (tw - 1) - x]; }
+            }
+            *(f32x4*)dst = v;
+        } else {
+            *dst = row[j < tw ? j : 2 * (tw - 1) - j];
+        }
+    }
+}
+
+// does tile d of a launch cover canvas element (Y, X) of canvas `acc`?
+__device__ __forceinline__ bool tile_covers(const rs_tile_desc& d, const float* acc, int sf, int Y, int X) {
+    return d.acc == acc && Y >= d.h0 * sf && Y < (d.h0 + d.th) * sf && X >= d.w0 * sf && X < (d.w0 + d.tw) * sf;
+}
+// acc_k[c][h0 sf + i][w0 sf + j] += tiles[k][c][i][j] over the tile's (th sf) x (tw sf) window, count_k += 1 there.  Tiles of one launch
+// may overlap in one canvas, so the thread of tile k's element owns its canvas element only when no tile j < k covers it, and then adds
+// tiles k, k+1, ... n-1 that cover it, in that order, onto the value already there: the floating-point additions of n successive
+// tile_accumulate_kernel launches in index order, one writer per element, no atomics.  (V = 4: all window edges are multiples of 4 canvas
+// columns, so the four elements of a group are covered by the same tiles.)
+template <int V>
+__global__ __launch_bounds__(256) void tile_scatter_kernel(TileDescs ds, int n, int C, int sf, const float* tiles, int Hpo, int Wpo) {
+    typedef float vec __attribute__((ext_vector_type(V)));
+    const int k = blockIdx.y;
+    float* acc = ds.d[k].acc;
+    float* count = ds.d[k].count;
+    const int Hc = ds.d[k].H * sf, Wc = ds.d[k].W * sf, y0 = ds.d[k].h0 * sf, x0 = ds.d[k].w0 * sf;
+    const int hh = ds.d[k].th * sf, wv = ds.d[k].tw * sf / V, total = C * hh * wv;
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < total; g += gridDim.x * blockDim.x) {
+        const int r = g / wv;
+        const int X = x0 + (g % wv) * V, Y = y0 + r % hh, c = r / hh;
+        bool own = true;
+        for (int j = 0; j < k && own; ++j) own = !tile_covers(ds.d[j], acc, sf, Y, X);
+        if (!own) continue;
+        float* pa = acc + ((long long)c * Hc + Y) * Wc + X;
+        float* pc = count + (long long)Y * Wc + X;
+        vec v = *(const vec*)pa;
+        vec cv = c == 0 ? *(const vec*)pc : (vec)(0.0f);
+        for (int j = k; j < n; ++j) {
+            if (!tile_covers(ds.d[j], acc, sf, Y, X)) continue;
+            v += *(const vec*)(tiles + (((long long)j * C + c) * Hpo + (Y - ds.d[j].h0 * sf)) * Wpo + (X - ds.d[j].w0 * sf));
+            cv += 1.0f;
+        }
+        *(vec*)pa = v;
+        if (c == 0) *(vec*)pc = cv;
+    }
+}
+
 inline unsigned nblk(long long n, int bs = 256, long long cap = 65536) { return (unsigned)std::min<long long>((n + bs - 1) / bs, cap); }
 
 }  // namespace
@@ -420,6 +495,70 @@ int rs_window_copy(const float* in, float* out, long long planes, int H, int W, 
         return -2;
     const long long n = planes * Ho * Wo;
     hipLaunchKernelGGL(window_copy_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, in, out, planes, H, W, h0, w0, Ho, Wo, scale);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int rs_set_last_error(const char* text, int rc);   // engine.hip (rs_last_error's text)
+
+// what both tile-pool entry points ask of a descriptor array; nullptr when it is fine
+static const char* tile_descs_error(const rs_tile_desc* desc, int n) {
+    if (n < 1 || n > RS_MAX_ROWS) return "tile count outside 1 .. RS_MAX_ROWS";
+    if (!desc) return "null descriptor array";
+    for (int k = 0; k < n; ++k) {
+        const rs_tile_desc& d = desc[k];
+        if (d.H < 1 || d.W < 1 || d.th < 1 || d.tw < 1 || d.h0 < 0 || d.w0 < 0 || d.h0 + d.th > d.H || d.w0 + d.tw > d.W)
+            return "a tile window leaves its plane";
+    }
+    return nullptr;
+}
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int rs_tile_gather(const rs_tile_desc* desc, int n, int C_src, float* out_lq, float* out_mask, int Hp, int Wp, void* stream) {
+    if (const char* e = tile_descs_error(desc, n)) return rs_set_last_error((std::string("rs_tile_gather: ") + e).c_str(), -2);
+    if (C_src != 3 && C_src != 4) return rs_set_last_error("rs_tile_gather: C_src must be 3 (LR planes) or 4 (LR planes + mask)", -2);
+    if (!out_lq) return rs_set_last_error("rs_tile_gather: null tensor (out_lq)", -2);
+    if ((C_src == 4) != (out_mask != nullptr)) return rs_set_last_error("rs_tile_gather: out_mask goes with C_src == 4, and only with it", -2);
+    TileDescs ds{};
+    for (int k = 0; k < n; ++k) {
+        const rs_tile_desc& d = desc[k];
+        if (!d.src) return rs_set_last_error("rs_tile_gather: null tensor (desc.src)", -2);
+        if (d.th > Hp || d.tw > Wp) return rs_set_last_error("rs_tile_gather: a tile is larger than the padded shape (th > Hp or tw > Wp)", -2);
+        // (one reflection at most, as torch.nn.functional.pad requires: the pad is smaller than the padded side)
+        if (Hp - d.th >= d.th || Wp - d.tw >= d.tw) return rs_set_last_error("rs_tile_gather: reflect padding of a full tile side or more", -2);
+        ds.d[k] = d;
+    }
+    const bool v4 = (Wp % 4) == 0 && al16(out_lq) && al16(out_mask);
+    const long long per = (long long)C_src * Hp * (v4 ? Wp / 4 : Wp);
+    if (per > 0x7fffffffLL) return rs_set_last_error("rs_tile_gather: padded tile too large", -2);
+    const dim3 grid(nblk(per, 256, 256), (unsigned)n);
+    if (v4) hipLaunchKernelGGL(tile_gather_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, ds, C_src, out_lq, out_mask, Hp, Wp);
+    else hipLaunchKernelGGL(tile_gather_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, ds, C_src, out_lq, out_mask, Hp, Wp);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int rs_tile_scatter(const rs_tile_desc* desc, int n, int C, int sf, const float* tiles, int Hp_out, int Wp_out, void* stream) {
+    if (const char* e = tile_descs_error(desc, n)) return rs_set_last_error((std::string("rs_tile_scatter: ") + e).c_str(), -2);
+    if (C < 1 || sf < 1) return rs_set_last_error("rs_tile_scatter: C and sf must be positive", -2);
+    if (!tiles) return rs_set_last_error("rs_tile_scatter: null tensor (tiles)", -2);
+    TileDescs ds{};
+    bool v4 = (Wp_out % 4) == 0 && al16(tiles);
+    long long per = 0;
+    for (int k = 0; k < n; ++k) {
+        const rs_tile_desc& d = desc[k];
+        if (!d.acc || !d.count) return rs_set_last_error("rs_tile_scatter: null tensor (desc.acc / desc.count)", -2);
+        if ((long long)d.th * sf > Hp_out || (long long)d.tw * sf > Wp_out)
+            return rs_set_last_error("rs_tile_scatter: a tile's window is larger than the tile tensor (th*sf > Hp_out or tw*sf > Wp_out)", -2);
+        for (int j = 0; j < k; ++j)
+            if (desc[j].acc == d.acc && (desc[j].count != d.count || desc[j].H != d.H || desc[j].W != d.W))
+                return rs_set_last_error("rs_tile_scatter: descriptors of one canvas disagree about its count plane or size", -2);
+        v4 = v4 && ((d.w0 * sf) % 4) == 0 && ((d.tw * sf) % 4) == 0 && ((d.W * sf) % 4) == 0 && al16(d.acc) && al16(d.count);
+        per = std::max(per, (long long)C * d.th * sf * d.tw * sf);
+        ds.d[k] = d;
+    }
+    if (per > 0x7fffffffLL) return rs_set_last_error("rs_tile_scatter: tile too large", -2);
+    const dim3 grid(nblk(v4 ? per / 4 : per, 256, 256), (unsigned)n);
+    if (v4) hipLaunchKernelGGL(tile_scatter_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, ds, n, C, sf, tiles, Hp_out, Wp_out);
+    else hipLaunchKernelGGL(tile_scatter_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, ds, n, C, sf, tiles, Hp_out, Wp_out);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

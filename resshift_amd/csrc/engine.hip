@@ -2059,6 +2059,8 @@ struct rs_engine {
 extern "C" {
 
 const char* rs_last_error(void) { return g_err.c_str(); }
+// (internal, not in the header: the entry points of the other translation units report their argument errors through this)
+int rs_set_last_error(const char* text, int rc) { g_err = text; return rc; }
 
 rs_engine* rs_create(const rs_config* cfg) {
     if (!cfg) { g_err = "null config"; return nullptr; }

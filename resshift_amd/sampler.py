@@ -206,11 +206,16 @@ class ResShiftSampler(BaseSampler):
         im = np.asarray(Image.open(path).convert("L" if gray else "RGB"), dtype=np.uint8)
         return torch.from_numpy(im.reshape(im.shape[0], im.shape[1], -1).copy())
 
-    def inference(self, in_path, out_path, mask_path=None, mask_back=True, bs=1, noise_repeat=False):
+    POOL_LOOKAHEAD = 128   # inference(pool=True) reads files ahead until this many tiles wait for a slot
+
+    def inference(self, in_path, out_path, mask_path=None, mask_back=True, bs=1, noise_repeat=False, pool=False):
         """sampler.py:167-308: batches of `bs` images are sharded over the ranks exactly like sampler.py:273-277; every
         rank writes its own PNGs.  uint8 -> [-1,1] (datapipe/datasets.py:59-63), the inpainting blend (sampler.py:218-222)
         and the final clamp / round to uint8 (utils/util_image.py:245-269) run on the device (rs_u8_to_input /
-        rs_output_to_u8): only uint8 pixels cross PCIe.  Inputs larger than `chop_size` take the tiled path."""
+        rs_output_to_u8): only uint8 pixels cross PCIe.  Inputs larger than `chop_size` take the tiled path.
+        `pool=True`: the files of this rank's share (same sharding) are read one by one - their sizes may differ - and submitted to ONE
+        `tilepool.TilePool`, whose batches hold tiles of several images; each PNG is written when its image completes.  Files are
+        submitted ahead while fewer than POOL_LOOKAHEAD tiles wait, then the pool steps."""
         in_path, out_path = Path(in_path), Path(out_path)
         if self.rank == 0:
             out_path.mkdir(parents=True, exist_ok=True)
@@ -226,6 +231,11 @@ class ResShiftSampler(BaseSampler):
         from PIL import Image
 
         micro = math.ceil(bs / self.num_gpus)   # sampler.py:274-277: the slice width comes from bs, also on the last, partial batch
+        if pool:
+            self._inference_pool(files, out_path, mask_path, mask_back, bs, micro, single, noise_repeat)
+            sharding.barrier()
+            self.write_log(f"Processing done, enjoy the results in {out_path}")
+            return
         for b0 in range(0, len(files), bs):
             batch = files[b0:b0 + bs]
             mine = batch[self.rank * micro:(self.rank + 1) * micro]
@@ -244,3 +254,33 @@ class ResShiftSampler(BaseSampler):
                     Image.fromarray(im if im.shape[2] != 1 else im[:, :, 0]).save(out_path / f"{p.stem}.png")
         sharding.barrier()
         self.write_log(f"Processing done, enjoy the results in {out_path}")
+
+    def _inference_pool(self, files, out_path, mask_path, mask_back, bs, micro, single, noise_repeat):
+        from PIL import Image
+
+        from .tilepool import TilePool
+
+        if noise_repeat:
+            raise NotImplementedError("noise_repeat shares one draw across a batch; the tile pool has no fixed batch")
+        tp = TilePool(self)
+        kept = {}   # image id -> (file, lq, mask) until its PNG is written
+
+        def write(done):
+            for rid, sr in done.items():
+                p, lq, mask = kept.pop(rid)
+                blend = mask is not None and mask_back
+                im = self.engine.output_to_u8(sr.unsqueeze(0), lq=lq if blend else None, mask=mask if blend else None)[0].cpu().numpy()
+                Image.fromarray(im if im.shape[2] != 1 else im[:, :, 0]).save(out_path / f"{p.stem}.png")
+
+        for b0 in range(0, len(files), bs):
+            for p in files[b0:b0 + bs][self.rank * micro:(self.rank + 1) * micro]:
+                lq = self.engine.u8_to_input(self._read_image_u8(p).unsqueeze(0).to(self.device))
+                mask = None
+                if mask_path is not None:
+                    mp = Path(mask_path) if single else Path(mask_path) / p.name
+                    mask = self.engine.u8_to_input(self._read_image_u8(mp, gray=True).unsqueeze(0).to(self.device))
+                kept[tp.submit(lq, mask=mask)] = (p, lq, mask)
+                while tp.waiting_tiles() >= self.POOL_LOOKAHEAD:
+                    write(tp.step())
+        while tp.pending():
+            write(tp.step())
