@@ -170,6 +170,31 @@ int rs_axpbypcz(const float* x, const float* z, const float* n, float* y, float 
 int rs_axpbypcz_rows(const float* x, const float* z, const float* n, float* y, const float* a, const float* b, const float* c,
                      long long per_image_count, int B, void* stream);
 
+/* ---- per-request seeds: Philox noise generated inside the sampler ---------------------------------
+ * A draw is a pure function of (seed, stream, draw index, element index): element i (index in the image's OWN latent [Cz,hz,wz], NCHW
+ * order) of draw k (k = 0: the prior draw of prior_sample, gaussian_diffusion.py:446,517-529; k = steps - t: the draw of the step at step
+ * index t, :358) is Box-Muller on Philox4x32-10 with counter (i / 4, k, stream, 0) and key (seed & 0xffffffff, seed >> 32); words
+ * (w0, w1) give elements 4q, 4q+1 and (w2, w3) elements 4q+2, 4q+3: u1 = ((wa >> 8) + 1) 2^-24, u2 = (wb >> 8) 2^-24,
+ * r = sqrtf(-2 logf(u1)), pair = (r cospi(2 u2), r sinpi(2 u2)).  `seed` names the request, `stream` a sub-request (the tile index
+ * inside an image; 0 for a whole image).  Equal keys give equal noise bits in any call, batch, slot or process. */
+typedef struct rs_noise_key {
+    uint64_t seed;
+    uint32_t stream;
+    uint32_t reserved;     /* must be 0 */
+} rs_noise_key;
+/* out[b][i] = normal i of draw draw[b] of keys[b] (dense fp32 [B][per_image_count]; keys and draw are HOST arrays): the definition
+ * above made callable, for tests and for a host that wants tensors.  -2: B outside 1 .. RS_MAX_ROWS, null pointer, reserved != 0,
+ * negative draw, per_image_count < 1. */
+int rs_noise_fill(const rs_noise_key* keys, const int* draw, float* out, long long per_image_count, int B, void* stream);
+/* rs_sample / rs_sample_begin / rs_sample_step with the noise generated in registers by the kernel that consumes it: image b uses
+ * keys[b] (HOST array of a->B resp. s->B keys) and the `noise` member of the struct is ignored.  Same launches as the tensor calls
+ * (rs_last_launch_count), bit for bit what the tensor call gives when fed rs_noise_fill's output.  rs_sample_seeded accepts any B
+ * (keys of a batch above RS_MAX_ROWS are copied to the device once per call); rs_sample_step_seeded keeps rs_sample_step's
+ * RS_MAX_ROWS rule for mixed step indices.  -2: null keys, reserved != 0, B out of range. */
+int rs_sample_seeded(rs_engine* e, const rs_sample_args* a, const rs_noise_key* keys);
+int rs_sample_begin_seeded(rs_engine* e, const rs_sample_args* a, float* x_T, const rs_noise_key* keys);
+int rs_sample_step_seeded(rs_engine* e, const rs_step_args* s, const rs_noise_key* keys);
+
 /* overlap-average tiling of large images (utils/util_image.py:889-979 ImageSpliterTh.update / .gather): NCHW fp32,
  * acc[b,c,h0:h0+th,w0:w0+tw] += tile, count[h0:h0+th,w0:w0+tw] += 1; finalize divides acc by count in place */
 int rs_tile_accumulate(float* acc, float* count, const float* tile, int B, int C, int H, int W, int h0, int w0, int th, int tw,

@@ -80,6 +80,25 @@ class TileDesc(C.Structure):
                 ("H", C.c_int), ("W", C.c_int), ("h0", C.c_int), ("w0", C.c_int), ("th", C.c_int), ("tw", C.c_int)]
 
 
+class NoiseKey(C.Structure):
+    """rs_noise_key: `seed` names a request, `stream` a sub-request (tile index inside an image; 0 for a whole image); 16 bytes"""
+    _fields_ = [("seed", C.c_uint64), ("stream", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def noise_keys(keys):
+    """[(seed, stream) | seed | NoiseKey] -> (NoiseKey * n); seeds are taken modulo 2^64, streams must fit 32 bits"""
+    arr = (NoiseKey * max(1, len(keys)))()
+    for d, k in zip(arr, keys):
+        if isinstance(k, NoiseKey):
+            d.seed, d.stream, d.reserved = k.seed, k.stream, k.reserved
+            continue
+        seed, stream = (k if isinstance(k, (tuple, list)) else (k, 0))
+        if not 0 <= int(stream) < 2 ** 32:
+            raise ValueError(f"noise key stream {stream} does not fit 32 bits")
+        d.seed, d.stream, d.reserved = int(seed) % 2 ** 64, int(stream), 0
+    return arr
+
+
 _P, _I, _F, _LL, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t
 
 # name -> (restype, argtypes); every symbol declared in include/resshift_hip.h is listed here.
@@ -104,6 +123,10 @@ SIGNATURES = {
     "rs_film_prewarm": (_I, [_P, C.POINTER(C.c_int), _I, _P]),
     "rs_axpbypcz": (_I, [_P, _P, _P, _P, _F, _F, _F, _LL, _P]),
     "rs_axpbypcz_rows": (_I, [_P, _P, _P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _LL, _I, _P]),
+    "rs_noise_fill": (_I, [C.POINTER(NoiseKey), C.POINTER(C.c_int), _P, _LL, _I, _P]),
+    "rs_sample_seeded": (_I, [_P, C.POINTER(SampleArgs), C.POINTER(NoiseKey)]),
+    "rs_sample_begin_seeded": (_I, [_P, C.POINTER(SampleArgs), _P, C.POINTER(NoiseKey)]),
+    "rs_sample_step_seeded": (_I, [_P, C.POINTER(StepArgs), C.POINTER(NoiseKey)]),
     "rs_tile_accumulate": (_I, [_P, _P, _P] + [_I] * 8 + [_P]),
     "rs_tile_finalize": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rs_window_copy": (_I, [_P, _P, _LL, _I, _I, _I, _I, _I, _I, _F, _P]),

@@ -12,7 +12,12 @@ keeps a dense pool of active images and, per `step()`:
 
 Same engine, precision policy and `padding_offset` as the sampler it wraps.  One LR size per instance: images of any size, cut into
 tiles that share such pools, are `tilepool.TilePool`'s business (it drives one ContinuousSampler per padded tile shape).  Out of scope:
-per-step mixed precision policies, `noise_repeat`, pixel-space models (no autoencoder).
+per-step mixed precision policies, `noise_repeat` (it is defined by a fixed batch, which a pool does not have - in either noise mode),
+pixel-space models (no autoencoder).
+
+`seeded=True`: a request is named by a seed and its noise is generated inside the engine's kernels from
+(seed, stream, draw index, element index) - no torch.randn at submit time, no draws in the pool, no per-step gather.  What a request
+gets no longer depends on the requests before it, on its slot or on the process that serves it.
 """
 from __future__ import annotations
 
@@ -23,6 +28,12 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib, sharding
+
+
+def request_seed(base_seed: int, index: int) -> int:
+    """The default seed of request `index` under a sampler seeded with `base_seed`: (base_seed * 2^32 + index) mod 2^64 - distinct for
+    every index below 2^32, and a pure function of the two numbers (no generator state)."""
+    return ((int(base_seed) << 32) + int(index)) % 2 ** 64
 
 
 def check_sampler(sampler, max_batch, who: str = "ContinuousSampler"):
@@ -38,9 +49,9 @@ def check_sampler(sampler, max_batch, who: str = "ContinuousSampler"):
 
 
 class ContinuousSampler:
-    def __init__(self, sampler, max_batch: int = 32, keep_aux: bool = False):
+    def __init__(self, sampler, max_batch: int = 32, keep_aux: bool = False, seeded: bool = False):
         """`keep_aux`: also keep each finished image's final latent and VQ indices in `self.aux[id]` ({"z_final", "indices"}, as
-        p_sample_loop's return_aux)"""
+        p_sample_loop's return_aux).  `seeded`: requests carry a (seed, stream) key instead of noise tensors (module docstring)."""
         precs = check_sampler(sampler, max_batch)
         d = sampler.base_diffusion
         self.sampler, self.diffusion, self.engine = sampler, d, sampler.engine
@@ -63,16 +74,24 @@ class ContinuousSampler:
         self._ids: List[int] = []
         self._t: List[int] = []          # step index of each slot's next step (steps-1 .. 0)
         self._X = self._Y = self._M = self._N = None
+        self.seeded = bool(seeded)
+        self._keys: List[tuple] = []     # seeded: (seed, stream) of each slot (no _N then)
         self.keep_aux = bool(keep_aux)
         self.aux: Dict[int, Dict[str, torch.Tensor]] = {}
 
     # ------------------------------------------------------------------ requests
-    def submit(self, lq, mask=None, noise=None, step_noises=None, noise_repeat=False) -> List[int]:
+    def submit(self, lq, mask=None, noise=None, step_noises=None, noise_repeat=False, seed=None, stream=0) -> List[int]:
         """Queue LR images lq [n,3,h,w] (or [3,h,w]) in [-1,1]; returns one id per image.  `noise` [n,Cz,hz,wz] and `step_noises`
         (steps tensors [n,Cz,hz,wz], in loop order) inject the draws; otherwise they are drawn now, in the reference's order (prior
-        noise, then one per step: gaussian_diffusion.py:446,358)."""
+        noise, then one per step: gaussian_diffusion.py:446,358).
+        Seeded mode: `seed` (an int for every image of the call, or one per image; default request_seed(sampler.seed, id)) and `stream`
+        name each image's noise; tensors are rejected.  `noise_repeat` is unsupported in both modes."""
         if noise_repeat:
             raise NotImplementedError("noise_repeat shares one draw across a batch; continuous batching has no fixed batch")
+        if self.seeded and (noise is not None or step_noises is not None):
+            raise ValueError("a seeded ContinuousSampler generates its noise from seeds: noise / step_noises tensors are not accepted")
+        if not self.seeded and (seed is not None or stream != 0):
+            raise ValueError("seed= / stream= need ContinuousSampler(..., seeded=True)")
         if lq.dim() == 3:
             lq = lq.unsqueeze(0)
             mask = mask.unsqueeze(0) if mask is not None and mask.dim() == 3 else mask
@@ -89,6 +108,17 @@ class ContinuousSampler:
         if self._pad != (0, 0):   # sample_func's reflect padding (sampler.py:130-138), the mask alike
             lq = sharding.reflect_pad(lq, *self._pad)
             mask = sharding.reflect_pad(mask, *self._pad) if mask is not None else None
+        if self.seeded:
+            seeds = [int(v) for v in seed] if isinstance(seed, (list, tuple)) else [seed] * n
+            if len(seeds) != n:
+                raise ValueError(f"seed: {n} images but {len(seeds)} seeds")
+            ids = []
+            for i in range(n):
+                sd = seeds[i] if seeds[i] is not None else request_seed(getattr(self.sampler, "seed", 0), self._next_id)
+                self._waiting.append((self._next_id, lq[i], mask[i] if mask is not None else None, (int(sd) % 2 ** 64, int(stream))))
+                ids.append(self._next_id)
+                self._next_id += 1
+            return ids
         zs = self.engine.latent_shape(n, lq.shape[2], lq.shape[3], self.sf)
         if noise is None:
             noise = torch.randn(zs, device=self.device, dtype=torch.float32)
@@ -117,10 +147,12 @@ class ContinuousSampler:
     # ------------------------------------------------------------------ scheduling
     def _alloc(self, y, m, draws):
         B = self.max_batch
-        self._X = torch.empty((B,) + tuple(draws.shape[1:]), device=self.device, dtype=torch.float32)
+        zs = tuple(self.engine.latent_shape(1, y.shape[-2], y.shape[-1], self.sf))[1:] if self.seeded else tuple(draws.shape[1:])
+        self._X = torch.empty((B,) + zs, device=self.device, dtype=torch.float32)
         self._Y = torch.empty((B,) + tuple(y.shape), device=self.device, dtype=torch.float32)
         self._M = torch.empty((B,) + tuple(m.shape), device=self.device, dtype=torch.float32) if m is not None else None
-        self._N = torch.empty((B,) + tuple(draws.shape), device=self.device, dtype=torch.float32)
+        if not self.seeded:   # (seeded: the draws are never stored)
+            self._N = torch.empty((B,) + tuple(draws.shape), device=self.device, dtype=torch.float32)
 
     def _admit(self):
         m = min(len(self._waiting), self.max_batch - self._n)
@@ -133,13 +165,19 @@ class ContinuousSampler:
         self._Y[a:b] = torch.stack([r[1] for r in reqs])
         if self._M is not None:
             self._M[a:b] = torch.stack([r[2] for r in reqs])
-        self._N[a:b] = torch.stack([r[3] for r in reqs])
-        self._begin(a, b, [r[0] for r in reqs])
+        if not self.seeded:
+            self._N[a:b] = torch.stack([r[3] for r in reqs])
+        self._begin(a, b, [r[0] for r in reqs], [r[3] for r in reqs] if self.seeded else None)
 
-    def _begin(self, a: int, b: int, ids: List[int]):
-        """slots a .. b-1 hold new images (LR planes, mask, draws): ONE rs_sample_begin batch makes their x_T"""
-        self.engine.sample_begin(self._Y[a:b], self._N[a:b, 0].contiguous(), self.tables, self.sf, self.scale_factor,
-                                 prec_encode=self.prec_encode, out=self._X[a:b])
+    def _begin(self, a: int, b: int, ids: List[int], keys=None):
+        """slots a .. b-1 hold new images (LR planes, mask, draws - or, seeded, their `keys`): ONE rs_sample_begin batch makes their x_T"""
+        if self.seeded:
+            self.engine.sample_begin(self._Y[a:b], None, self.tables, self.sf, self.scale_factor, prec_encode=self.prec_encode,
+                                     out=self._X[a:b], keys=list(keys))
+            self._keys += list(keys)
+        else:
+            self.engine.sample_begin(self._Y[a:b], self._N[a:b, 0].contiguous(), self.tables, self.sf, self.scale_factor,
+                                     prec_encode=self.prec_encode, out=self._X[a:b])
         self._ids += ids
         self._t += [self.steps - 1] * (b - a)
         self._n = b
@@ -147,16 +185,19 @@ class ContinuousSampler:
     def _admit_rows(self, ids: List[int], draws: List[torch.Tensor], shape, fill):
         """(private: tilepool.py)  Admit len(ids) <= max_batch - active images whose LR planes are ALREADY of the padded shape `shape`
         (hp, wp) and are written in place by `fill(Y_rows [m,3,hp,wp], M_rows [m,1,hp,wp] | None)` - straight into the pool, no staging
-        copy; draws[i] [steps+1,Cz,hz,wz] as submit() stacks them.  Nothing waits in this instance's own queue then."""
+        copy; draws[i] [steps+1,Cz,hz,wz] as submit() stacks them - seeded: draws[i] = the image's (seed, stream) key.  Nothing waits in this
+        instance's own queue then."""
         m = len(ids)
         assert 0 < m <= self.max_batch - self._n and not self._waiting
         if self._X is None:
             hp, wp = shape
-            self._alloc(torch.empty(3, hp, wp, device="meta"), torch.empty(1, hp, wp, device="meta") if self.cond_mask else None, draws[0])
+            self._alloc(torch.empty(3, hp, wp, device="meta"), torch.empty(1, hp, wp, device="meta") if self.cond_mask else None,
+                        None if self.seeded else draws[0])
         a, b = self._n, self._n + m
         fill(self._Y[a:b], self._M[a:b] if self._M is not None else None)
-        self._N[a:b] = torch.stack(draws)
-        self._begin(a, b, list(ids))
+        if not self.seeded:
+            self._N[a:b] = torch.stack(draws)
+        self._begin(a, b, list(ids), draws if self.seeded else None)
 
     def _compact(self, keep: List[int]):
         k = len(keep)
@@ -167,6 +208,7 @@ class ContinuousSampler:
                     P[:k] = P.index_select(0, idx)
         self._ids = [self._ids[i] for i in keep]
         self._t = [self._t[i] for i in keep]
+        self._keys = [self._keys[i] for i in keep] if self.seeded else self._keys
         self._n = k
 
     def step(self) -> Dict[int, torch.Tensor]:
@@ -187,11 +229,15 @@ class ContinuousSampler:
         n = self._n
         if n == 0:
             return [], None
-        # this step's draw of each slot: draw k = steps - t (draw 0 is the prior noise)
-        k = torch.tensor([self.steps - t for t in self._t], device=self.device, dtype=torch.long)
-        noise = self._N[torch.arange(n, device=self.device), k]
-        self.engine.sample_step(self._X[:n], self._Y[:n], list(self._t), noise, self.tables, self.sf,
-                                mask=self._M[:n] if self._M is not None else None, prec=self.prec_unet)
+        if self.seeded:   # draw steps - t of each slot's key, generated by the kernel that adds it
+            self.engine.sample_step(self._X[:n], self._Y[:n], list(self._t), None, self.tables, self.sf,
+                                    mask=self._M[:n] if self._M is not None else None, prec=self.prec_unet, keys=list(self._keys))
+        else:
+            # this step's draw of each slot: draw k = steps - t (draw 0 is the prior noise)
+            k = torch.tensor([self.steps - t for t in self._t], device=self.device, dtype=torch.long)
+            noise = self._N[torch.arange(n, device=self.device), k]
+            self.engine.sample_step(self._X[:n], self._Y[:n], list(self._t), noise, self.tables, self.sf,
+                                    mask=self._M[:n] if self._M is not None else None, prec=self.prec_unet)
         done = [i for i in range(n) if self._t[i] == 0]
         self._t = [t - 1 for t in self._t]
         ids, img = [], None

@@ -8,6 +8,7 @@
 //   VQ:       VectorQuantizer2.forward ldm/modules/vqvae/quantize.py:271-312 (expanded-form distance,
 //             first-minimum argmin, straight-through expression z + (z_q - z)).
 #include "common.h"
+#include "philox.h"
 #include "../../include/resshift_hip.h"
 #include <algorithm>
 #include <string>
@@ -77,14 +78,21 @@ __global__ void convert_kernel(const TI* src, TO* dst, int C, long long npix) {
     }
 }
 
+// the combine expression of every kernel of this family (tensor noise or generated noise): v = a x [+ b z] [+ c n].  ONE definition, so that
+// a seeded step is bit for bit the tensor step fed with noise_fill_kernel's output.  One rounded product, then one fused multiply-add
+// per further term - spelled with fmaf, so that the roundings do not depend on how the compiler contracts or if-converts a kernel's loop
+// (they are the roundings `v = a * x; v += b * z; v += c * n` has always compiled to here: v_mul_f32, v_fmac_f32, v_fmac_f32).
+__device__ __forceinline__ float axpbypcz_combine(float a, float x, bool has_z, float b, float z, bool has_n, float c, float n) {
+    float v = a * x;
+    if (has_z) v = fmaf(b, z, v);
+    if (has_n) v = fmaf(c, n, v);
+    return v;
+}
+
 // y = a*x + b*z + c*n   (all fp32, any layout as long as all operands share it)
 __global__ void axpbypcz_kernel(const float* x, const float* z, const float* n, float* y, float a, float b, float c, long long cnt) {
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < cnt; g += (long long)gridDim.x * blockDim.x) {
-        float v = a * x[g];
-        if (z) v += b * z[g];
-        if (n) v += c * n[g];
-        y[g] = v;
-    }
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < cnt; g += (long long)gridDim.x * blockDim.x)
+        y[g] = axpbypcz_combine(a, x[g], z != nullptr, b, z ? z[g] : 0.f, n != nullptr, c, n ? n[g] : 0.f);
 }
 
 // the same with one (a, b, c) per image: image r = g / per covers elements [r * per, (r + 1) * per).  The coefficients travel by value
@@ -95,10 +103,69 @@ struct RowCoefs { float a[RS_MAX_ROWS], b[RS_MAX_ROWS], c[RS_MAX_ROWS]; };
 __global__ void axpbypcz_rows_kernel(const float* x, const float* z, const float* n, float* y, RowCoefs k, long long per, long long cnt) {
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < cnt; g += (long long)gridDim.x * blockDim.x) {
         const int r = (int)(g / per);
-        float v = k.a[r] * x[g];
-        if (z) v += k.b[r] * z[g];
-        if (n && k.c[r] != 0.f) v += k.c[r] * n[g];
-        y[g] = v;
+        const bool has_n = n && k.c[r] != 0.f;
+        y[g] = axpbypcz_combine(k.a[r], x[g], z != nullptr, k.b[r], z ? z[g] : 0.f, has_n, k.c[r], has_n ? n[g] : 0.f);
+    }
+}
+
+// ---- per-request seeds (philox.h) ---------------------------------------------------------------------
+// Keys and draw indices travel by value next to RowCoefs (64 x 16 B + 64 x 4 B); blockIdx.y is the image, so key, draw and
+// coefficients are wave-uniform.  A batch of more than RS_MAX_ROWS images (rs_sample_seeded: every image at one step) reads its keys
+// from `kdev` (device copy) and shares row 0 of the coefficients and draws.
+struct RowKeys { rs_noise_key k[RS_MAX_ROWS]; int draw[RS_MAX_ROWS]; };
+
+// out[b][i] = normal i of draw nk.draw[b] of key nk.k[b]: the specification made callable.  Thread = one Philox call = four elements;
+// V4: per % 4 == 0 and a 16-byte aligned `out` (one 16-byte store), else element by element (a latent that is no multiple of 4 drops
+// the surplus).
+template <bool V4>
+__global__ __launch_bounds__(256) void noise_fill_kernel(float* out, RowKeys nk, long long per) {
+    const int b = blockIdx.y;
+    const rs_noise_key key = nk.k[b];
+    const uint32_t draw = (uint32_t)nk.draw[b];
+    float* o = out + (long long)b * per;
+    const long long nq = (per + 3) / 4;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
+        float n[4];
+        rs_noise4(key.seed, key.stream, draw, (uint32_t)q, n);
+        if constexpr (V4) {
+            f32x4 v = {n[0], n[1], n[2], n[3]};
+            *(f32x4*)(o + 4 * q) = v;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * q + e < per) o[4 * q + e] = n[e];
+        }
+    }
+}
+
+// y = a[b] x + b[b] z + c[b] n(key[b], draw[b]) per image b: axpbypcz_rows_kernel with the noise made in registers.  c[b] == 0 (an
+// image at t = 0) skips the generator.  In place (y == x) is fine: a thread reads its own four elements before it writes them.
+template <bool V4>
+__global__ __launch_bounds__(256) void axpbypcz_seeded_kernel(const float* x, const float* z, float* y, RowCoefs k, RowKeys nk,
+                                                              const rs_noise_key* kdev, int uniform, long long per) {
+    const int b = blockIdx.y, r = uniform ? 0 : b;
+    const rs_noise_key key = kdev ? kdev[b] : nk.k[b];
+    const uint32_t draw = (uint32_t)nk.draw[r];
+    const float ca = k.a[r], cb = k.b[r], cc = k.c[r];
+    const bool has_z = z != nullptr, has_n = cc != 0.f;
+    const long long base = (long long)b * per, nq = (per + 3) / 4;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
+        float n[4] = {0.f, 0.f, 0.f, 0.f};
+        if (has_n) rs_noise4(key.seed, key.stream, draw, (uint32_t)q, n);
+        const long long g = base + 4 * q;
+        if constexpr (V4) {
+            const f32x4 xv = *(const f32x4*)(x + g);
+            f32x4 zv = {0.f, 0.f, 0.f, 0.f};
+            if (has_z) zv = *(const f32x4*)(z + g);
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = axpbypcz_combine(ca, xv[e], has_z, cb, zv[e], has_n, cc, n[e]);
+            *(f32x4*)(y + g) = v;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * q + e < per) y[g + e] = axpbypcz_combine(ca, x[g + e], has_z, cb, has_z ? z[g + e] : 0.f, has_n, cc, n[e]);
+        }
     }
 }
 
@@ -447,6 +514,54 @@ int rs_axpbypcz_rows_launch(const float* x, const float* z, const float* n, floa
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int rs_set_last_error(const char* text, int rc);   // engine.hip (rs_last_error's text)
+
+static inline bool al16f(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// what the seeded entry points ask of a key array; nullptr when it is fine
+static const char* noise_keys_error(const rs_noise_key* keys, int B) {
+    if (!keys) return "null keys";
+    for (int b = 0; b < B; ++b)
+        if (keys[b].reserved != 0) return "a key's reserved field is not 0";
+    return nullptr;
+}
+static inline dim3 seeded_grid(long long per, int B) { return dim3(nblk((per + 3) / 4, 256, 1024), (unsigned)B); }
+
+int rs_noise_fill(const rs_noise_key* keys, const int* draw, float* out, long long per_image_count, int B, void* stream) {
+    if (B < 1 || B > RS_MAX_ROWS) return rs_set_last_error("rs_noise_fill: B must be 1 .. RS_MAX_ROWS", -2);
+    if (const char* e = noise_keys_error(keys, B)) return rs_set_last_error((std::string("rs_noise_fill: ") + e).c_str(), -2);
+    if (!draw || !out) return rs_set_last_error("rs_noise_fill: null draw indices or output", -2);
+    if (per_image_count < 1 || per_image_count > 0x3ffffffffLL) return rs_set_last_error("rs_noise_fill: per_image_count outside 1 .. 2^34 - 1", -2);
+    RowKeys nk{};
+    for (int b = 0; b < B; ++b) {
+        if (draw[b] < 0) return rs_set_last_error("rs_noise_fill: negative draw index", -2);
+        nk.k[b] = keys[b]; nk.draw[b] = draw[b];
+    }
+    const dim3 grid = seeded_grid(per_image_count, B);
+    if ((per_image_count % 4) == 0 && al16f(out)) hipLaunchKernelGGL(noise_fill_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, out, nk, per_image_count);
+    else hipLaunchKernelGGL(noise_fill_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, out, nk, per_image_count);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// y = a x + b z + c noise(keys, draw) per image.  B <= RS_MAX_ROWS: keys (host), a / b / c / draw (host, [B]) by value.  B > RS_MAX_ROWS:
+// `keys_dev` (device, [B]) and ONE coefficient triple / draw index (a[0], b[0], c[0], draw[0]) for every image.
+int rs_axpbypcz_seeded_launch(const float* x, const float* z, float* y, const float* a, const float* b, const float* c, const rs_noise_key* keys,
+                              const rs_noise_key* keys_dev, const int* draw, long long per, int B, hipStream_t st) {
+    const bool big = B > RS_MAX_ROWS;
+    if (B < 1 || per < 1 || per > 0x3ffffffffLL || !x || !y || !a || !draw || (big ? !keys_dev : !keys)) return -2;
+    RowCoefs k{};
+    RowKeys nk{};
+    for (int r = 0; r < (big ? 1 : B); ++r) {
+        k.a[r] = a[r]; k.b[r] = b ? b[r] : 0.f; k.c[r] = c ? c[r] : 0.f;
+        nk.draw[r] = draw[r];
+        if (!big) nk.k[r] = keys[r];
+    }
+    const dim3 grid = seeded_grid(per, B);
+    const bool v4 = (per % 4) == 0 && al16f(x) && al16f(y) && al16f(z);
+    if (v4) hipLaunchKernelGGL(axpbypcz_seeded_kernel<true>, grid, dim3(256), 0, st, x, z, y, k, nk, big ? keys_dev : nullptr, big ? 1 : 0, per);
+    else hipLaunchKernelGGL(axpbypcz_seeded_kernel<false>, grid, dim3(256), 0, st, x, z, y, k, nk, big ? keys_dev : nullptr, big ? 1 : 0, per);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int rs_film_gather_launch(const float* const* rows, int B, int total, float* out, hipStream_t st) {
     if (B < 1 || B > RS_MAX_ROWS || total < 1) return -2;
     FilmRows s{};
@@ -497,8 +612,6 @@ int rs_window_copy(const float* in, float* out, long long planes, int H, int W, 
     hipLaunchKernelGGL(window_copy_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, in, out, planes, H, W, h0, w0, Ho, Wo, scale);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-
-int rs_set_last_error(const char* text, int rc);   // engine.hip (rs_last_error's text)
 
 // what both tile-pool entry points ask of a descriptor array; nullptr when it is fine
 static const char* tile_descs_error(const rs_tile_desc* desc, int n) {

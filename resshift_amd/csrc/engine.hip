@@ -56,6 +56,8 @@ int rs_nhwc_to_nchw_launch(const void* in, int in_dt, float* out, int B, int C, 
 int rs_axpbypcz_launch(const float* x, const float* z, const float* n, float* y, float a, float b, float c, long long cnt, hipStream_t st);
 int rs_axpbypcz_rows_launch(const float* x, const float* z, const float* n, float* y, const float* a, const float* b, const float* c, long long per,
                             int B, hipStream_t st);
+int rs_axpbypcz_seeded_launch(const float* x, const float* z, float* y, const float* a, const float* b, const float* c, const rs_noise_key* keys,
+                              const rs_noise_key* keys_dev, const int* draw, long long per, int B, hipStream_t st);
 int rs_film_gather_launch(const float* const* rows, int B, int total, float* out, hipStream_t st);
 int rs_nchw_to_nhwc_rows_launch(const float* in, void* out, int out_dt, int B, int C, int HW, int ldo, int coff, const float* scale, hipStream_t st);
 int rs_clamp_launch(float* x, float lo, float hi, long long cnt, hipStream_t st);
@@ -475,6 +477,21 @@ struct rs_engine {
     long long last_igemm_launches = 0, last_gn_launches = 0;
     bool debug = false;
     std::vector<TraceRec> trace;                        // records of the last traced call (Exec::tr)
+    // per-request seeds (philox.h): the keys of a seeded batch of more than RS_MAX_ROWS images, copied to the device once per call
+    rs_noise_key* keys_dev = nullptr; size_t keys_cap = 0;
+    const rs_noise_key* stage_keys(const rs_noise_key* keys, int B, hipStream_t st) {
+        if (rs_fake_device()) return (const rs_noise_key*)(uintptr_t)4096;   // (never dereferenced: every launch fails there)
+        if ((size_t)B > keys_cap) {
+            (void)hipStreamSynchronize(st);
+            if (keys_dev) (void)hipFree(keys_dev);
+            keys_dev = nullptr; keys_cap = 0;
+            if (hipMalloc((void**)&keys_dev, (size_t)B * sizeof(rs_noise_key)) != hipSuccess) return nullptr;
+            keys_cap = (size_t)B;
+        }
+        // (stream-ordered and complete on return: the caller's host array may go away, and an earlier call's kernels no longer read the buffer)
+        if (hipMemcpyWithStream(keys_dev, keys, (size_t)B * sizeof(rs_noise_key), hipMemcpyHostToDevice, st) != hipSuccess) return nullptr;
+        return keys_dev;
+    }
     char* cap_base = nullptr; size_t cap_bytes = 0; bool cap_host = false;   // their capture region (run(); freed by rs_debug_enable(0))
     void free_capture() {
         if (cap_base) { if (cap_host) free(cap_base); else (void)hipFree(cap_base); }
@@ -1860,7 +1877,10 @@ struct rs_engine {
     // retires images at every step)
     int latent_div() const { return 1 << (cfg.ae.n_levels - 1); }
     // encode_first_stage(y, up_sample=True) -> * scale_factor -> prior_sample (gaussian_diffusion.py:500-529): x_T = z_y + prior_scale * noise0
-    void sample_prologue(Exec& ex, const rs_sample_args* a, float* z_y, float* xt, const float* noise0) {
+    // `keys` (seeded calls): the prior draw is draw 0 of keys[b], generated by the kernel in place of the read of noise0 (keys_dev: the device
+    // copy of a batch above RS_MAX_ROWS)
+    void sample_prologue(Exec& ex, const rs_sample_args* a, float* z_y, float* xt, const float* noise0, const rs_noise_key* keys = nullptr,
+                         const rs_noise_key* keys_dev = nullptr) {
         const rs_ae_config& ae = cfg.ae;
         const int B = a->B, Hi = a->h * a->sf, Wi = a->w * a->sf, f = latent_div();
         const long long zcount = (long long)B * ae.embed_dim * (Hi / f) * (Wi / f);
@@ -1878,7 +1898,14 @@ struct rs_engine {
         if (!ex.dry) {
             // z_y * scale_factor, then prior_sample: x_T = z_y + kappa*sqrt(eta_T)*noise (gaussian_diffusion.py:512,529)
             if (a->scale_factor != 1.0f) ex.check(rs_axpbypcz_launch(z_y, nullptr, nullptr, z_y, a->scale_factor, 0.f, 0.f, zcount, ex.st), "scale z_y");
-            ex.check(rs_axpbypcz_launch(z_y, nullptr, noise0, xt, 1.f, 0.f, a->prior_scale, zcount, ex.st), "prior_sample");
+            if (keys) {
+                const int nr = B > RS_MAX_ROWS ? 1 : B;
+                float ca[RS_MAX_ROWS], cc[RS_MAX_ROWS];
+                int dr[RS_MAX_ROWS];
+                for (int b = 0; b < nr; ++b) { ca[b] = 1.f; cc[b] = a->prior_scale; dr[b] = 0; }
+                ex.check(rs_axpbypcz_seeded_launch(z_y, nullptr, xt, ca, nullptr, cc, keys, keys_dev, dr, zcount / B, B, ex.st), "prior_sample (seeded)");
+            } else
+                ex.check(rs_axpbypcz_launch(z_y, nullptr, noise0, xt, 1.f, 0.f, a->prior_scale, zcount, ex.st), "prior_sample");
         }
     }
     // one p_sample (gaussian_diffusion.py:332-365) of every image b at its own step index t[b]: pred = model(_scale_input(x_t), tmap[t], lq),
@@ -1886,7 +1913,8 @@ struct rs_engine {
     // the per-image FiLM table (+ one gather launch), _scale_input per image inside the UNet's input conversion and the per-image
     // elementwise kernel: every image gets bit for bit what it would get in a homogeneous batch of the same size.  films[i]: cached FiLM row of step index i (rows not used may be null).
     void sample_step(Exec& ex, float* xt, float* pred, const View* feat, const float* y, const float* mask, int h, int w, int B, int hz, int wz,
-                     int prec, const int* t, const rs_sample_args* a, const float* const* films, const float* noise) {
+                     int prec, const int* t, const rs_sample_args* a, const float* const* films, const float* noise, const rs_noise_key* keys = nullptr,
+                     const rs_noise_key* keys_dev = nullptr) {
         bool mixed = false;
         for (int b = 1; b < B; ++b) mixed |= t[b] != t[0];
         const long long zcount = (long long)B * cfg.unet.in_channels * hz * wz;
@@ -1894,7 +1922,15 @@ struct rs_engine {
             const int i = t[0];
             unet_body(ex, xt, a->inv_std[i], feat, y, mask, h, w, pred, B, hz, wz, prec, films[i]);
             // mean = c1*x_t + c2*x0 (:218-221); sample = mean + [t>0]*sigma_t*eps (:358-364)
-            if (!ex.dry) ex.check(rs_axpbypcz_launch(xt, pred, i > 0 ? noise : nullptr, xt, a->coef1[i], a->coef2[i], a->sigma[i], zcount, ex.st), "posterior step");
+            if (ex.dry) return;
+            if (keys) {   // the draw of the step at step index i is draw steps - i of every image's key
+                const int nr = B > RS_MAX_ROWS ? 1 : B;
+                float ca[RS_MAX_ROWS], cb[RS_MAX_ROWS], cc[RS_MAX_ROWS];
+                int dr[RS_MAX_ROWS];
+                for (int b = 0; b < nr; ++b) { ca[b] = a->coef1[i]; cb[b] = a->coef2[i]; cc[b] = i > 0 ? a->sigma[i] : 0.f; dr[b] = a->steps - i; }
+                ex.check(rs_axpbypcz_seeded_launch(xt, pred, xt, ca, cb, cc, keys, keys_dev, dr, zcount / B, B, ex.st), "posterior step (seeded)");
+            } else
+                ex.check(rs_axpbypcz_launch(xt, pred, i > 0 ? noise : nullptr, xt, a->coef1[i], a->coef2[i], a->sigma[i], zcount, ex.st), "posterior step");
             return;
         }
         const size_t mk = ex.mark();
@@ -1907,7 +1943,12 @@ struct rs_engine {
         unet_body(ex, xt, 1.0f, feat, y, mask, h, w, pred, B, hz, wz, prec, tab, film_total, ca);
         if (!ex.dry) {
             for (int b = 0; b < B; ++b) { ca[b] = a->coef1[t[b]]; cb[b] = a->coef2[t[b]]; cc[b] = t[b] > 0 ? a->sigma[t[b]] : 0.f; }
-            ex.check(rs_axpbypcz_rows_launch(xt, pred, noise, xt, ca, cb, cc, per, B, ex.st), "posterior step (per image)");
+            if (keys) {
+                int dr[RS_MAX_ROWS];
+                for (int b = 0; b < B; ++b) dr[b] = a->steps - t[b];
+                ex.check(rs_axpbypcz_seeded_launch(xt, pred, xt, ca, cb, cc, keys, nullptr, dr, per, B, ex.st), "posterior step (per image, seeded)");
+            } else
+                ex.check(rs_axpbypcz_rows_launch(xt, pred, noise, xt, ca, cb, cc, per, B, ex.st), "posterior step (per image)");
         }
         ex.reset(mk);
     }
@@ -2085,6 +2126,7 @@ void rs_destroy(rs_engine* e) {
     if (!rs_fake_device()) {
         for (auto& kv : e->film_cache) (void)hipFree(kv.second);
         if (e->arena.base) (void)hipFree(e->arena.base);
+        if (e->keys_dev) (void)hipFree(e->keys_dev);
     }
     e->free_capture();
     delete e;
@@ -2339,7 +2381,17 @@ static std::string sample_args_error(rs_engine* e, const rs_sample_args* a, bool
 }
 
 // gaussian_diffusion.py:367-472: encode_first_stage(up_sample) -> prior_sample -> T x p_sample -> decode_first_stage
-int rs_sample(rs_engine* e, const rs_sample_args* a) {
+// what the seeded entry points ask of their keys (house style of the by-value calls: -2 and rs_last_error's text); 0 when fine
+static int noise_keys_check(const char* who, const rs_noise_key* keys, int B) {
+    if (!keys) return rs_set_last_error((std::string(who) + ": null keys").c_str(), -2);
+    if (B < 1 || B > 65535) return rs_set_last_error((std::string(who) + ": B must be 1 .. 65535").c_str(), -2);
+    for (int b = 0; b < B; ++b)
+        if (keys[b].reserved != 0) return rs_set_last_error((std::string(who) + ": keys[" + std::to_string(b) + "].reserved is not 0").c_str(), -2);
+    return 0;
+}
+
+// rs_sample (keys == nullptr: a->noise) and rs_sample_seeded (keys: a->noise is ignored)
+static int sample_impl(rs_engine* e, const rs_sample_args* a, const rs_noise_key* keys) {
     if (!e || !a) return fail("null argument");
     if (a->steps < 1 || a->steps > RS_MAX_STEPS) return fail("bad step count");
     for (int i = 0; i < a->steps; ++i) if (a->prec_unet[i] != RS_F16 && a->prec_unet[i] != RS_F32 && a->prec_unet[i] != RS_F16S) return fail("bad precision");
@@ -2347,7 +2399,7 @@ int rs_sample(rs_engine* e, const rs_sample_args* a) {
         const std::string err = sample_args_error(e, a, true, true);
         if (!err.empty()) return fail("rs_sample: " + err);
     }
-    if (!a->noise) return fail("rs_sample: bad batch / size / null tensor");
+    if (!keys && !a->noise) return fail("rs_sample: bad batch / size / null tensor");
     if (e->cfg.unet.cond_mask && !a->mask) return fail("rs_sample: this UNet is conditioned on a mask (cond_mask) but mask is NULL");
     hipStream_t st = (hipStream_t)a->stream;
     const int B = a->B, f = e->latent_div(), hz = a->h * a->sf / f, wz = a->w * a->sf / f;
@@ -2357,6 +2409,8 @@ int rs_sample(rs_engine* e, const rs_sample_args* a) {
         if (!films[t]) return fail("FiLM table allocation failed");
     }
     const long long zcount = (long long)B * e->cfg.ae.embed_dim * hz * wz;
+    const rs_noise_key* kd = nullptr;
+    if (keys && B > RS_MAX_ROWS && !(kd = e->stage_keys(keys, B, st))) return fail("rs_sample_seeded: device copy of the keys failed");
     return e->run(st, [&](Exec& ex) {
         float* z_y = (float*)ex.raw(zcount * 4);
         float* xt = (float*)ex.raw(zcount * 4);
@@ -2368,31 +2422,50 @@ int rs_sample(rs_engine* e, const rs_sample_args* a) {
                 const int pr = a->prec_unet[i];
                 if (!have_feat[pr]) { feat[pr] = e->feature_extract(ex, a->y, a->mask, B, a->h, a->w, pr); have_feat[pr] = true; }
             }
-        e->sample_prologue(ex, a, z_y, xt, a->noise);
+        e->sample_prologue(ex, a, z_y, xt, a->noise, keys, kd);
         std::vector<int> tb(B);
         for (int i = a->steps - 1, k = 1; i >= 0; --i, ++k) {
             const int pr = a->prec_unet[i];
             std::fill(tb.begin(), tb.end(), i);
             e->sample_step(ex, xt, pred, e->fe_convs.empty() ? nullptr : &feat[pr], a->y, a->mask, a->h, a->w, B, hz, wz, pr, tb.data(), a, films.data(),
-                           a->noise + (long long)k * zcount);
+                           keys ? nullptr : a->noise + (long long)k * zcount, keys, kd);
         }
         e->sample_epilogue(ex, a, xt);
     });
 }
 
-int rs_sample_begin(rs_engine* e, const rs_sample_args* a, float* x_T) {
+int rs_sample(rs_engine* e, const rs_sample_args* a) { return sample_impl(e, a, nullptr); }
+
+int rs_sample_seeded(rs_engine* e, const rs_sample_args* a, const rs_noise_key* keys) {
+    if (!e || !a) return fail("rs_sample_seeded: null argument");
+    if (const int rc = noise_keys_check("rs_sample_seeded", keys, a->B)) return rc;
+    return sample_impl(e, a, keys);
+}
+
+static int sample_begin_impl(rs_engine* e, const rs_sample_args* a, float* x_T, const rs_noise_key* keys) {
     const std::string err = sample_args_error(e, a, true, false);
     if (!err.empty()) return fail("rs_sample_begin: " + err);
-    if (!a->noise || !x_T) return fail("rs_sample_begin: null tensor (noise / x_T)");
+    if (!keys && !a->noise) return fail("rs_sample_begin: null tensor (noise / x_T)");
+    if (!x_T) return fail("rs_sample_begin: null tensor (noise / x_T)");
     const int f = e->latent_div();
     const long long zcount = (long long)a->B * e->cfg.ae.embed_dim * (a->h * a->sf / f) * (a->w * a->sf / f);
+    const rs_noise_key* kd = nullptr;
+    if (keys && a->B > RS_MAX_ROWS && !(kd = e->stage_keys(keys, a->B, (hipStream_t)a->stream))) return fail("rs_sample_begin_seeded: device copy of the keys failed");
     return e->run((hipStream_t)a->stream, [&](Exec& ex) {
         float* z_y = (float*)ex.raw(zcount * 4);
-        e->sample_prologue(ex, a, z_y, x_T, a->noise);
+        e->sample_prologue(ex, a, z_y, x_T, a->noise, keys, kd);
     });
 }
 
-int rs_sample_step(rs_engine* e, const rs_step_args* s) {
+int rs_sample_begin(rs_engine* e, const rs_sample_args* a, float* x_T) { return sample_begin_impl(e, a, x_T, nullptr); }
+
+int rs_sample_begin_seeded(rs_engine* e, const rs_sample_args* a, float* x_T, const rs_noise_key* keys) {
+    if (!e || !a) return fail("rs_sample_begin_seeded: null argument");
+    if (const int rc = noise_keys_check("rs_sample_begin_seeded", keys, a->B)) return rc;
+    return sample_begin_impl(e, a, x_T, keys);
+}
+
+static int sample_step_impl(rs_engine* e, const rs_step_args* s, const rs_noise_key* keys) {
     if (!e || !s || !s->sched) return fail("rs_sample_step: null argument");
     const rs_sample_args* a = s->sched;
     if (a->steps < 1 || a->steps > RS_MAX_STEPS) return fail("rs_sample_step: bad step count in the schedule");
@@ -2415,7 +2488,9 @@ int rs_sample_step(rs_engine* e, const rs_step_args* s) {
         noisy |= s->t[b] > 0;
     }
     if (mixed && B > RS_MAX_ROWS) return fail("rs_sample_step: mixed step indices in a batch of more than RS_MAX_ROWS (" + std::to_string(RS_MAX_ROWS) + ") images");
-    if (noisy && !s->noise) return fail("rs_sample_step: noise is NULL but an image is at t > 0");
+    if (noisy && !keys && !s->noise) return fail("rs_sample_step: noise is NULL but an image is at t > 0");
+    const rs_noise_key* kd = nullptr;
+    if (keys && B > RS_MAX_ROWS && !(kd = e->stage_keys(keys, B, (hipStream_t)s->stream))) return fail("rs_sample_step_seeded: device copy of the keys failed");
     hipStream_t st = (hipStream_t)s->stream;
     std::vector<const float*> films(a->steps, nullptr);
     for (int b = 0; b < B; ++b) {
@@ -2429,8 +2504,16 @@ int rs_sample_step(rs_engine* e, const rs_step_args* s) {
         // (feature-extractor configs: the conditioning features of this batch, per call)
         View feat; const View* fp = nullptr;
         if (!e->fe_convs.empty()) { feat = e->feature_extract(ex, s->y, s->mask, B, a->h, a->w, s->prec); fp = &feat; }
-        e->sample_step(ex, s->x, pred, fp, s->y, s->mask, a->h, a->w, B, hz, wz, s->prec, s->t, a, films.data(), s->noise);
+        e->sample_step(ex, s->x, pred, fp, s->y, s->mask, a->h, a->w, B, hz, wz, s->prec, s->t, a, films.data(), keys ? nullptr : s->noise, keys, kd);
     });
+}
+
+int rs_sample_step(rs_engine* e, const rs_step_args* s) { return sample_step_impl(e, s, nullptr); }
+
+int rs_sample_step_seeded(rs_engine* e, const rs_step_args* s, const rs_noise_key* keys) {
+    if (!e || !s) return fail("rs_sample_step_seeded: null argument");
+    if (const int rc = noise_keys_check("rs_sample_step_seeded", keys, s->B)) return rc;
+    return sample_step_impl(e, s, keys);
 }
 
 int rs_film_prewarm(rs_engine* e, const int* timesteps, int n, void* stream) {

@@ -246,6 +246,34 @@ class Engine:
         self._chk(rc, "rs_output_to_u8")
         return out
 
+    @staticmethod
+    def _keys(keys, noise, B: int, who: str):
+        """(NoiseKey * B) of a seeded call; `keys` and a noise tensor are mutually exclusive"""
+        if noise is not None:
+            raise ValueError(f"{who}: pass either noise tensors or keys= (per-request seeds), not both")
+        if len(keys) != B:
+            raise ValueError(f"{who}: {B} images but {len(keys)} keys")
+        return _lib.noise_keys(keys)
+
+    def noise_fill(self, keys, draws, shape):
+        """fp32 device tensor [len(keys), *shape]: row b holds draw `draws[b]` of key `keys[b]` ((seed, stream) pairs, bare seeds or
+        _lib.NoiseKey) for an image whose own latent has `shape` = (Cz, hz, wz) - the normals a seeded call generates in registers
+        (rs_noise_fill; draw 0 is the prior draw, draw steps - t the draw of the step at step index t)."""
+        B = len(keys)
+        if len(draws) != B:
+            raise ValueError(f"noise_fill: {B} keys but {len(draws)} draw indices")
+        shape = tuple(int(v) for v in shape)
+        per = int(np.prod(shape))
+        out = torch.empty((B,) + shape, device=self.device, dtype=torch.float32)
+        R = _lib.RS_MAX_ROWS
+        with torch.cuda.device(self.device):
+            for b0 in range(0, B, R):
+                n = min(R, B - b0)
+                dr = (C.c_int * n)(*[int(v) for v in draws[b0:b0 + n]])
+                rc = self.lib.rs_noise_fill(_lib.noise_keys(keys[b0:b0 + n]), dr, out[b0:].data_ptr(), per, n, self._stream())
+                self._chk(rc, "rs_noise_fill")
+        return out
+
     def latent_shape(self, B: int, h: int, w: int, sf: int):
         f = 2 ** (int(self.cfg.ae.n_levels) - 1)
         return (B, int(self.cfg.ae.embed_dim), h * sf // f, w * sf // f)
@@ -264,32 +292,43 @@ class Engine:
             a.prec_unet[t] = parse_precision(pu[t])
         a.prior_scale = float(tables["prior_scale"])
 
-    def sample_begin(self, y, noise, tables: Dict[str, np.ndarray], sf: int, scale_factor: float, prec_encode=F16, out=None):
-        """encode_first_stage(y, up_sample=True) -> prior_sample with the prior draw `noise` [B,Cz,hz,wz]: x_T (rs_sample_begin)."""
-        y, noise = self._f32c(y), self._f32c(noise)
+    def sample_begin(self, y, noise, tables: Dict[str, np.ndarray], sf: int, scale_factor: float, prec_encode=F16, out=None, keys=None):
+        """encode_first_stage(y, up_sample=True) -> prior_sample with the prior draw `noise` [B,Cz,hz,wz]: x_T (rs_sample_begin).
+        `keys` (one per image, see noise_fill) instead of `noise` (then None): draw 0 of each key, generated in the kernel
+        (rs_sample_begin_seeded)."""
+        y = self._f32c(y)
         B, _, h, w = y.shape
         zs = self.latent_shape(B, h, w, sf)
-        if tuple(noise.shape) != zs:
-            raise ValueError(f"sample_begin: noise must be {zs}, got {tuple(noise.shape)}")
+        karr = self._keys(keys, noise, B, "sample_begin") if keys is not None else None
+        if karr is None:
+            noise = self._f32c(noise)
+            if tuple(noise.shape) != zs:
+                raise ValueError(f"sample_begin: noise must be {zs}, got {tuple(noise.shape)}")
         x = torch.empty(zs, device=y.device, dtype=torch.float32) if out is None else out
         a = _lib.SampleArgs()
         self._schedule(a, tables)
-        a.y, a.noise, a.B, a.h, a.w, a.sf = y.data_ptr(), noise.data_ptr(), B, h, w, int(sf)
+        a.y, a.noise, a.B, a.h, a.w, a.sf = y.data_ptr(), (noise.data_ptr() if karr is None else None), B, h, w, int(sf)
         a.scale_factor, a.prec_encode, a.prec_decode, a.stream = float(scale_factor), parse_precision(prec_encode), F16, self._stream()
         with torch.cuda.device(self.device):
-            rc = self.lib.rs_sample_begin(self._h, C.byref(a), x.data_ptr())
-        self._chk(rc, "rs_sample_begin")
+            if karr is None:
+                rc = self.lib.rs_sample_begin(self._h, C.byref(a), x.data_ptr())
+            else:
+                rc = self.lib.rs_sample_begin_seeded(self._h, C.byref(a), x.data_ptr(), karr)
+        self._chk(rc, "rs_sample_begin" if karr is None else "rs_sample_begin_seeded")
         return x
 
-    def sample_step(self, x, y, t: Sequence[int], noise, tables: Dict[str, np.ndarray], sf: int, mask=None, prec=F16, pred_xstart=None):
+    def sample_step(self, x, y, t: Sequence[int], noise, tables: Dict[str, np.ndarray], sf: int, mask=None, prec=F16, pred_xstart=None, keys=None):
         """One p_sample of every image b at its own step index t[b] (indices into `tables`), x [B,Cz,hz,wz] updated IN PLACE
-        (contiguous fp32); noise [B,Cz,hz,wz] this step's draws (may be None when every t[b] is 0).  Returns x (rs_sample_step)."""
+        (contiguous fp32); noise [B,Cz,hz,wz] this step's draws (may be None when every t[b] is 0).  Returns x (rs_sample_step).
+        `keys` (one per image, see noise_fill) instead of `noise` (then None): image b uses draw steps - t[b] of its key, generated in the
+        kernel (rs_sample_step_seeded) - the same launches, no noise read."""
         if x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
             raise ValueError("sample_step updates x in place: it must be a contiguous float32 device tensor")
         y = self._f32c(y)
         B, _, h, w = y.shape
         if x.shape[0] != B or len(t) != B:
             raise ValueError(f"sample_step: x has {x.shape[0]} images, y {B}, t {len(t)}")
+        karr = self._keys(keys, noise, B, "sample_step") if keys is not None else None
         nt = self._f32c(noise) if noise is not None else None
         mk = self._f32c(mask) if mask is not None else None
         a = _lib.SampleArgs()
@@ -304,8 +343,8 @@ class Engine:
         ts = (C.c_int * B)(*[int(v) for v in t])
         s.t, s.B, s.prec, s.stream = ts, B, parse_precision(prec), self._stream()
         with torch.cuda.device(self.device):
-            rc = self.lib.rs_sample_step(self._h, C.byref(s))
-        self._chk(rc, "rs_sample_step")
+            rc = self.lib.rs_sample_step(self._h, C.byref(s)) if karr is None else self.lib.rs_sample_step_seeded(self._h, C.byref(s), karr)
+        self._chk(rc, "rs_sample_step" if karr is None else "rs_sample_step_seeded")
         return x
 
     def film_prewarm(self, timesteps: Sequence[int]):
@@ -334,21 +373,24 @@ class Engine:
         return out
 
     def sample(self, y, noise, tables: Dict[str, np.ndarray], sf: int, scale_factor: float, mask=None, prec_unet=F16, prec_encode=F16,
-               prec_decode=F16, return_aux=False):
-        """The whole p_sample_loop in one native call.  noise: [steps+1,B,Cz,hz,wz] fp32 in draw order."""
+               prec_decode=F16, return_aux=False, keys=None):
+        """The whole p_sample_loop in one native call.  noise: [steps+1,B,Cz,hz,wz] fp32 in draw order - or None with `keys` (one per
+        image, see noise_fill): draws 0 .. steps of each key, generated in the kernels that consume them (rs_sample_seeded)."""
         y = self._f32c(y)
-        noise = self._f32c(noise)
         B, _, h, w = y.shape
         steps = int(len(tables["coef1"]))
         f = 2 ** (int(self.cfg.ae.n_levels) - 1)
         hz, wz, cz = h * sf // f, w * sf // f, int(self.cfg.ae.embed_dim)
-        assert tuple(noise.shape) == (steps + 1, B, cz, hz, wz), (tuple(noise.shape), (steps + 1, B, cz, hz, wz))
+        karr = self._keys(keys, noise, B, "sample") if keys is not None else None
+        if karr is None:
+            noise = self._f32c(noise)
+            assert tuple(noise.shape) == (steps + 1, B, cz, hz, wz), (tuple(noise.shape), (steps + 1, B, cz, hz, wz))
         out = torch.empty(B, int(self.cfg.ae.out_ch), h * sf, w * sf, device=y.device, dtype=torch.float32)
         a = _lib.SampleArgs()
         mk = self._f32c(mask) if mask is not None else None
         z_out = torch.empty(B, cz, hz, wz, device=y.device, dtype=torch.float32) if return_aux else None
         idx = torch.empty(B * hz * wz, device=y.device, dtype=torch.int32) if return_aux else None
-        a.y, a.noise, a.out = y.data_ptr(), noise.data_ptr(), out.data_ptr()
+        a.y, a.noise, a.out = y.data_ptr(), (noise.data_ptr() if karr is None else None), out.data_ptr()
         a.mask = mk.data_ptr() if mk is not None else None
         a.z_out = z_out.data_ptr() if z_out is not None else None
         a.idx_out = idx.data_ptr() if idx is not None else None
@@ -366,8 +408,8 @@ class Engine:
         a.prec_encode, a.prec_decode = parse_precision(prec_encode), parse_precision(prec_decode)
         a.stream = self._stream()
         with torch.cuda.device(self.device):
-            rc = self.lib.rs_sample(self._h, C.byref(a))
-        self._chk(rc, "rs_sample")
+            rc = self.lib.rs_sample(self._h, C.byref(a)) if karr is None else self.lib.rs_sample_seeded(self._h, C.byref(a), karr)
+        self._chk(rc, "rs_sample" if karr is None else "rs_sample_seeded")
         if return_aux:
             return out, {"z_final": z_out, "indices": idx}
         return out

@@ -284,10 +284,26 @@ class ResShiftDiffusion:
         sample = self._axpbypcz(out["mean"], None, noise, 1.0, 0.0, sigma, eng)
         return {"sample": sample, "pred_xstart": out["pred_xstart"], "mean": out["mean"]}
 
+    @staticmethod
+    def _seed_keys(seeds, B: int, noise, step_noises, noise_repeat):
+        """seeds= of p_sample_loop -> [(seed, stream)] per image"""
+        if noise is not None or step_noises is not None or noise_repeat:
+            raise ValueError("seeds= names every draw: it excludes noise, step_noises and noise_repeat")
+        keys = [tuple(int(v) for v in k) if isinstance(k, (tuple, list)) else (int(k), 0) for k in seeds]
+        if len(keys) != B:
+            raise ValueError(f"seeds: {B} images but {len(keys)} seeds")
+        return keys
+
     def p_sample_loop_progressive(self, y, model, first_stage_model=None, noise=None, noise_repeat=False, clip_denoised=True,
-                                  denoised_fn=None, model_kwargs=None, device=None, progress=False, step_noises=None):
-        """gaussian_diffusion.py:421-472: generator of per-step dicts {"sample","pred_xstart","mean"}."""
+                                  denoised_fn=None, model_kwargs=None, device=None, progress=False, step_noises=None, seeds=None):
+        """gaussian_diffusion.py:421-472: generator of per-step dicts {"sample","pred_xstart","mean"}.  `seeds`: see p_sample_loop (every
+        draw is the seeded definition's, one rs_noise_fill call per draw)."""
         z_y = self.encode_first_stage(y, first_stage_model, up_sample=True)
+        if seeds is not None:
+            keys = self._seed_keys(seeds, z_y.shape[0], noise, step_noises, noise_repeat)
+            eng = model.engine() if isinstance(model, UNetModelSwin) else self._any_engine()
+            fill = lambda k: eng.noise_fill(keys, [k] * len(keys), tuple(z_y.shape[1:]))
+            noise, step_noises = fill(0), [fill(k) for k in range(1, self.num_timesteps + 1)]
         if noise is None:
             noise = torch.randn_like(z_y)
         if noise_repeat:
@@ -303,8 +319,11 @@ class ResShiftDiffusion:
 
     def p_sample_loop(self, y, model, first_stage_model=None, consistencydecoder=None, noise=None, noise_repeat=False,
                       clip_denoised=True, denoised_fn=None, model_kwargs=None, device=None, progress=False, step_noises=None,
-                      return_aux=False):
-        """gaussian_diffusion.py:367-419.  Fast path: one native `rs_sample` call for the whole loop."""
+                      return_aux=False, seeds=None):
+        """gaussian_diffusion.py:367-419.  Fast path: one native `rs_sample` call for the whole loop.
+        `seeds`: one per image - an int (stream 0) or a (seed, stream) pair.  Image b then gets draws 0 .. steps of its key
+        whatever the batch, the slot or the process: no torch.randn, no noise tensor (fast path: `rs_sample_seeded`, the normals are made
+        in the kernels that consume them).  Mutually exclusive with noise / step_noises / noise_repeat."""
         fused_ok = (isinstance(model, UNetModelSwin) and isinstance(first_stage_model, VQModelTorch) and consistencydecoder is None
                     and denoised_fn is None and not clip_denoised)
         if not fused_ok:
@@ -312,11 +331,20 @@ class ResShiftDiffusion:
             for sample in self.p_sample_loop_progressive(y, model, first_stage_model=first_stage_model, noise=noise,
                                                          noise_repeat=noise_repeat, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                                          model_kwargs=model_kwargs, device=device, progress=progress,
-                                                         step_noises=step_noises):
+                                                         step_noises=step_noises, seeds=seeds):
                 final = sample["sample"]
             return self.decode_first_stage(final, first_stage_model=first_stage_model, consistencydecoder=consistencydecoder)
         eng = self._fused_engine(model, first_stage_model)
         B, _, h, w = y.shape
+        if seeds is not None:
+            mask = (model_kwargs or {}).get("mask", None)
+            lq = (model_kwargs or {}).get("lq", None)
+            if lq is not None and lq.data_ptr() != y.data_ptr() and not torch.equal(lq, y):
+                raise NotImplementedError("fused loop conditions the UNet on y itself (sampler.py:140-148)")
+            return eng.sample(y, None, self.step_tables(), sf=self.sf, scale_factor=self.scale_factor, mask=mask,
+                              prec_unet=self._unet_precisions(), prec_encode=self._prec(self.precision_encode),
+                              prec_decode=self._prec(self.precision_decode), return_aux=return_aux,
+                              keys=self._seed_keys(seeds, B, noise, step_noises, noise_repeat))
         f = 2 ** (int(eng.cfg.ae.n_levels) - 1)
         zshape = (B, int(eng.cfg.ae.embed_dim), h * self.sf // f, w * self.sf // f)
         T = self.num_timesteps

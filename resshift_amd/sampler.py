@@ -143,8 +143,9 @@ class BaseSampler:
 
 
 class ResShiftSampler(BaseSampler):
-    def sample_func(self, y0, noise_repeat=False, mask=False, noise=None, step_noises=None):
-        """y0: [n,c,h,w] in [-1,1]; returns [n,c,h*sf,w*sf] in [-1,1] (sampler.py:119-165)."""
+    def sample_func(self, y0, noise_repeat=False, mask=False, noise=None, step_noises=None, seeds=None):
+        """y0: [n,c,h,w] in [-1,1]; returns [n,c,h*sf,w*sf] in [-1,1] (sampler.py:119-165).  `seeds`: one int or (seed, stream) pair per
+        image - per-request noise generated inside the engine (p_sample_loop's seeds=) instead of torch.randn / tensors."""
         if noise_repeat:
             self.setup_seed()
         if mask is False:
@@ -170,19 +171,37 @@ class ResShiftSampler(BaseSampler):
         results = self.base_diffusion.p_sample_loop(y=y0, model=self.model, first_stage_model=self.autoencoder, noise=noise,
                                                     noise_repeat=noise_repeat, clip_denoised=(self.autoencoder is None),
                                                     denoised_fn=None, model_kwargs=model_kwargs, progress=False,
-                                                    step_noises=step_noises)
+                                                    step_noises=step_noises, **({"seeds": seeds} if seeds is not None else {}))
         if flag_pad:
             results = results[:, :, : ori_h * self.sf, : ori_w * self.sf]
         return results.clamp_(-1.0, 1.0)
 
-    def sample_tiled(self, im_lq, mask=None, noise_repeat=False, tile_noises=None):
+    def image_seed(self, index: int) -> int:
+        """The seed `inference(seeded=True)` gives the image at position `index` of the sorted listing of the WHOLE input (not of a rank's
+        share): continuous.request_seed(self.seed, index) = (self.seed * 2^32 + index) mod 2^64."""
+        from .continuous import request_seed
+
+        return request_seed(self.seed, index)
+
+    def sample_tiled(self, im_lq, mask=None, noise_repeat=False, tile_noises=None, seed=None):
         """sampler.py:176-216 (`_process_per_image`): inputs larger than `chop_size` are cut into overlapping
         `chop_size` tiles (stride `chop_stride`, `chop_bs` tiles per sampler call), sampled independently and
         overlap-averaged on the GPU; smaller inputs go straight to `sample_func`.  Returns [-1,1] like sample_func.
-        `tile_noises[k] = (noise, step_noises)` injects the draws of the k-th sampler call (parity runs)."""
+        `tile_noises[k] = (noise, step_noises)` injects the draws of the k-th sampler call (parity runs).
+        `seed` (an int, or one per image of the batch): tile j of an image (index in tiling.extract_starts order) draws its noise from
+        key (seed, stream = j) - what tilepool.TilePool(seeded=True) gives the same image; an untiled image is its tile 0."""
         from .tiling import TileSplitter
 
+        B0 = im_lq.shape[0]
+        if seed is not None:
+            if tile_noises is not None or noise_repeat:
+                raise ValueError("seed= names every draw: it excludes tile_noises and noise_repeat")
+            seeds = [int(v) for v in seed] if isinstance(seed, (list, tuple)) else [int(seed)] * B0
+            if len(seeds) != B0:
+                raise ValueError(f"seed: {B0} images but {len(seeds)} seeds")
         if not (im_lq.shape[2] > self.chop_size or im_lq.shape[3] > self.chop_size):
+            if seed is not None:
+                return self.sample_func(im_lq, mask=mask, seeds=[(sd, 0) for sd in seeds])
             nz = tile_noises[0] if tile_noises else (None, None)
             return self.sample_func(im_lq, noise_repeat=noise_repeat, mask=mask, noise=nz[0], step_noises=nz[1])
         x = torch.cat([im_lq, mask], dim=1) if mask is not None else im_lq
@@ -192,8 +211,12 @@ class ResShiftSampler(BaseSampler):
                 pch, mask_pch = pch[:, :-1].contiguous(), pch[:, -1:].contiguous()
             else:
                 mask_pch = None
-            nz = tile_noises[k] if tile_noises else (None, None)
-            out = self.sample_func(pch, noise_repeat=noise_repeat, mask=mask_pch, noise=nz[0], step_noises=nz[1])
+            if seed is not None:   # rows of this call: tile k * chop_bs + kk, image b at row kk * B0 + b (TileSplitter.__next__)
+                keys = [(seeds[b], k * self.chop_bs + kk) for kk in range(len(index_infos)) for b in range(B0)]
+                out = self.sample_func(pch, mask=mask_pch, seeds=keys)
+            else:
+                nz = tile_noises[k] if tile_noises else (None, None)
+                out = self.sample_func(pch, noise_repeat=noise_repeat, mask=mask_pch, noise=nz[0], step_noises=nz[1])
             splitter.update(out, index_infos)
         return splitter.gather()
 
@@ -208,14 +231,19 @@ class ResShiftSampler(BaseSampler):
 
     POOL_LOOKAHEAD = 128   # inference(pool=True) reads files ahead until this many tiles wait for a slot
 
-    def inference(self, in_path, out_path, mask_path=None, mask_back=True, bs=1, noise_repeat=False, pool=False):
+    def inference(self, in_path, out_path, mask_path=None, mask_back=True, bs=1, noise_repeat=False, pool=False, seeded=False):
         """sampler.py:167-308: batches of `bs` images are sharded over the ranks exactly like sampler.py:273-277; every
         rank writes its own PNGs.  uint8 -> [-1,1] (datapipe/datasets.py:59-63), the inpainting blend (sampler.py:218-222)
         and the final clamp / round to uint8 (utils/util_image.py:245-269) run on the device (rs_u8_to_input /
         rs_output_to_u8): only uint8 pixels cross PCIe.  Inputs larger than `chop_size` take the tiled path.
         `pool=True`: the files of this rank's share (same sharding) are read one by one - their sizes may differ - and submitted to ONE
         `tilepool.TilePool`, whose batches hold tiles of several images; each PNG is written when its image completes.  Files are
-        submitted ahead while fewer than POOL_LOOKAHEAD tiles wait, then the pool steps."""
+        submitted ahead while fewer than POOL_LOOKAHEAD tiles wait, then the pool steps.
+        `seeded=True` (with and without `pool`): the image at position i of the sorted listing of the whole input gets the seed
+        `image_seed(i)`, its tile j the stream j - the noise of a file does not depend on the number of ranks, on `bs` or
+        on `pool`, so neither do the PNGs beyond the engine's own batch-size sensitivity.  Excludes `noise_repeat`."""
+        if seeded and noise_repeat:
+            raise ValueError("seeded=True names every draw by (seed, stream): it excludes noise_repeat")
         in_path, out_path = Path(in_path), Path(out_path)
         if self.rank == 0:
             out_path.mkdir(parents=True, exist_ok=True)
@@ -232,13 +260,14 @@ class ResShiftSampler(BaseSampler):
 
         micro = math.ceil(bs / self.num_gpus)   # sampler.py:274-277: the slice width comes from bs, also on the last, partial batch
         if pool:
-            self._inference_pool(files, out_path, mask_path, mask_back, bs, micro, single, noise_repeat)
+            self._inference_pool(files, out_path, mask_path, mask_back, bs, micro, single, noise_repeat, seeded)
             sharding.barrier()
             self.write_log(f"Processing done, enjoy the results in {out_path}")
             return
         for b0 in range(0, len(files), bs):
             batch = files[b0:b0 + bs]
             mine = batch[self.rank * micro:(self.rank + 1) * micro]
+            first = b0 + self.rank * micro   # position of mine[0] in the whole listing
             if mine:
                 lq = self.engine.u8_to_input(torch.stack([self._read_image_u8(p) for p in mine]).to(self.device))
                 mask = None
@@ -247,7 +276,10 @@ class ResShiftSampler(BaseSampler):
                     # mask_path as the mask file itself (sampler.py:296-297)
                     mpaths = [Path(mask_path)] if single else [Path(mask_path) / p.name for p in mine]
                     mask = self.engine.u8_to_input(torch.stack([self._read_image_u8(m, gray=True) for m in mpaths]).to(self.device))
-                sr = self.sample_tiled(lq, mask=mask, noise_repeat=noise_repeat)
+                if seeded:
+                    sr = self.sample_tiled(lq, mask=mask, seed=[self.image_seed(first + j) for j in range(len(mine))])
+                else:
+                    sr = self.sample_tiled(lq, mask=mask, noise_repeat=noise_repeat)
                 blend = mask is not None and mask_back
                 out_u8 = self.engine.output_to_u8(sr, lq=lq if blend else None, mask=mask if blend else None).cpu().numpy()
                 for p, im in zip(mine, out_u8):
@@ -255,14 +287,14 @@ class ResShiftSampler(BaseSampler):
         sharding.barrier()
         self.write_log(f"Processing done, enjoy the results in {out_path}")
 
-    def _inference_pool(self, files, out_path, mask_path, mask_back, bs, micro, single, noise_repeat):
+    def _inference_pool(self, files, out_path, mask_path, mask_back, bs, micro, single, noise_repeat, seeded=False):
         from PIL import Image
 
         from .tilepool import TilePool
 
         if noise_repeat:
             raise NotImplementedError("noise_repeat shares one draw across a batch; the tile pool has no fixed batch")
-        tp = TilePool(self)
+        tp = TilePool(self, seeded=seeded)
         kept = {}   # image id -> (file, lq, mask) until its PNG is written
 
         def write(done):
@@ -273,13 +305,15 @@ class ResShiftSampler(BaseSampler):
                 Image.fromarray(im if im.shape[2] != 1 else im[:, :, 0]).save(out_path / f"{p.stem}.png")
 
         for b0 in range(0, len(files), bs):
-            for p in files[b0:b0 + bs][self.rank * micro:(self.rank + 1) * micro]:
+            for j, p in enumerate(files[b0:b0 + bs][self.rank * micro:(self.rank + 1) * micro]):
                 lq = self.engine.u8_to_input(self._read_image_u8(p).unsqueeze(0).to(self.device))
                 mask = None
                 if mask_path is not None:
                     mp = Path(mask_path) if single else Path(mask_path) / p.name
                     mask = self.engine.u8_to_input(self._read_image_u8(mp, gray=True).unsqueeze(0).to(self.device))
-                kept[tp.submit(lq, mask=mask)] = (p, lq, mask)
+                # (position of this file in the whole listing: b0 + rank * micro + j)
+                rid = tp.submit(lq, mask=mask, seed=self.image_seed(b0 + self.rank * micro + j)) if seeded else tp.submit(lq, mask=mask)
+                kept[rid] = (p, lq, mask)
                 while tp.waiting_tiles() >= self.POOL_LOOKAHEAD:
                     write(tp.step())
         while tp.pending():

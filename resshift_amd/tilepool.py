@@ -19,9 +19,14 @@ shape and nothing in the network mixes batch entries, so `TilePool` pools the ti
     of one divided by one) and returned.
 
 Per-tile arithmetic is the engine's per-image arithmetic at that batch size: an image whose tiles make up one batch comes out bit for
-bit as `sample_tiled` with `chop_bs` = that batch.  The restrictions of `ContinuousSampler` carry over: no `noise_repeat`, one UNet
+bit as `sample_tiled` with `chop_bs` = that batch.  The restrictions of `ContinuousSampler` carry over: no `noise_repeat` (it is defined
+by a fixed batch; unsupported with tensors and with seeds alike), one UNet
 precision for every step, latent-space models.  Out of scope: images of different sizes inside one UNet batch, one pool across ranks,
 a tile weighting other than the reference's uniform average.
+
+`seeded=True`: `submit(image, seed=...)` names the image; tile j (index in `tiling.extract_starts` order, the order of
+`tile_windows`) draws its noise from key (seed, stream = j) inside the engine's kernels.  No draws are made or stored, and an image's
+tiles get the same noise whatever else is pending, whichever pool or rank serves them, and in `ResShiftSampler.sample_tiled(seed=)`.
 """
 from __future__ import annotations
 
@@ -32,7 +37,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
-from .continuous import ContinuousSampler, check_sampler
+from .continuous import ContinuousSampler, check_sampler, request_seed
 from .tiling import extract_starts
 
 HEADLINE_PIXELS = 32 * 64 * 64   # LR pixels of the benchmark's batch (32 images of 64 x 64): what `max_batch=None` fills a class up to
@@ -65,10 +70,11 @@ class _Class:
 
 
 class TilePool:
-    def __init__(self, sampler, max_batch: Optional[int] = None, keep_log: bool = False):
+    def __init__(self, sampler, max_batch: Optional[int] = None, keep_log: bool = False, seeded: bool = False):
         """`max_batch`: most tiles of one class in flight.  None: clamp(32 * 64*64 // (Hp * Wp), 1, 32) per class - the LR pixel count of
         the benchmark's batch; an explicit value holds for every class, up to RS_MAX_ROWS.  `keep_log`: record in `self.batches`, per
-        engine step, the (image id, tile index) of every row the step held."""
+        engine step, the (image id, tile index) of every row the step held.  `seeded`: images carry a seed instead of noise tensors
+        (module docstring)."""
         check_sampler(sampler, max_batch, who="TilePool")
         self.sampler, self.max_batch = sampler, (int(max_batch) if max_batch is not None else None)
         d = sampler.base_diffusion
@@ -84,6 +90,7 @@ class TilePool:
         self._tiles: Dict[int, tuple] = {}   # tile sequence number -> (image, (h0, w0, th, tw), class key, draws [steps+1,Cz,hz,wz])
         self._next_image = self._next_tile = 0
         self.keep_log, self.batches = bool(keep_log), []
+        self.seeded = bool(seeded)
         self._tile_index: Dict[int, int] = {}
 
     # ------------------------------------------------------------------ requests
@@ -92,11 +99,16 @@ class TilePool:
             return self.max_batch
         return max(1, min(32, HEADLINE_PIXELS // (key[0] * key[1])))
 
-    def submit(self, lq, mask=None, tile_noises=None) -> int:
+    def submit(self, lq, mask=None, tile_noises=None, seed=None) -> int:
         """Queue one LR image lq [3,H,W] (or [1,3,H,W]) in [-1,1], with its mask [1,H,W] where the model takes one; returns its id.
         `tile_noises[k] = (noise [Cz,hz,wz], step_noises: steps tensors alike, in loop order)` injects tile k's draws (a leading batch
         axis of 1 is accepted); otherwise they are drawn now, tile by tile in index order - one torch.randn of [steps+1,Cz,hz,wz] per tile,
-        row 0 the prior noise, row k the draw of the k-th loop iteration - so a seeded run is reproducible."""
+        row 0 the prior noise, row k the draw of the k-th loop iteration - so a run under torch.manual_seed is reproducible.
+        Seeded mode: `seed` (default request_seed(sampler.seed, image id)) names the image, tile j uses stream j; tile_noises is rejected."""
+        if self.seeded and tile_noises is not None:
+            raise ValueError("a seeded TilePool generates its noise from seeds: tile_noises tensors are not accepted")
+        if not self.seeded and seed is not None:
+            raise ValueError("seed= needs TilePool(..., seeded=True)")
         if lq.dim() == 4:
             if lq.shape[0] != 1:
                 raise ValueError("TilePool.submit takes ONE image (sizes may differ between images): submit them one by one")
@@ -125,7 +137,10 @@ class TilePool:
             raise ValueError(f"tile_noises: this image has {len(wins)} tiles, got draws for {len(tile_noises)}")
         zs = tuple(self.engine.latent_shape(1, key[0], key[1], self.sf))[1:]
         draws = []
-        for k in range(len(wins)):
+        if self.seeded:
+            sd = int(seed if seed is not None else request_seed(getattr(self.sampler, "seed", 0), self._next_image)) % 2 ** 64
+            draws = [(sd, j) for j in range(len(wins))]
+        for k in range(len(wins) if not self.seeded else 0):
             if tile_noises is None:
                 draws.append(torch.randn((self.steps + 1,) + zs, device=self.device, dtype=torch.float32))
             else:
@@ -136,7 +151,7 @@ class TilePool:
         im = _Image(self._next_image, src, len(wins))
         self._next_image += 1
         if key not in self._classes:
-            self._classes[key] = _Class(ContinuousSampler(self.sampler, max_batch=self.class_max_batch(key)))
+            self._classes[key] = _Class(ContinuousSampler(self.sampler, max_batch=self.class_max_batch(key), seeded=self.seeded))
         for k, win in enumerate(wins):
             self._tiles[self._next_tile] = (im, win, key, draws[k])
             self._tile_index[self._next_tile] = k

@@ -7,6 +7,14 @@
                   arrived and the previous batch is done).
 
     python scripts/continuous_bench.py [--reps 10] [--requests 96]
+
+`--seeded` measures instead the seeded pool (per-request Philox noise generated inside the step's kernel) against the tensor
+pool in ONE process, alternated round by round: (d) the pool's step at B = 32 with mixed step indices - tensor: the per-step gather of
+each slot's draw from the [B, steps+1, ...] pool tensor + rs_sample_step; seeded: rs_sample_step_seeded alone - and (e) saturated img/s
+of `ContinuousSampler(seeded=...)` over 4 pool-loads.  Medians with the min / max of the rounds (the spread).  `--out FILE` also writes
+the JSON to FILE.
+
+    python scripts/continuous_bench.py --seeded [--reps 10] [--out profiles/continuous_seeded.json]
 """
 from __future__ import annotations
 
@@ -36,10 +44,68 @@ def sync_time(fn):
     return time.perf_counter() - t0, r
 
 
+def spread(v):
+    return {"median": round(float(np.median(v)), 3), "min": round(float(np.min(v)), 3), "max": round(float(np.max(v)), 3), "rounds": len(v)}
+
+
+def seeded_vs_tensor(args, smp, y, dev):
+    """(d) + (e) of the module docstring; returns the result dict"""
+    d, eng = smp.base_diffusion, smp.engine
+    tables, T, sf = d.step_tables(), d.num_timesteps, d.sf
+    prec = d._unet_precisions()[0]
+    g = torch.Generator().manual_seed(5)
+    zs = eng.latent_shape(B, LR, LR, sf)
+    x0 = torch.randn(zs, generator=g).to(dev)
+    pool_n = torch.randn((B, T + 1) + tuple(zs[1:]), generator=g).to(dev)   # the tensor pool's _N
+    keys = [(1000 + b, 0) for b in range(B)]
+    ts = [b % T for b in range(B)]
+    rows = torch.arange(B, device=dev)
+
+    def tensor_step(x):
+        k = torch.tensor([T - t for t in ts], device=dev, dtype=torch.long)   # as ContinuousSampler._step_batch
+        eng.sample_step(x, y, ts, pool_n[rows, k], tables, sf, prec=prec)
+
+    def seeded_step(x):
+        eng.sample_step(x, y, ts, None, tables, sf, prec=prec, keys=keys)
+
+    x = x0.clone()
+    for fn in (tensor_step, seeded_step):   # (arena growth, first launches)
+        fn(x)
+    t_ms, s_ms = [], []
+    for r in range(args.reps):
+        for fn, acc in ((tensor_step, t_ms), (seeded_step, s_ms))[:: 1 if r % 2 == 0 else -1]:
+            x.copy_(x0)
+            acc.append(1e3 * sync_time(lambda: fn(x))[0])
+    pools = {False: ContinuousSampler(smp, max_batch=B), True: ContinuousSampler(smp, max_batch=B, seeded=True)}
+    for cs in pools.values():   # (pool allocation, first calls)
+        cs.submit(y)
+        cs.drain()
+    rate = {False: [], True: []}
+    for r in range(max(3, args.reps // 2)):
+        for seeded in ((False, True) if r % 2 == 0 else (True, False)):
+            cs = pools[seeded]
+
+            def load():   # submit time counts: the tensor pool draws steps + 1 latents per image there
+                for _ in range(4):
+                    cs.submit(y)
+                cs.drain()
+
+            sec, _ = sync_time(load)
+            rate[seeded].append(4 * B / sec)
+    res = {"config": "realsr_swinunet_realesrgan256", "policy": "parity", "batch": B,
+           "step_ms_mixed_b32": {"tensor_gather_plus_step": spread(t_ms), "seeded_step": spread(s_ms)},
+           "saturated_img_s": {"tensor_pool": spread(rate[False]), "seeded_pool": spread(rate[True])}}
+    res["step_ms_mixed_b32"]["seeded_over_tensor"] = round(res["step_ms_mixed_b32"]["seeded_step"]["median"] / res["step_ms_mixed_b32"]["tensor_gather_plus_step"]["median"], 4)
+    res["saturated_img_s"]["seeded_over_tensor"] = round(res["saturated_img_s"]["seeded_pool"]["median"] / res["saturated_img_s"]["tensor_pool"]["median"], 4)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--requests", type=int, default=96)
+    ap.add_argument("--seeded", action="store_true", help="seeded pool vs tensor pool, alternated in one process (module docstring)")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
     dev = torch.device("cuda:0")
@@ -55,10 +121,17 @@ def main():
     prec = d._unet_precisions()[0]
     g = torch.Generator().manual_seed(5)
     y = (torch.rand(B, 3, LR, LR, generator=g) * 2 - 1).to(dev)
+    eng.film_prewarm([int(v) for v in tables["tmap"]])
+    if args.seeded:
+        line = json.dumps(seeded_vs_tensor(args, smp, y, dev))
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     zs = eng.latent_shape(B, LR, LR, sf)
     noise = torch.randn(zs, generator=g).to(dev)
     x0 = torch.randn(zs, generator=g).to(dev)
-    eng.film_prewarm([int(v) for v in tables["tmap"]])
 
     # (a) one step at B = 32: homogeneous vs mixed step indices, alternated
     t_h, t_m = [T // 2] * B, [b % T for b in range(B)]
@@ -129,8 +202,12 @@ def main():
                            "img_s": round(len(lat_c) / span_c, 2)},
             "full_batches_32": {"p50_ms": round(1e3 * float(np.percentile(lat_b, 50)), 1), "p95_ms": round(1e3 * float(np.percentile(lat_b, 95)), 1),
                                 "img_s": round(len(lat_b) / (last - arr[0]), 2)}}
-    print(json.dumps({"config": "realsr_swinunet_realesrgan256", "policy": "parity", "batch": B, "step_ms": step, "saturated": saturated,
-                      "staggered": stag}), flush=True)
+    line = json.dumps({"config": "realsr_swinunet_realesrgan256", "policy": "parity", "batch": B, "step_ms": step, "saturated": saturated,
+                       "staggered": stag})
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
 
 
 if __name__ == "__main__":
