@@ -228,6 +228,28 @@ int rs_tile_gather(const rs_tile_desc* desc, int n, int C_src, float* out_lq, fl
  * agree in count, H and W; distinct canvases must not alias.  -2: as rs_tile_gather, sf < 1, th*sf > Hp_out or tw*sf > Wp_out. */
 int rs_tile_scatter(const rs_tile_desc* desc, int n, int C, int sf, const float* tiles, int Hp_out, int Wp_out, void* stream);
 
+/* ---- feathered tile blending (opt-in; the uniform average above stays the default and keeps its bits) -------------
+ * Overlapping tiles are independent samples, so a uniform average steps by (A + B)/2 - A at every overlap edge.  Feathering weights a
+ * tile down towards its own edges, so that the blend crosses an overlap in a ramp.  For a tile whose HR window is nh x nw pixels
+ * (nh = th*sf, nw = tw*sf; for rs_tile_accumulate_weighted, whose arguments are HR pixels already, nh = th, nw = tw) and ramp widths
+ * Rh, Rw in HR pixels, the same for every tile of a call (the host passes (chop_size - chop_stride) * sf for both):
+ *     w1(p, n, R) = 1                                    if R == 0
+ *                 = min(1, (min(p, n-1-p) + 0.5) / R)    otherwise          (symmetric, in (0, 1], n < 2R ramps up to less than 1)
+ *     w(i, j)     = w1(i, nh, Rh) * w1(j, nw, Rw)
+ *     acc  [.., y0+i, x0+j] += w(i, j) * tile[.., i, j]
+ *     count[    y0+i, x0+j] += w(i, j)                    (the count plane holds a weight SUM now)
+ * and the output is acc / count: rs_tile_finalize, unchanged.  Image borders need no special case: where one tile covers a pixel its
+ * weight cancels in the division.  In fp32: w1 = fminf(1, ((float)min(p, n-1-p) + 0.5f) * (1.0f / (float)R)), w = w1h * w1w rounded
+ * once, sum = fmaf(w, v, sum), count = count + w - the same expressions in both entry points, so rs_tile_scatter_weighted gives the
+ * bits of rs_tile_accumulate_weighted called tile by tile in index order (one writer per canvas element, no atomics), and R = 0 gives
+ * the bits of the unweighted calls.  tests/_feather_ref.py restates this in float64.
+ * -2 (with rs_last_error): Rh < 0 or Rw < 0; accumulate: a null pointer, B, C, th or tw < 1, a window that leaves the canvas;
+ * scatter: everything rs_tile_scatter rejects. */
+int rs_tile_accumulate_weighted(float* acc, float* count, const float* tile, int B, int C, int H, int W, int h0, int w0, int th, int tw,
+                                int Rh, int Rw, void* stream);
+int rs_tile_scatter_weighted(const rs_tile_desc* desc, int n, int C, int sf, const float* tiles, int Hp_out, int Wp_out, int Rh, int Rw,
+                             void* stream);
+
 /* uint8 pre / post processing on the device.
  * rs_u8_to_input:  interleaved uint8 [B,H,W,C] -> planar fp32 [B,C,H,W] in [-1,1]  ((v/255 - 0.5)/0.5; replaces
  *                  datapipe/datasets.py:59-63 ToTensor + Normalize on the host)

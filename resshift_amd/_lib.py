@@ -132,6 +132,8 @@ SIGNATURES = {
     "rs_window_copy": (_I, [_P, _P, _LL, _I, _I, _I, _I, _I, _I, _F, _P]),
     "rs_tile_gather": (_I, [C.POINTER(TileDesc), _I, _I, _P, _P, _I, _I, _P]),
     "rs_tile_scatter": (_I, [C.POINTER(TileDesc), _I, _I, _I, _P, _I, _I, _P]),
+    "rs_tile_accumulate_weighted": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
+    "rs_tile_scatter_weighted": (_I, [C.POINTER(TileDesc), _I, _I, _I, _P, _I, _I, _I, _I, _P]),
     "rs_u8_to_input": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rs_output_to_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rs_arena_bytes": (_SZ, [_P]),
@@ -256,10 +258,12 @@ def tile_gather(tiles, out_lq, out_mask=None):
                                 Hp, Wp, current_stream_ptr()), "rs_tile_gather")
 
 
-def tile_scatter(tiles, batch, sf):
+def tile_scatter(tiles, batch, sf, ramp=None):
     """rs_tile_scatter: `tiles` = [(acc [C,H*sf,W*sf], count [H*sf,W*sf], H, W, h0, w0, th, tw)] for the rows of `batch` [n,C,Hp_out,Wp_out]:
     adds each row's top-left (th*sf) x (tw*sf) crop into its canvas window and 1 into the count there - one launch, the bits of
-    rs_tile_accumulate called tile by tile in index order (tiles of one launch may overlap)."""
+    rs_tile_accumulate called tile by tile in index order (tiles of one launch may overlap).
+    `ramp` = (Rh, Rw) in HR pixels: rs_tile_scatter_weighted instead - feathered blending, the crop and the count weighted down towards
+    the tile's edges (include/resshift_hip.h), the bits of tile_accumulate_weighted tile by tile."""
     n = len(tiles)
     if not (batch.is_cuda and batch.dtype == torch.float32 and batch.is_contiguous() and batch.dim() == 4 and batch.shape[0] == n):
         raise ValueError(f"tile_scatter: the tiles must be one contiguous float32 device tensor [{n},C,Hp,Wp]")
@@ -269,7 +273,23 @@ def tile_scatter(tiles, batch, sf):
                 and tuple(acc.shape) == (Cc, H * sf, W * sf) and tuple(cnt.shape) == (H * sf, W * sf)):
             raise ValueError(f"tile_scatter: a canvas must be contiguous float32 [{Cc},H*sf,W*sf] with its count plane [H*sf,W*sf]")
     descs = _tile_descs([(None, acc.data_ptr(), cnt.data_ptr(), H, W, h0, w0, th, tw) for acc, cnt, H, W, h0, w0, th, tw in tiles])
-    check(load().rs_tile_scatter(descs, n, Cc, int(sf), batch.data_ptr(), int(batch.shape[2]), int(batch.shape[3]), current_stream_ptr()), "rs_tile_scatter")
+    if ramp is None:
+        check(load().rs_tile_scatter(descs, n, Cc, int(sf), batch.data_ptr(), int(batch.shape[2]), int(batch.shape[3]), current_stream_ptr()), "rs_tile_scatter")
+    else:
+        check(load().rs_tile_scatter_weighted(descs, n, Cc, int(sf), batch.data_ptr(), int(batch.shape[2]), int(batch.shape[3]), int(ramp[0]),
+                                              int(ramp[1]), current_stream_ptr()), "rs_tile_scatter_weighted")
+
+
+def tile_accumulate_weighted(acc, count, tile, h0, w0, ramp):
+    """rs_tile_accumulate_weighted: canvas acc [B,C,H,W] and its count plane [H,W] (HR pixels) += the feather-weighted `tile` [B,C,th,tw]
+    at (h0, w0); `ramp` = (Rh, Rw) in HR pixels.  Contiguous fp32 device tensors."""
+    B, Cc, H, W = acc.shape
+    th, tw = tile.shape[2:]
+    for t, shape in ((acc, (B, Cc, H, W)), (count, (H, W)), (tile, (B, Cc, th, tw))):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError("tile_accumulate_weighted: acc [B,C,H,W], count [H,W] and tile [B,C,th,tw] must be contiguous float32 device tensors")
+    check(load().rs_tile_accumulate_weighted(acc.data_ptr(), count.data_ptr(), tile.data_ptr(), B, Cc, H, W, int(h0), int(w0), th, tw,
+                                             int(ramp[0]), int(ramp[1]), current_stream_ptr()), "rs_tile_accumulate_weighted")
 
 
 def tile_finalize(acc, count):

@@ -308,6 +308,45 @@ __global__ void tile_accumulate_kernel(float* acc, float* count, const float* ti
         if (bc == 0) count[(long long)(h0 + y) * W + w0 + x] += 1.0f;
     }
 }
+// ---- feathered blending (include/resshift_hip.h "feathered tile blending") ------------------------------
+// The weight and the update of BOTH weighted kernels below - ONE definition each, so that rs_tile_scatter_weighted is bit for bit
+// rs_tile_accumulate_weighted tile by tile whatever the compiler does with either loop (as axpbypcz_combine above).  Contraction is
+// switched off inside them: `count + w` after `w = wh * ww` would otherwise become fma(wh, ww, count) in one kernel and not in the other
+// (the __f*_rn intrinsics are plain operators here and contract like them).  The one fused operation is the fmaf that is spelled out.
+// inv_R = 1 / R, formed once per thread; R == 0 travels as 2, which makes every weight min(1, >= 1) = 1 exactly.
+__device__ __forceinline__ float feather_inv(int R) { return R > 0 ? 1.0f / (float)R : 2.0f; }
+__device__ __forceinline__ float feather_w1(int p, int n, float inv_R) {
+#pragma clang fp contract(off)
+    return fminf(1.f, ((float)min(p, n - 1 - p) + 0.5f) * inv_R);   // (an integer below 2^24 plus a half is exact)
+}
+__device__ __forceinline__ float feather_w2(float wh, float ww) {
+#pragma clang fp contract(off)
+    return wh * ww;
+}
+__device__ __forceinline__ void feather_update(float w, float v, float& sum, float& cnt) {
+#pragma clang fp contract(off)
+    sum = fmaf(w, v, sum);
+    cnt = cnt + w;
+}
+// acc[b,c,h0+y,w0+x] += w(y, x) tile[b,c,y,x];  count[h0+y,w0+x] += w(y, x), w the feather weight of the th x tw tile
+__global__ void tile_accumulate_weighted_kernel(float* acc, float* count, const float* tile, int B, int C, int H, int W, int h0, int w0,
+                                                int th, int tw, int Rh, int Rw) {
+    const long long n = (long long)B * C * th * tw;
+    const float ih = feather_inv(Rh), iw = feather_inv(Rw);
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (long long)gridDim.x * blockDim.x) {
+        const int x = (int)(g % tw);
+        long long t = g / tw;
+        const int y = (int)(t % th);
+        const long long bc = t / th;
+        const float w = feather_w2(feather_w1(y, th, ih), feather_w1(x, tw, iw));
+        float* pa = acc + (bc * H + h0 + y) * W + w0 + x;
+        float* pc = count + (long long)(h0 + y) * W + w0 + x;
+        float s = *pa, cv = bc == 0 ? *pc : 0.f;
+        feather_update(w, tile[g], s, cv);
+        *pa = s;
+        if (bc == 0) *pc = cv;
+    }
+}
 __global__ void tile_finalize_kernel(float* acc, const float* count, long long BC, long long HW) {
     const long long n = BC * HW;
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (long long)gridDim.x * blockDim.x)
@@ -382,6 +421,47 @@ __global__ __launch_bounds__(256) void tile_scatter_kernel(TileDescs ds, int n, 
             if (!tile_covers(ds.d[j], acc, sf, Y, X)) continue;
             v += *(const vec*)(tiles + (((long long)j * C + c) * Hpo + (Y - ds.d[j].h0 * sf)) * Wpo + (X - ds.d[j].w0 * sf));
             cv += 1.0f;
+        }
+        *(vec*)pa = v;
+        if (c == 0) *(vec*)pc = cv;
+    }
+}
+// The same walk with feather weights: acc_k += w tiles[k], count_k += w, w = feather_w1(i, th sf, 1 / Rh) feather_w1(j, tw sf, 1 / Rw) at
+// (i, j) of tile k's window - computed from the indices, no table, no load.  The four elements of a group share their covering tiles
+// (as above) and a tile's row weight, not its column weights.  Ownership, order and the one-writer rule are tile_scatter_kernel's, the
+// arithmetic is tile_accumulate_weighted_kernel's (feather_update): n successive weighted accumulate launches in index order.
+template <int V>
+__global__ __launch_bounds__(256) void tile_scatter_weighted_kernel(TileDescs ds, int n, int C, int sf, const float* tiles, int Hpo, int Wpo,
+                                                                    int Rh, int Rw) {
+    typedef float vec __attribute__((ext_vector_type(V)));
+    const int k = blockIdx.y;
+    float* acc = ds.d[k].acc;
+    float* count = ds.d[k].count;
+    const int Hc = ds.d[k].H * sf, Wc = ds.d[k].W * sf, y0 = ds.d[k].h0 * sf, x0 = ds.d[k].w0 * sf;
+    const int hh = ds.d[k].th * sf, wv = ds.d[k].tw * sf / V, total = C * hh * wv;
+    const float ih = feather_inv(Rh), iw = feather_inv(Rw);
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < total; g += gridDim.x * blockDim.x) {
+        const int r = g / wv;
+        const int X = x0 + (g % wv) * V, Y = y0 + r % hh, c = r / hh;
+        bool own = true;
+        for (int j = 0; j < k && own; ++j) own = !tile_covers(ds.d[j], acc, sf, Y, X);
+        if (!own) continue;
+        float* pa = acc + ((long long)c * Hc + Y) * Wc + X;
+        float* pc = count + (long long)Y * Wc + X;
+        vec v = *(const vec*)pa;
+        vec cv = c == 0 ? *(const vec*)pc : (vec)(0.0f);
+        for (int j = k; j < n; ++j) {
+            if (!tile_covers(ds.d[j], acc, sf, Y, X)) continue;
+            const int i = Y - ds.d[j].h0 * sf, jx = X - ds.d[j].w0 * sf, nh = ds.d[j].th * sf, nw = ds.d[j].tw * sf;
+            const vec t = *(const vec*)(tiles + (((long long)j * C + c) * Hpo + i) * Wpo + jx);
+            const float wh = feather_w1(i, nh, ih);
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                float s = v[e], cnt = cv[e];
+                feather_update(feather_w2(wh, feather_w1(jx + e, nw, iw)), t[e], s, cnt);
+                v[e] = s;
+                cv[e] = cnt;
+            }
         }
         *(vec*)pa = v;
         if (c == 0) *(vec*)pc = cv;
@@ -604,6 +684,18 @@ int rs_tile_accumulate(float* acc, float* count, const float* tile, int B, int C
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int rs_tile_accumulate_weighted(float* acc, float* count, const float* tile, int B, int C, int H, int W, int h0, int w0, int th, int tw,
+                                int Rh, int Rw, void* stream) {
+    if (!acc || !count || !tile) return rs_set_last_error("rs_tile_accumulate_weighted: null tensor (acc / count / tile)", -2);
+    if (B < 1 || C < 1 || th < 1 || tw < 1 || h0 < 0 || w0 < 0 || h0 + th > H || w0 + tw > W)
+        return rs_set_last_error("rs_tile_accumulate_weighted: the tile window leaves its canvas", -2);
+    if (Rh < 0 || Rw < 0) return rs_set_last_error("rs_tile_accumulate_weighted: ramp widths Rh and Rw must not be negative", -2);
+    const long long n = (long long)B * C * th * tw;
+    hipLaunchKernelGGL(tile_accumulate_weighted_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, acc, count, tile, B, C, H, W, h0, w0,
+                       th, tw, Rh, Rw);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int rs_window_copy(const float* in, float* out, long long planes, int H, int W, int h0, int w0, int Ho, int Wo, float scale, void* stream) {
     // (one reflection at most, as torch: the window may overhang the plane by less than its size)
     if (planes <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || h0 < 0 || w0 < 0 || h0 + Ho > 2 * H - 1 || w0 + Wo > 2 * W - 1 || h0 >= H || w0 >= W)
@@ -649,30 +741,49 @@ int rs_tile_gather(const rs_tile_desc* desc, int n, int C_src, float* out_lq, fl
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int rs_tile_scatter(const rs_tile_desc* desc, int n, int C, int sf, const float* tiles, int Hp_out, int Wp_out, void* stream) {
-    if (const char* e = tile_descs_error(desc, n)) return rs_set_last_error((std::string("rs_tile_scatter: ") + e).c_str(), -2);
-    if (C < 1 || sf < 1) return rs_set_last_error("rs_tile_scatter: C and sf must be positive", -2);
-    if (!tiles) return rs_set_last_error("rs_tile_scatter: null tensor (tiles)", -2);
+// rs_tile_scatter (weighted = false: Rh, Rw unused) and rs_tile_scatter_weighted: one set of checks, one grid, one choice of path
+static int tile_scatter_launch(const char* who, const rs_tile_desc* desc, int n, int C, int sf, const float* tiles, int Hp_out, int Wp_out,
+                               bool weighted, int Rh, int Rw, void* stream) {
+    const std::string pre = std::string(who) + ": ";
+    if (const char* e = tile_descs_error(desc, n)) return rs_set_last_error((pre + e).c_str(), -2);
+    if (C < 1 || sf < 1) return rs_set_last_error((pre + "C and sf must be positive").c_str(), -2);
+    if (weighted && (Rh < 0 || Rw < 0)) return rs_set_last_error((pre + "ramp widths Rh and Rw must not be negative").c_str(), -2);
+    if (!tiles) return rs_set_last_error((pre + "null tensor (tiles)").c_str(), -2);
     TileDescs ds{};
     bool v4 = (Wp_out % 4) == 0 && al16(tiles);
     long long per = 0;
     for (int k = 0; k < n; ++k) {
         const rs_tile_desc& d = desc[k];
-        if (!d.acc || !d.count) return rs_set_last_error("rs_tile_scatter: null tensor (desc.acc / desc.count)", -2);
+        if (!d.acc || !d.count) return rs_set_last_error((pre + "null tensor (desc.acc / desc.count)").c_str(), -2);
         if ((long long)d.th * sf > Hp_out || (long long)d.tw * sf > Wp_out)
-            return rs_set_last_error("rs_tile_scatter: a tile's window is larger than the tile tensor (th*sf > Hp_out or tw*sf > Wp_out)", -2);
+            return rs_set_last_error((pre + "a tile's window is larger than the tile tensor (th*sf > Hp_out or tw*sf > Wp_out)").c_str(), -2);
         for (int j = 0; j < k; ++j)
             if (desc[j].acc == d.acc && (desc[j].count != d.count || desc[j].H != d.H || desc[j].W != d.W))
-                return rs_set_last_error("rs_tile_scatter: descriptors of one canvas disagree about its count plane or size", -2);
+                return rs_set_last_error((pre + "descriptors of one canvas disagree about its count plane or size").c_str(), -2);
         v4 = v4 && ((d.w0 * sf) % 4) == 0 && ((d.tw * sf) % 4) == 0 && ((d.W * sf) % 4) == 0 && al16(d.acc) && al16(d.count);
         per = std::max(per, (long long)C * d.th * sf * d.tw * sf);
         ds.d[k] = d;
     }
-    if (per > 0x7fffffffLL) return rs_set_last_error("rs_tile_scatter: tile too large", -2);
+    if (per > 0x7fffffffLL) return rs_set_last_error((pre + "tile too large").c_str(), -2);
     const dim3 grid(nblk(v4 ? per / 4 : per, 256, 256), (unsigned)n);
-    if (v4) hipLaunchKernelGGL(tile_scatter_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, ds, n, C, sf, tiles, Hp_out, Wp_out);
-    else hipLaunchKernelGGL(tile_scatter_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, ds, n, C, sf, tiles, Hp_out, Wp_out);
+    const hipStream_t st = (hipStream_t)stream;
+    if (!weighted) {
+        if (v4) hipLaunchKernelGGL(tile_scatter_kernel<4>, grid, dim3(256), 0, st, ds, n, C, sf, tiles, Hp_out, Wp_out);
+        else hipLaunchKernelGGL(tile_scatter_kernel<1>, grid, dim3(256), 0, st, ds, n, C, sf, tiles, Hp_out, Wp_out);
+    } else {
+        if (v4) hipLaunchKernelGGL(tile_scatter_weighted_kernel<4>, grid, dim3(256), 0, st, ds, n, C, sf, tiles, Hp_out, Wp_out, Rh, Rw);
+        else hipLaunchKernelGGL(tile_scatter_weighted_kernel<1>, grid, dim3(256), 0, st, ds, n, C, sf, tiles, Hp_out, Wp_out, Rh, Rw);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int rs_tile_scatter(const rs_tile_desc* desc, int n, int C, int sf, const float* tiles, int Hp_out, int Wp_out, void* stream) {
+    return tile_scatter_launch("rs_tile_scatter", desc, n, C, sf, tiles, Hp_out, Wp_out, false, 0, 0, stream);
+}
+
+int rs_tile_scatter_weighted(const rs_tile_desc* desc, int n, int C, int sf, const float* tiles, int Hp_out, int Wp_out, int Rh, int Rw,
+                             void* stream) {
+    return tile_scatter_launch("rs_tile_scatter_weighted", desc, n, C, sf, tiles, Hp_out, Wp_out, true, Rh, Rw, stream);
 }
 
 int rs_tile_finalize(float* acc, const float* count, int B, int C, int H, int W, void* stream) {

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import sharding
+from . import sharding, tiling
 from .autoencoder import VQModelTorch
 from .config import ConfigNode, load_config
 from .gaussian_diffusion import create_gaussian_diffusion
@@ -67,14 +67,18 @@ class BaseSampler:
                 "split": ("split", "split", "split")}
 
     def __init__(self, configs, sf=4, use_amp=True, chop_size=128, chop_stride=128, chop_bs=1, padding_offset=16, seed=10000,
-                 state_dicts: Optional[Mapping[str, Mapping[str, torch.Tensor]]] = None, blob_cache=None, precision=None, pack="policy"):
+                 state_dicts: Optional[Mapping[str, Mapping[str, torch.Tensor]]] = None, blob_cache=None, precision=None, pack="policy",
+                 tile_blend="uniform"):
         """`state_dicts` ({"model": sd, "autoencoder": sd}) replaces checkpoint files, e.g. for synthetic-weight runs.
         `blob_cache`: file that keeps the packed device weights between runs (sharding.build_engine_with_broadcast).
         `precision`: "parity" | "fp16" | "fp32" | "split" (POLICIES).  Default: "parity" when `use_amp` (the reduced-precision path of the
         reference, sampler.py:185 - here the fastest policy that still reproduces the reference's CPU output to >= 60 dB: split-precision
         encoder + UNet, fp16 decoder; the reference's own autocast path, and "fp16" here, flip 2 - 7 % of the VQ codes), "fp32" otherwise.
         `pack`: "policy" - the engine packs, broadcasts and caches only the weight forms that policy needs (a later set_precision to a
-        form that was not packed fails loudly); "all" - every form (a process that switches policies)."""
+        form that was not packed fails loudly); "all" - every form (a process that switches policies).
+        `tile_blend`: how overlapping tiles of `sample_tiled` / `inference` (with and without `pool`) are blended: "uniform" - the
+        reference's average; "feather" - every tile weighted down towards its own edges across the overlap.  An image of
+        one tile is the same under both."""
         self.configs = configs if isinstance(configs, Mapping) else load_config(configs)
         self.sf = sf
         self.chop_size, self.chop_stride, self.chop_bs = chop_size, chop_stride, chop_bs
@@ -83,6 +87,8 @@ class BaseSampler:
         self.precision = precision if precision is not None else ("parity" if use_amp else "fp32")
         if self.precision not in self.POLICIES:
             raise ValueError(f"unknown precision policy {self.precision!r} (one of {sorted(self.POLICIES)})")
+        tiling.check_blend(tile_blend)
+        self.tile_blend = tile_blend
         if pack not in ("policy", "all"):
             raise ValueError("pack must be 'policy' or 'all'")
         self.pack = pack
@@ -205,7 +211,9 @@ class ResShiftSampler(BaseSampler):
             nz = tile_noises[0] if tile_noises else (None, None)
             return self.sample_func(im_lq, noise_repeat=noise_repeat, mask=mask, noise=nz[0], step_noises=nz[1])
         x = torch.cat([im_lq, mask], dim=1) if mask is not None else im_lq
-        splitter = TileSplitter(x, self.chop_size, stride=self.chop_stride, sf=self.sf, extra_bs=self.chop_bs)
+        blend = getattr(self, "tile_blend", "uniform")   # ("uniform" issues exactly the calls it always has)
+        splitter = TileSplitter(x, self.chop_size, stride=self.chop_stride, sf=self.sf, extra_bs=self.chop_bs,
+                                **({"blend": blend} if blend != "uniform" else {}))
         for k, (pch, index_infos) in enumerate(splitter):
             if mask is not None:
                 pch, mask_pch = pch[:, :-1].contiguous(), pch[:, -1:].contiguous()

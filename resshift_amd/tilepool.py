@@ -21,8 +21,11 @@ shape and nothing in the network mixes batch entries, so `TilePool` pools the ti
 Per-tile arithmetic is the engine's per-image arithmetic at that batch size: an image whose tiles make up one batch comes out bit for
 bit as `sample_tiled` with `chop_bs` = that batch.  The restrictions of `ContinuousSampler` carry over: no `noise_repeat` (it is defined
 by a fixed batch; unsupported with tensors and with seeds alike), one UNet
-precision for every step, latent-space models.  Out of scope: images of different sizes inside one UNet batch, one pool across ranks,
-a tile weighting other than the reference's uniform average.
+precision for every step, latent-space models.  Out of scope: images of different sizes inside one UNet batch, one pool across ranks.
+
+The blend is the sampler's `tile_blend`: "uniform" (default, the reference's average, the launches above) or "feather" (DESIGN.md 7d):
+tiles retire through ONE `rs_tile_scatter_weighted` launch - the bits of `rs_tile_accumulate_weighted` tile by tile, which is what
+`sample_tiled` issues under the same mode - and the count plane holds the weight sum that `rs_tile_finalize` divides by.
 
 `seeded=True`: `submit(image, seed=...)` names the image; tile j (index in `tiling.extract_starts` order, the order of
 `tile_windows`) draws its noise from key (seed, stream = j) inside the engine's kernels.  No draws are made or stored, and an image's
@@ -38,7 +41,7 @@ import torch
 
 from . import _lib
 from .continuous import ContinuousSampler, check_sampler, request_seed
-from .tiling import extract_starts
+from .tiling import check_blend, extract_starts, feather_ramp
 
 HEADLINE_PIXELS = 32 * 64 * 64   # LR pixels of the benchmark's batch (32 images of 64 x 64): what `max_batch=None` fills a class up to
 
@@ -91,6 +94,10 @@ class TilePool:
         self._next_image = self._next_tile = 0
         self.keep_log, self.batches = bool(keep_log), []
         self.seeded = bool(seeded)
+        # the blend is the sampler's (BaseSampler(tile_blend=)): "feather" retires tiles through rs_tile_scatter_weighted
+        self.blend = getattr(sampler, "tile_blend", "uniform")
+        check_blend(self.blend)
+        self.ramp = feather_ramp(self.chop_size, self.chop_stride, self.sf) if self.blend == "feather" else None
         self._tile_index: Dict[int, int] = {}
 
     # ------------------------------------------------------------------ requests
@@ -213,7 +220,10 @@ class TilePool:
             im.left -= 1
             if im.left == 0:
                 done.append(im)
-        _lib.tile_scatter(rows, batch, self.sf)
+        if self.ramp is None:
+            _lib.tile_scatter(rows, batch, self.sf)
+        else:
+            _lib.tile_scatter(rows, batch, self.sf, ramp=self.ramp)
         for im in done:
             out[im.id] = _lib.tile_finalize(im.acc, im.count)
             del self._images[im.id]

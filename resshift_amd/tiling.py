@@ -3,8 +3,8 @@ driven by sampler.py:186-208).
 
 Same iteration protocol as the reference class — `for patches, index_infos in splitter: splitter.update(out, index_infos)`,
 then `splitter.gather()` — but the accumulation / normalisation runs in the engine's tile kernels
-(`rs_tile_accumulate`, `rs_tile_finalize`) on NCHW fp32 device tensors.  Tiles are independent units, so `extra_bs` tiles
-travel through the sampler as one batch.
+(`rs_tile_accumulate`, `rs_tile_finalize`; `rs_tile_accumulate_weighted` for `blend="feather"`) on NCHW fp32 device
+tensors.  Tiles are independent units, so `extra_bs` tiles travel through the sampler as one batch.
 """
 from __future__ import annotations
 
@@ -29,9 +29,27 @@ def extract_starts(length: int, pch_size: int, stride: int) -> List[int]:
     return out
 
 
+BLENDS = ("uniform", "feather")
+
+
+def check_blend(blend) -> None:
+    if blend not in BLENDS:
+        raise ValueError(f"unknown tile blend {blend!r} (one of {sorted(BLENDS)})")
+
+
+def feather_ramp(pch_size: int, stride: int, sf: int) -> Tuple[int, int]:
+    """(Rh, Rw) of the feather blend in HR pixels: the overlap of two neighbouring tiles"""
+    r = (int(pch_size) - int(stride)) * int(sf)
+    return (r, r)
+
+
 class TileSplitter:
-    def __init__(self, im: torch.Tensor, pch_size: int, stride: int, sf: int = 1, extra_bs: int = 1):
+    def __init__(self, im: torch.Tensor, pch_size: int, stride: int, sf: int = 1, extra_bs: int = 1, blend: str = "uniform"):
+        """`blend`: "uniform" - the reference's overlap average (rs_tile_accumulate); "feather" - every tile weighted down towards its own
+        edges over the overlap width (pch_size - stride) * sf (rs_tile_accumulate_weighted, include/resshift_hip.h)."""
         assert stride <= pch_size
+        check_blend(blend)
+        self.blend, self.ramp = blend, feather_ramp(pch_size, stride, sf)
         self.lib = _lib.load()
         self.pch_size, self.stride, self.sf, self.extra_bs = pch_size, stride, sf, extra_bs
         bs, chn, height, width = im.shape
@@ -86,6 +104,9 @@ class TileSplitter:
             if (h1 - h0, w1 - w0) != (th, tw):   # the kernel reads the tile with row pitch tw
                 raise ValueError(f"tile result is {th}x{tw} but its canvas window is {h1 - h0}x{w1 - w0}")
             tile = pch_res[k * self.true_bs:(k + 1) * self.true_bs]
+            if self.blend == "feather":
+                _lib.tile_accumulate_weighted(self.im_res, self.pixel_count, tile, h0, w0, self.ramp)
+                continue
             rc = self.lib.rs_tile_accumulate(self.im_res.data_ptr(), self.pixel_count.data_ptr(), tile.data_ptr(), B, Cc, H, W, h0, w0,
                                              h1 - h0, w1 - w0, st)
             _lib.check(rc, "rs_tile_accumulate")

@@ -12,6 +12,13 @@ round, `spread` is (max - min) / median of that mode's rounds.  Host clock aroun
                      launches of the per-image path they replace (rs_window_copy crops; rs_tile_accumulate calls), enqueue included.
 
     python scripts/tilepool_bench.py [--reps 3]
+
+`--blend feather` measures the feathered blend instead, and prints ONE JSON line of its own: the mixed folder through
+`TilePool` with the sampler's tile_blend "uniform" and "feather" alternating round by round in one process (images/s, median round and
+spread as above), and the device-event time of ONE scatter launch of a full pool step's tiles, rs_tile_scatter against
+rs_tile_scatter_weighted with R = (chop_size - chop_stride) * sf, measured in alternating rounds likewise.
+
+    python scripts/tilepool_bench.py --blend feather [--reps 5]
 """
 from __future__ import annotations
 
@@ -61,9 +68,65 @@ def event_ms(fn, iters):
     return a.elapsed_time(b) / iters
 
 
+def blend_bench(smp, dev, plan, reps, result):
+    """uniform and feather, round by round: the mixed folder through the pool, and one scatter launch of 32 tiles of 64 x 64 (sf 4)"""
+    w = WORKLOADS["mixed_folder"]
+    g = torch.Generator().manual_seed(3)
+    ims = [(torch.rand(1, 3, h, wd, generator=g) * 2 - 1).to(dev) for h, wd in workload_sizes("mixed_folder")]
+    smp.chop_size, smp.chop_stride = w["chop_size"], w["chop_stride"]
+    blends = ("uniform", "feather")
+
+    def run_pool(blend):
+        smp.tile_blend = blend
+        tp = TilePool(smp)
+        assert tp.blend == blend
+        for y in ims:
+            tp.submit(y)
+        return tp.drain()
+
+    secs = {b: [] for b in blends}
+    for rnd in range(reps + 1):   # round 0 warms up
+        for b in blends:
+            dt, _ = sync_time(lambda: run_pool(b))
+            if rnd:
+                secs[b].append(dt)
+            print(f"[tilepool_bench] mixed_folder round {rnd} {b}: {dt:.3f} s", file=sys.stderr, flush=True)
+    smp.tile_blend = "uniform"
+    out = dict(plan)
+    for b, v in secs.items():
+        med = float(np.median(v))
+        out[b] = {"seconds": [round(x, 4) for x in v], "images_s": round(plan["images"] / med, 3), "tiles_s": round(plan["tiles"] / med, 2),
+                  "spread": round((max(v) - min(v)) / med, 4)}
+    out["feather_over_uniform"] = round(out["feather"]["images_s"] / out["uniform"]["images_s"], 4)
+    result["mixed_folder"] = out
+
+    n, sf, P = 32, 4, 64
+    ramp = ((w["chop_size"] - w["chop_stride"]) * sf,) * 2
+    wins = tile_windows(256, 256, 64, 48)
+    wins = (wins + wins)[:n]
+    batch = torch.rand(n, 3, P * sf, P * sf, device=dev)
+    acc, cnt = torch.zeros(3, 256 * sf, 256 * sf, device=dev), torch.zeros(256 * sf, 256 * sf, device=dev)
+    rows = [(acc, cnt, 256, 256, *wn) for wn in wins]
+    launches = {"uniform": lambda: _lib.tile_scatter(rows, batch, sf), "feather": lambda: _lib.tile_scatter(rows, batch, sf, ramp=ramp)}
+    ms = {b: [] for b in blends}
+    for rnd in range(reps + 1):
+        for b in blends:
+            t = event_ms(launches[b], 50)
+            if rnd:
+                ms[b].append(t)
+    result["scatter_launch"] = {"tiles_per_step": n, "tile": "64x64 LR, sf 4", "ramp": ramp[0], "iters_per_round": 50}
+    for b, v in ms.items():
+        med = float(np.median(v))
+        result["scatter_launch"][b] = {"ms": [round(x, 4) for x in v], "median_ms": round(med, 4), "spread": round((max(v) - min(v)) / med, 4)}
+    result["scatter_launch"]["feather_over_uniform"] = round(result["scatter_launch"]["feather"]["median_ms"]
+                                                             / result["scatter_launch"]["uniform"]["median_ms"], 4)
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--blend", choices=["feather"], default=None, help="measure the feathered blend against the uniform one instead")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
     plan = {}
@@ -82,6 +145,9 @@ def main():
                       autoencoder=ConfigNode(target="ldm.models.autoencoder.VQModelTorch", ckpt_path=None, params=aep))
     smp = ResShiftSampler(conf, sf=4, use_amp=True, padding_offset=64, seed=7, state_dicts=sds, precision="parity")
     result = {"config": "realsr_swinunet_realesrgan256", "policy": "parity", "reps": args.reps}
+    if args.blend:
+        print(json.dumps(blend_bench(smp, dev, plan["mixed_folder"], args.reps, result)), flush=True)
+        return
 
     for name, w in WORKLOADS.items():
         g = torch.Generator().manual_seed(3)
