@@ -250,6 +250,36 @@ int rs_tile_accumulate_weighted(float* acc, float* count, const float* tile, int
 int rs_tile_scatter_weighted(const rs_tile_desc* desc, int n, int C, int sf, const float* tiles, int Hp_out, int Wp_out, int Rh, int Rw,
                              void* stream);
 
+/* ---- colour correction against the low-quality input (opt-in) ----------------------------------------
+ * A sample drifts in tone and colour from its input, and every tile of a large image drifts on its own.  The remedy keeps the sample's
+ * detail and takes the low frequencies (wavelet) or the per-channel statistics (adain) from the up-sampled input: the
+ * `color_fix = wavelet | adain` switch of StableSR's and of later ResShift samplers.  Stateless, like the rs_tile_* family.
+ *   sr  [B,C,H*sf,W*sf]  fp32 NCHW in [-1,1]: the sample        lq  [B,C,H,W]  fp32 NCHW in [-1,1]: its input        sf >= 1
+ *   up(lq) = rs_bicubic's definition (F.interpolate(mode='bicubic', align_corners=False): A = -0.75, border-clamped taps, the expressions
+ *            of bicubic_up_kernel in csrc/elementwise.hip); up = identity at sf = 1.
+ * RS_COLOR_FIX_WAVELET:  out = clamp(sr - L(sr - up(lq)), -1, 1)
+ *   L = B_16 o B_8 o B_4 o B_2 o B_1, five a-trous levels, B_1 applied first (the order matters at the borders).  B_d is the separable
+ *   3x3 kernel [1/4 1/2 1/4]^T [1/4 1/2 1/4] with dilation d: a horizontal pass, then a vertical one, each
+ *       y[i] = 1/4 (x[clamp(i - d, 0, n-1)] + x[clamp(i + d, 0, n-1)]) + 1/2 x[i]
+ *   (replicate padding of the level's OWN input).  This is high(sr) + low(up(lq)) of StableSR's wavelet_reconstruction: the decomposition
+ *   is linear, replicate padding included, so it is written on the one difference image D = sr - up(lq).  Total reach: 31 pixels.
+ *   In fp32: y = fmaf(0.25f, a + c, 0.5f * b) for the taps (a, b, c) - one expression for every pixel, clamped index or not, so the value
+ *   of a pixel is a function of the image alone, not of the launch geometry.
+ * RS_COLOR_FIX_ADAIN:  per image and channel  out = clamp((sr - mean_sr) * std_lq / std_sr + mean_lq, -1, 1)
+ *   std = sqrt(unbiased variance + 1e-5) (a one-pixel plane has variance 0); the lq statistics are taken over the LR plane itself.  The
+ *   variance comes from centred values (per-chunk means, chunks merged by Chan's update in a fixed order) - never E[x^2] - mean^2 - and
+ *   without floating-point atomics: a plane's statistics do not depend on the batch it travels in.
+ * tests/_colorfix_ref.py restates both in float64.
+ * `work`: device scratch of rs_color_fix_work_bytes(...) bytes (0 for wavelet: work may be null), 4-byte aligned; `out` must not overlap
+ * `sr` or `lq` (workgroups read sr in their neighbours' tiles).  Argument errors are found before anything is launched, -2 with
+ * rs_last_error() starting "rs_color_fix: ": a null pointer, a dimension or sf below 1, an unknown mode, an overlapping out, a
+ * workspace that is too small. */
+#define RS_COLOR_FIX_WAVELET 1
+#define RS_COLOR_FIX_ADAIN 2
+size_t rs_color_fix_work_bytes(int B, int C, int H, int W, int sf, int mode);
+int rs_color_fix(const float* sr, const float* lq, float* out, int B, int C, int H, int W, int sf, int mode, void* work, size_t work_bytes,
+                 void* stream);
+
 /* uint8 pre / post processing on the device.
  * rs_u8_to_input:  interleaved uint8 [B,H,W,C] -> planar fp32 [B,C,H,W] in [-1,1]  ((v/255 - 0.5)/0.5; replaces
  *                  datapipe/datasets.py:59-63 ToTensor + Normalize on the host)

@@ -21,6 +21,9 @@ RS_PREC_SPLIT = 2
 RS_MAX_LEVELS = 8
 RS_MAX_STEPS = 64
 RS_MAX_ROWS = 64   # most images of one per-image call (include/resshift_hip.h)
+RS_COLOR_FIX_WAVELET = 1
+RS_COLOR_FIX_ADAIN = 2
+COLOR_FIX_MODES = {"wavelet": RS_COLOR_FIX_WAVELET, "adain": RS_COLOR_FIX_ADAIN}
 
 
 class UNetConfig(C.Structure):
@@ -134,6 +137,8 @@ SIGNATURES = {
     "rs_tile_scatter": (_I, [C.POINTER(TileDesc), _I, _I, _I, _P, _I, _I, _P]),
     "rs_tile_accumulate_weighted": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
     "rs_tile_scatter_weighted": (_I, [C.POINTER(TileDesc), _I, _I, _I, _P, _I, _I, _I, _I, _P]),
+    "rs_color_fix_work_bytes": (_SZ, [_I] * 6),
+    "rs_color_fix": (_I, [_P, _P, _P] + [_I] * 6 + [_P, _SZ, _P]),
     "rs_u8_to_input": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rs_output_to_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rs_arena_bytes": (_SZ, [_P]),
@@ -297,3 +302,26 @@ def tile_finalize(acc, count):
     Cc, H, W = acc.shape
     check(load().rs_tile_finalize(acc.data_ptr(), count.data_ptr(), 1, Cc, H, W, current_stream_ptr()), "rs_tile_finalize")
     return acc
+
+
+def color_fix(sr, lq, mode):
+    """rs_color_fix: the sample sr [B,C,H*sf,W*sf] corrected against its input lq [B,C,H,W] (contiguous fp32 device tensors in [-1,1]; sf
+    = the integer ratio of their sizes), `mode` "wavelet" | "adain" (include/resshift_hip.h).  Returns a new tensor; the scratch of the
+    adain statistics is a torch tensor of rs_color_fix_work_bytes bytes that lives until the call's stream work is done."""
+    if mode not in COLOR_FIX_MODES:
+        raise ValueError(f"unknown colour fix {mode!r} (one of {sorted(COLOR_FIX_MODES)})")
+    for t in (sr, lq):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4):
+            raise ValueError("color_fix: sr [B,C,H*sf,W*sf] and lq [B,C,H,W] must be contiguous float32 device tensors")
+    B, Cc, H, W = lq.shape
+    sf = sr.shape[2] // H
+    if sf < 1 or tuple(sr.shape) != (B, Cc, H * sf, W * sf):
+        raise ValueError(f"color_fix: sr {tuple(sr.shape)} is no integer multiple of lq {tuple(lq.shape)}")
+    lib = load()
+    m = COLOR_FIX_MODES[mode]
+    need = int(lib.rs_color_fix_work_bytes(B, Cc, H, W, sf, m))
+    work = torch.empty(need, device=sr.device, dtype=torch.uint8) if need else None
+    out = torch.empty_like(sr)
+    check(lib.rs_color_fix(sr.data_ptr(), lq.data_ptr(), out.data_ptr(), B, Cc, H, W, sf, m, work.data_ptr() if need else None, need,
+                           current_stream_ptr()), "rs_color_fix")
+    return out

@@ -197,6 +197,13 @@ class Engine:
         self._chk(rc, "rs_bicubic")
         return out
 
+    def color_fix(self, sr, lq, mode="wavelet"):
+        """The sample sr [B,C,H*sf,W*sf] corrected against its input lq [B,C,H,W], both in [-1,1]: "wavelet" keeps sr's detail and takes
+        the low frequencies of the bicubic up-sampled lq, "adain" takes lq's per-channel mean and deviation (rs_color_fix).
+        Returns a new tensor; whole images only - tiles are corrected after they are blended."""
+        with torch.cuda.device(self.device):
+            return _lib.color_fix(self._f32c(sr), self._f32c(lq), mode)
+
     def axpbypcz(self, x, z, n, a, b, c, out=None):
         """out = a*x + b*z + c*n elementwise on fp32 tensors of identical layout (z, n optional)."""
         x = self._f32c(x)

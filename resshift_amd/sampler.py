@@ -68,7 +68,7 @@ class BaseSampler:
 
     def __init__(self, configs, sf=4, use_amp=True, chop_size=128, chop_stride=128, chop_bs=1, padding_offset=16, seed=10000,
                  state_dicts: Optional[Mapping[str, Mapping[str, torch.Tensor]]] = None, blob_cache=None, precision=None, pack="policy",
-                 tile_blend="uniform"):
+                 tile_blend="uniform", color_fix="none"):
         """`state_dicts` ({"model": sd, "autoencoder": sd}) replaces checkpoint files, e.g. for synthetic-weight runs.
         `blob_cache`: file that keeps the packed device weights between runs (sharding.build_engine_with_broadcast).
         `precision`: "parity" | "fp16" | "fp32" | "split" (POLICIES).  Default: "parity" when `use_amp` (the reduced-precision path of the
@@ -78,7 +78,11 @@ class BaseSampler:
         form that was not packed fails loudly); "all" - every form (a process that switches policies).
         `tile_blend`: how overlapping tiles of `sample_tiled` / `inference` (with and without `pool`) are blended: "uniform" - the
         reference's average; "feather" - every tile weighted down towards its own edges across the overlap.  An image of
-        one tile is the same under both."""
+        one tile is the same under both.
+        `color_fix`: "none" | "wavelet" | "adain" - colour correction of every whole image `sample_tiled` / `inference` (with and without
+        `pool`) return against its LQ input, on the device (rs_color_fix): "wavelet" keeps the sample's detail and takes the
+        low frequencies of the bicubic up-sampled input, "adain" takes the input's per-channel mean and deviation.  Tiles are corrected
+        after they are blended, never one by one; `sample_func` is not affected.  Undefined for masked (inpainting) inputs: ValueError."""
         self.configs = configs if isinstance(configs, Mapping) else load_config(configs)
         self.sf = sf
         self.chop_size, self.chop_stride, self.chop_bs = chop_size, chop_stride, chop_bs
@@ -89,6 +93,8 @@ class BaseSampler:
             raise ValueError(f"unknown precision policy {self.precision!r} (one of {sorted(self.POLICIES)})")
         tiling.check_blend(tile_blend)
         self.tile_blend = tile_blend
+        tiling.check_color_fix(color_fix)
+        self.color_fix = color_fix
         if pack not in ("policy", "all"):
             raise ValueError("pack must be 'policy' or 'all'")
         self.pack = pack
@@ -198,6 +204,10 @@ class ResShiftSampler(BaseSampler):
         key (seed, stream = j) - what tilepool.TilePool(seeded=True) gives the same image; an untiled image is its tile 0."""
         from .tiling import TileSplitter
 
+        fix = getattr(self, "color_fix", "none")   # ("none" issues exactly the calls it always has)
+        tiling.check_color_fix(fix)
+        if fix != "none" and mask is not None:
+            raise ValueError(f"color_fix={fix!r} is undefined for a masked input (the LQ image has a hole): use color_fix='none'")
         B0 = im_lq.shape[0]
         if seed is not None:
             if tile_noises is not None or noise_repeat:
@@ -207,9 +217,11 @@ class ResShiftSampler(BaseSampler):
                 raise ValueError(f"seed: {B0} images but {len(seeds)} seeds")
         if not (im_lq.shape[2] > self.chop_size or im_lq.shape[3] > self.chop_size):
             if seed is not None:
-                return self.sample_func(im_lq, mask=mask, seeds=[(sd, 0) for sd in seeds])
-            nz = tile_noises[0] if tile_noises else (None, None)
-            return self.sample_func(im_lq, noise_repeat=noise_repeat, mask=mask, noise=nz[0], step_noises=nz[1])
+                sr = self.sample_func(im_lq, mask=mask, seeds=[(sd, 0) for sd in seeds])
+            else:
+                nz = tile_noises[0] if tile_noises else (None, None)
+                sr = self.sample_func(im_lq, noise_repeat=noise_repeat, mask=mask, noise=nz[0], step_noises=nz[1])
+            return sr if fix == "none" else self.engine.color_fix(sr, im_lq, fix)
         x = torch.cat([im_lq, mask], dim=1) if mask is not None else im_lq
         blend = getattr(self, "tile_blend", "uniform")   # ("uniform" issues exactly the calls it always has)
         splitter = TileSplitter(x, self.chop_size, stride=self.chop_stride, sf=self.sf, extra_bs=self.chop_bs,
@@ -226,7 +238,8 @@ class ResShiftSampler(BaseSampler):
                 nz = tile_noises[k] if tile_noises else (None, None)
                 out = self.sample_func(pch, noise_repeat=noise_repeat, mask=mask_pch, noise=nz[0], step_noises=nz[1])
             splitter.update(out, index_infos)
-        return splitter.gather()
+        sr = splitter.gather()
+        return sr if fix == "none" else self.engine.color_fix(sr, im_lq, fix)
 
     # ------------------------------------------------------------------ file-level demo driver
     @staticmethod
@@ -249,9 +262,13 @@ class ResShiftSampler(BaseSampler):
         submitted ahead while fewer than POOL_LOOKAHEAD tiles wait, then the pool steps.
         `seeded=True` (with and without `pool`): the image at position i of the sorted listing of the whole input gets the seed
         `image_seed(i)`, its tile j the stream j - the noise of a file does not depend on the number of ranks, on `bs` or
-        on `pool`, so neither do the PNGs beyond the engine's own batch-size sensitivity.  Excludes `noise_repeat`."""
+        on `pool`, so neither do the PNGs beyond the engine's own batch-size sensitivity.  Excludes `noise_repeat`.
+        The sampler's `color_fix` reaches every image through `sample_tiled` resp. the `TilePool`; it excludes `mask_path`."""
         if seeded and noise_repeat:
             raise ValueError("seeded=True names every draw by (seed, stream): it excludes noise_repeat")
+        fix = getattr(self, "color_fix", "none")
+        if fix != "none" and mask_path is not None:
+            raise ValueError(f"color_fix={fix!r} is undefined for masked (inpainting) inputs: use color_fix='none'")
         in_path, out_path = Path(in_path), Path(out_path)
         if self.rank == 0:
             out_path.mkdir(parents=True, exist_ok=True)

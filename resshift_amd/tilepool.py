@@ -27,6 +27,9 @@ The blend is the sampler's `tile_blend`: "uniform" (default, the reference's ave
 tiles retire through ONE `rs_tile_scatter_weighted` launch - the bits of `rs_tile_accumulate_weighted` tile by tile, which is what
 `sample_tiled` issues under the same mode - and the count plane holds the weight sum that `rs_tile_finalize` divides by.
 
+The sampler's `color_fix` ("none" by default) is applied to each completed image after `rs_tile_finalize`, against the
+image's own LQ planes (`rs_color_fix`): tiles are never corrected one by one.
+
 `seeded=True`: `submit(image, seed=...)` names the image; tile j (index in `tiling.extract_starts` order, the order of
 `tile_windows`) draws its noise from key (seed, stream = j) inside the engine's kernels.  No draws are made or stored, and an image's
 tiles get the same noise whatever else is pending, whichever pool or rank serves them, and in `ResShiftSampler.sample_tiled(seed=)`.
@@ -41,7 +44,7 @@ import torch
 
 from . import _lib
 from .continuous import ContinuousSampler, check_sampler, request_seed
-from .tiling import check_blend, extract_starts, feather_ramp
+from .tiling import check_blend, check_color_fix, extract_starts, feather_ramp
 
 HEADLINE_PIXELS = 32 * 64 * 64   # LR pixels of the benchmark's batch (32 images of 64 x 64): what `max_batch=None` fills a class up to
 
@@ -99,6 +102,11 @@ class TilePool:
         check_blend(self.blend)
         self.ramp = feather_ramp(self.chop_size, self.chop_stride, self.sf) if self.blend == "feather" else None
         self._tile_index: Dict[int, int] = {}
+        # so is the colour correction (BaseSampler(color_fix=)): applied to each completed image, never to a tile
+        self.color_fix = getattr(sampler, "color_fix", "none")
+        check_color_fix(self.color_fix)
+        if self.color_fix != "none" and self.cond_mask:
+            raise ValueError(f"color_fix={self.color_fix!r} is undefined for a model conditioned on a mask (the LQ image has a hole)")
 
     # ------------------------------------------------------------------ requests
     def class_max_batch(self, key: Tuple[int, int]) -> int:
@@ -225,7 +233,10 @@ class TilePool:
         else:
             _lib.tile_scatter(rows, batch, self.sf, ramp=self.ramp)
         for im in done:
-            out[im.id] = _lib.tile_finalize(im.acc, im.count)
+            res = _lib.tile_finalize(im.acc, im.count)
+            if self.color_fix != "none":   # the whole image against its own LQ planes
+                res = self.engine.color_fix(res.unsqueeze(0), im.src[:3].unsqueeze(0), self.color_fix)[0]
+            out[im.id] = res
             del self._images[im.id]
         return out
 

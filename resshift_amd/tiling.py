@@ -37,6 +37,14 @@ def check_blend(blend) -> None:
         raise ValueError(f"unknown tile blend {blend!r} (one of {sorted(BLENDS)})")
 
 
+COLOR_FIXES = ("none", "wavelet", "adain")
+
+
+def check_color_fix(color_fix) -> None:
+    if color_fix not in COLOR_FIXES:
+        raise ValueError(f"unknown colour fix {color_fix!r} (one of {sorted(COLOR_FIXES)})")
+
+
 def feather_ramp(pch_size: int, stride: int, sf: int) -> Tuple[int, int]:
     """(Rh, Rw) of the feather blend in HR pixels: the overlap of two neighbouring tiles"""
     r = (int(pch_size) - int(stride)) * int(sf)
