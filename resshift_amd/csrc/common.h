@@ -229,12 +229,13 @@ struct IGemmParams {
     int act;
     float out_scale;     // applied to the accumulator before bias
     long long bs_x0, bs_w, bs_y, bs_res;  // blockIdx.z batch strides in elements (batched GEMM mode)
-    int splitk;          // >1: grid.z slices K; fp32 partial slabs in `partial`, finished by splitk_reduce_kernel
+    int splitk;          // >1: grid.z slices K; fp32 partial slabs in `partial`, finished by splitk_reduce_kernel (set by rs_conv_launch from the plan)
     float* partial;      // [splitk][M][Cout] fp32 workspace (caller owned)
     unsigned x_bytes, w_bytes;  // extents of the x0 / w buffers for the igemm2 buffer descriptors (filled in by its launcher)
     int sh_howo, sh_wo;         // log2(Ho*Wo), log2(Wo) when both are powers of two, else -1 (filled in by the igemm2 launcher)
     int dbg;                    // timing ablations (RS_IGEMM_DBG): 1 = no operand loads after the prologue, 2 = no ds_read/MFMA, 4 = no barriers
-    int no_halo;                // 1: never the halo kernel (split storage: it scales the hi weight fragment by 2^11 - a layer with |w| >= 30 takes igemm_split)
+    int unscaled_w;             // planning input, 1: only kernels that leave the weights unscaled (split storage: the halo kernel scales the hi
+                                // weight fragment by 2^11 - a layer with |w| >= 30 takes igemm_split)
     // fused input transform (halo kernel igemm4.hip only): x is the RAW tensor; act_in(x * xcoef[b][0][c] + xcoef[b][1][c]),
     // rounded to the storage type, is what the convolution sees (GroupNorm affine [B][2][C0] of GNParams::coef + SiLU)
     const float* xcoef;
@@ -252,7 +253,7 @@ struct IGemmParams {
     // ldm/modules/diffusionmodules/model.py:121-127,148-149 nin_shortcut): y = conv3x3(act(gn(x0))) + bias + W_s sx + sbias.  The
     // shortcut is sC more K columns of the SAME accumulator - centre-tap stages behind the nine taps' stages, fed from the RAW block
     // input `sx` [B,Hs,Ws,(sld)] (no GroupNorm on those chunks) and the shortcut's split weights `sw` [Cout][sC hi | sC lo]: its
-    // GEMM launch, its output tensor and the residual read of that tensor disappear.  sx == null: none.
+    // GEMM launch, its output tensor and the residual read of that tensor disappear.  sC == 0: none (sC / sld are what the plan sees).
     const void* sx; const void* sw; const float* sbias;
     int sC, sld;
     unsigned sx_bytes, sw_bytes;   // (filled in by the launcher)
@@ -265,6 +266,19 @@ struct IGemmParams {
     // Winograd F(2x2,3x3) form of this layer's weights (wino.hip: rs_wino_pack order; split storage only), or null: with it a 3x3 / stride-1
     // conv on a plane that tiles by 16 x 16 runs on wino_kernel instead of the halo kernel (rs_wino_plan)
     const void* ww;
+};
+
+// Which kernel runs an IGemmParams launch, and how: made ONCE per launch by rs_conv_plan (igemm.hip) and executed by rs_conv_launch.  A
+// function of the layout (shapes, strides, storage types, nz) and of the request flags alone - Winograd weights present (ww), folded
+// shortcut present (sC > 0), unscaled_w, osc, act, dbg bit 6 - never of a pointer's value or alignment: the engine's dry sizing pass and
+// its real pass plan the same launch and must get the same answer.
+enum ConvKernel { CK_NONE = 0, CK_WINO, CK_HALO, CK_HALO_SEG, CK_SPLIT, CK_IGEMM3, CK_IGEMM2, CK_IGEMM };   // CK_NONE: no kernel takes the launch
+struct ConvPlan {
+    int kernel;      // ConvKernel (halo: CK_HALO = 256-pixel tiles on big planes, CK_HALO_SEG = the small-plane geometries)
+    int BP, BC;      // pixel tile (halo: tile width TW; igemm2: its variant code) and channel tile
+    int SEG;         // CK_HALO_SEG: 16 = one 16 x 16 image per tile, 8 = four 8 x 8 images per tile
+    int splitk;      // K slices (1: none); > 1 needs IGemmParams::partial = [splitk][M][Cout] floats
+    int stats_px;    // pixels per IGemmParams::ystats slab if the launch is asked for output statistics (0: it cannot produce them)
 };
 
 #if defined(__HIPCC__)

@@ -33,18 +33,11 @@
 #include <vector>
 
 extern "C" {
-int rs_igemm_launch(const IGemmParams* p, int in_dt, int out_dt, int nz, hipStream_t st);
-int rs_igemm_splitk_plan(int M, int Cout, int Ktot, int in_dt);
-int rs_igemm4_pick(const IGemmParams* p, int in_dt, int out_dt, int nz, int* TW, int* BC);
-int rs_igemm4_plan(const IGemmParams* p, int in_dt, int out_dt, int nz, int* TW, int* BC, int* SEG, int* SK);
-int rs_igemm4_stats_px(const IGemmParams* p, int in_dt);
-int rs_wino_plan(const IGemmParams* p, int in_dt, int out_dt, int nz);
-int rs_wino_launch(const IGemmParams* p, hipStream_t st);
+int rs_conv_plan(const IGemmParams* p, int in_dt, int out_dt, int nz, ConvPlan* plan);   // igemm.hip: THE kernel / tile / split-K decision
+int rs_conv_launch(const IGemmParams* p, int in_dt, int out_dt, int nz, const ConvPlan* plan, hipStream_t st);
 size_t rs_wino_weight_bytes(int Cin, int Cout);
 float rs_wino_pack(const float* w_ref, int Cin, int Cout, void* dst);
-int rs_wino_stats_px();
 int rs_wino_tiles(const IGemmParams* p);
-int rs_igemm_split_stats_px(const IGemmParams* p, int splitk);
 int rs_direct_conv_launch(const DirectConvParams* p, int in_dt, int out_dt, hipStream_t st);
 int rs_head_conv_launch(const void* x, int in_dt, const float* coef_dev, const float* w_dev, const float* bias_dev, float* y, int B, int H, int W, int C,
                         int ldx, int Cout, int ldy, hipStream_t st);
@@ -332,35 +325,25 @@ struct Exec {
             tag_of.emplace_back(b); tag_flops.push_back(flops);
         }
     }
-    void igemm(const IGemmParams& p, int in_dt, int out_dt, int nz, const char* what) {
-        const int Kall = p.Ktot + (p.sx ? p.sC : 0);   // (+ the K columns of a folded 1x1 shortcut)
-        igemm_flops[in_dt == RS_F16 ? 0 : (in_dt == RS_F16S ? 2 : 1)] += 2.0 * (double)p.M * (double)p.Cout * (double)Kall * (double)nz;
-        {
-            int tw, bc;
-            const bool wino = rs_wino_plan(&p, in_dt, out_dt, nz) != 0;
-            const bool halo = !wino && rs_igemm4_pick(&p, in_dt, out_dt, nz, &tw, &bc) != 0;
-            const int f = wino ? F_WINO_S : (in_dt == RS_F16 ? (halo ? F_HALO16 : F_IGEMM16) : (in_dt == RS_F16S ? (halo ? F_HALO_SPLIT : F_IGEMM_SPLIT) : F_IGEMM32));
-            fam_note(f, 2.0 * (double)p.M * (double)p.Cout * (double)Kall * (double)nz, p.M, p.Cout, Kall, nz);
-        }
+    // (`pl`: the launch's plan, made once by the caller - the family it is booked under, the reduce launch of its split-K slices)
+    void igemm(const IGemmParams& p, const ConvPlan& pl, int in_dt, int out_dt, int nz, const char* what) {
+        const int Kall = p.Ktot + p.sC;   // (+ the K columns of a folded 1x1 shortcut)
+        const double fl = 2.0 * (double)p.M * (double)p.Cout * (double)Kall * (double)nz;
+        igemm_flops[in_dt == RS_F16 ? 0 : (in_dt == RS_F16S ? 2 : 1)] += fl;
+        const bool halo = pl.kernel == CK_HALO || pl.kernel == CK_HALO_SEG;
+        fam_note(pl.kernel == CK_WINO ? F_WINO_S : (in_dt == RS_F16 ? (halo ? F_HALO16 : F_IGEMM16) : (in_dt == RS_F16S ? (halo ? F_HALO_SPLIT : F_IGEMM_SPLIT) : F_IGEMM32)),
+                 fl, p.M, p.Cout, Kall, nz);
         {
             const double isz = in_dt == RS_F16 ? 2.0 : 4.0, osz = out_dt == RS_F16 ? 2.0 : 4.0;
-            const double src = (double)p.B * p.Hs * p.Ws * (double)(p.C0 + p.C1 + (p.sx ? p.sC : 0)) * isz;
+            const double src = (double)p.B * p.Hs * p.Ws * (double)(p.C0 + p.C1 + p.sC) * isz;
             const double out = (double)p.M * p.Cout * osz;
             igemm_bytes += (double)nz * (src + (double)p.Cout * Kall * isz + out + (p.res ? out : 0.0));
         }
         ++igemm_launches;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (prof && prof->on) {
-            if (prof->used + 2 > prof->ev.size()) {
-                const size_t old = prof->ev.size();
-                prof->ev.resize(old + 1024);
-                for (size_t i = old; i < prof->ev.size(); ++i) (void)hipEventCreate(&prof->ev[i]);
-            }
-            e0 = prof->ev[prof->used++]; e1 = prof->ev[prof->used++];
-            (void)hipEventRecord(e0, st);
-        }
-        check(rs_igemm_launch(&p, in_dt, out_dt, nz, st), what);
-        if (p.splitk > 1) ++launches;   // (the slices' reduce kernel)
+        hipEvent_t e0, e1;
+        bracket(prof, st, e0, e1);
+        check(rs_conv_launch(&p, in_dt, out_dt, nz, &pl, st), what);
+        if (pl.splitk > 1) ++launches;   // (the slices' reduce kernel)
         if (e1) (void)hipEventRecord(e1, st);
     }
     // fused qkv projection + window attention: the projection's FLOPs / compulsory bytes stay in the MFMA-family bookkeeping
@@ -371,16 +354,8 @@ struct Exec {
         fam_note(sp ? F_WINATTN_S : F_WINATTN, 2.0 * M * (p.wproj ? 4.0 : 3.0) * E * E + 2.0 * 2.0 * M * 64.0 * E, (long long)M, E, E);   // + QK^T and PV of the 64-token windows
         igemm_bytes += (sp ? 4.0 : 2.0) * (M * E * (p.res ? 3.0 : 2.0) + (p.wproj ? 4.0 : 3.0) * E * E);
         ++igemm_launches;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (prof && prof->on) {
-            if (prof->used + 2 > prof->ev.size()) {
-                const size_t old = prof->ev.size();
-                prof->ev.resize(old + 1024);
-                for (size_t i = old; i < prof->ev.size(); ++i) (void)hipEventCreate(&prof->ev[i]);
-            }
-            e0 = prof->ev[prof->used++]; e1 = prof->ev[prof->used++];
-            (void)hipEventRecord(e0, st);
-        }
+        hipEvent_t e0, e1;
+        bracket(prof, st, e0, e1);
         if (sp) check(rs_win_attn_qkv_split_launch(&p, st), "win_attn_qkv_split");
         else check(rs_win_attn_qkv_launch(&p, st), "win_attn_qkv");
         if (e1) (void)hipEventRecord(e1, st);
@@ -411,16 +386,8 @@ struct Exec {
         fam_note(sp ? F_SWINMLP_S : F_SWINMLP, fl, M, NO, HD);
         igemm_bytes += (sp ? 4.0 : 2.0) * ((double)M * (E * ((res || NO != E) ? 2.0 : 1.0) + NO) + (double)E * HD + (double)NO * (NO != E ? HD + E : HD));
         ++igemm_launches;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (prof && prof->on) {
-            if (prof->used + 2 > prof->ev.size()) {
-                const size_t old = prof->ev.size();
-                prof->ev.resize(old + 1024);
-                for (size_t i = old; i < prof->ev.size(); ++i) (void)hipEventCreate(&prof->ev[i]);
-            }
-            e0 = prof->ev[prof->used++]; e1 = prof->ev[prof->used++];
-            (void)hipEventRecord(e0, st);
-        }
+        hipEvent_t e0, e1;
+        bracket(prof, st, e0, e1);
         if (sp) check(rs_swin_mlp_split_launch_n(x, w1, b1, w2, b2, res, y, M, ldx, ldres, ldy, E, HD, NO, xcoef, HW, ystats, ystats_ld, tail, st), "swin_mlp_split");
         else check(rs_swin_mlp_launch(x, w1, b1, w2, b2, res, y, M, ldx, ldres, ldy, E, HD, xcoef, HW, ystats, ystats_ld, st), "swin_mlp");
         if (e1) (void)hipEventRecord(e1, st);
@@ -463,7 +430,7 @@ struct rs_engine {
     // ... and a layer whose weights reach |w| >= 30 is not a reason to refuse the policy: only the kernels that scale the hi fragment by
     // 2^11 (the halo conv, the fused split Swin kernels) cannot take it, the generic split kernel (igemm_split.hip: two accumulators, no
     // scaling) can.  One flag byte per conv / linear in build order, written into the blob by the packing rank (it travels with the
-    // broadcast) and read back by rs_weights_ready; halo_conv() / basiclayer() route a flagged layer to the generic kernels.
+    // broadcast) and read back by rs_weights_ready; plan_conv() (IGemmParams::unscaled_w) / basiclayer() route a flagged layer to the generic kernels.
     std::vector<unsigned char> big_w;
     int conv_count = 0;
     unsigned char* big_w_dev = nullptr;
@@ -696,34 +663,39 @@ struct rs_engine {
         // launches that cannot fill the chip each - the pass is 0.9 ms slower than with the 32 -> 64 step alone)
         return (long long)x.B * x.H * x.W >= 16384;
     }
+    // the plan of each of the four launches (same shape, scattered rows: osc)
+    ConvPlan upfold_plan(const ConvW (&upf)[4], const View& x, const View& y) const {
+        View yl = y; yl.H = x.H; yl.W = x.W;   // a launch computes the low-resolution grid; its rows are scattered into y
+        IGemmParams p = conv_params(upf[0], x, nullptr, yl, 1, 1, 1, 1, 0, nullptr, 1.f);
+        p.osc = 2;
+        ConvPlan pl{};
+        (void)rs_conv_plan(&p, x.dt, y.dt, 1, &pl);
+        return pl;
+    }
     // statistics of y for the consuming GroupNorm from the four launches' epilogues (split storage): one slab per low-resolution pixel tile
     // and parity class
-    void upfold_want_stats(Exec& ex, const ConvW (&upf)[4], const View& x, View& y) {
+    void upfold_want_stats(Exec& ex, const ConvPlan& pl, const View& x, View& y) {
         static const bool on = []() { const char* e = getenv("RS_GN_EPI_STATS"); return !(e && e[0] == '0'); }();
         static const bool gen = []() { const char* e = getenv("RS_GN_GEN_STATS"); return !(e && e[0] == '0'); }();
         y.st = nullptr; y.st2 = nullptr; y.st_prod = -1;
-        if (!on || !gen || x.dt != RS_F16S || y.dt != RS_F16S) return;
-        View yl = y; yl.H = x.H; yl.W = x.W;
-        const IGemmParams pp = conv_params(upf[0], x, nullptr, yl, 1, 1, 1, 1, 0, nullptr, 1.f);
-        const int spx = rs_igemm_split_stats_px(&pp, 1);
-        if (spx <= 0 || ((x.H * x.W) % spx)) return;
+        const int spx = pl.stats_px;
+        if (!on || !gen || pl.kernel != CK_SPLIT || spx <= 0 || ((x.H * x.W) % spx)) return;
         y.stS = 4 * (x.H * x.W / spx); y.stld = y.C;
         y.st = ex.pool((size_t)y.B * y.stS * y.stld * 2 * sizeof(float));
         y.st_prod = ex.prod_seq++;
     }
-    void upfold_conv(Exec& ex, const ConvW (&upf)[4], const View& x, const View& y) {
+    void upfold_conv(Exec& ex, const ConvPlan& pl, const ConvW (&upf)[4], const View& x, const View& y) {
         if (ex.dry) return;
         GNTail tl{};
         if (y.st) (void)ex.fill_tail(y.st_prod, y.B, tl);   // ONE tail (one ticket per image) for the four launches
         for (int q = 0; q < 4; ++q) {
             const int py = q >> 1, px = q & 1;
-            View yl = y; yl.H = x.H; yl.W = x.W;   // the launch computes the low-resolution grid; its rows are scattered into y
+            View yl = y; yl.H = x.H; yl.W = x.W;
             IGemmParams p = conv_params(upf[q], x, nullptr, yl, 1, 1 - py, 1 - px, 1, 0, nullptr, 1.f);
-            p.no_halo = 1;
             p.osc = 2; p.ooy = py; p.oox = px;
             if (y.st) { p.ystats = y.st; p.ystats_ld = y.stld; p.tail = tl; }
             if (!p.w) { ex.err = -3; g_err = "weights for this precision were not packed (enable_f16/enable_f32/enable_split)"; return; }
-            ex.igemm(p, x.dt, y.dt, 1, "igemm");
+            ex.igemm(p, pl, x.dt, y.dt, 1, "igemm");
         }
     }
     // Fragment-major copies of a 1x1 weight [N][K] (N % 16 == 0, K % 32 == 0) for win_attn_qkv_kernel / win_attn_qkv_split_kernel: lane
@@ -1034,9 +1006,9 @@ struct rs_engine {
     }
 
     // ---------------------------------------------------------------- ops
-    // parameter block of one implicit-GEMM conv launch (shared by conv() and the halo-kernel eligibility test)
-    static IGemmParams conv_params(const ConvW& w, const View& x, const View* x1, const View& y, int stride, int pad_t, int pad_l, int up,
-                                   int act, const View* res, float out_scale) {
+    // parameter block of one implicit-GEMM conv launch: the layout and the planning inputs (plan_conv()); conv() adds what only the launch needs
+    IGemmParams conv_params(const ConvW& w, const View& x, const View* x1, const View& y, int stride, int pad_t, int pad_l, int up,
+                            int act, const View* res, float out_scale) const {
         const int C1 = x1 ? x1->C : 0;
         IGemmParams p{};
         p.x0 = x.p; p.x1 = x1 ? x1->p : nullptr; p.w = w.w_for(x.dt); p.bias = w.bias;
@@ -1047,51 +1019,32 @@ struct rs_engine {
         p.M = y.B * y.H * y.W; p.Ktot = w.KH * w.KW * (x.C + C1); p.act = act; p.out_scale = out_scale;
         p.splitk = 1;
         p.ww = (x.dt == RS_F16S && !x1) ? w.ww : nullptr;
+        p.unscaled_w = (x.dt == RS_F16S && big(w)) ? 1 : 0;   // |w| >= 30: no 2^11 scaling of the hi fragment - the generic split kernel takes it
         return p;
     }
-    // true when this 3x3 conv runs on the halo kernel (igemm4.hip), which can apply a GroupNorm affine + SiLU to its input
-    // while the halo tile sits in LDS: the producer's raw output is read, the GroupNorm apply pass disappears
-    // (`sk`: the halo kernel's own split-K factor for this launch - the small planes of the 16 x 16 / 8 x 8 levels run as split-K
-    // slices over the stage sequence, igemm4_kernel.h; `seg`: its tile geometry, 8 = four 8 x 8 images per tile)
-    // (`folded`: the launch will carry a folded 1x1 shortcut - only the halo kernel does that; `wino`: out, the Winograd kernel takes it)
-    bool halo_conv(const ConvW& w, const View& x, const View& y, const View* res, int* sk = nullptr, int* seg = nullptr, bool folded = false,
-                   bool* wino = nullptr) const {
-        if (wino) *wino = false;
-        if (w.direct || (x.dt != RS_F16 && x.dt != RS_F16S) || y.dt != x.dt || x.C != w.CinP) return false;
-        if (x.dt == RS_F16S && big(w)) return false;   // |w| >= 30: no 2^11 scaling of the hi fragment - the generic split kernel takes it (conv(): IGemmParams::no_halo)
-        const IGemmParams p = conv_params(w, x, nullptr, y, 1, 1, 1, 1, 0, res, 1.f);
-        if (!folded && rs_wino_plan(&p, x.dt, y.dt, 1)) {   // same fusions as the halo kernel (input transform, statistics, tail), its own tiles
-            if (sk) *sk = 1;
-            if (seg) *seg = 0;
-            if (wino) *wino = true;
-            return true;
-        }
-        int tw, bc, sg = 0, k = 1;
-        if (!rs_igemm4_plan(&p, x.dt, y.dt, 1, &tw, &bc, &sg, &k)) return false;
-        if (sk) *sk = k;
-        if (seg) *seg = sg;
-        return true;
+    // The plan of the launch conv() makes for these arguments (rs_conv_plan: the kernel, its split-K factor, the statistics it can leave).
+    // A conv is planned ONCE: by its call site, which hands the plan to want_stats() / skip_fold() / gn_silu_conv3() / conv(), or by conv()
+    // itself.  The dry and the real pass get the same plan: it depends on the layout only.  On the halo and Winograd kernels the conv can
+    // apply a GroupNorm affine + SiLU to its input while the tile sits in LDS (fuses_gn()); `skx`: the block input of a folded 1x1 shortcut.
+    ConvPlan plan_conv(const ConvW& w, const View& x, const View* x1, const View& y, int stride, int pad_t, int pad_l, int up, int act,
+                       const View* res, const View* skx = nullptr) const {
+        ConvPlan pl{};   // (CK_NONE: the direct kernel, or a launch that conv() refuses)
+        if (w.direct || x.C + (x1 ? x1->C : 0) != w.CinP) return pl;
+        IGemmParams p = conv_params(w, x, x1, y, stride, pad_t, pad_l, up, act, res, 1.f);
+        if (skx) { p.sC = skx->C; p.sld = skx->ld; }
+        (void)rs_conv_plan(&p, x.dt, y.dt, 1, &pl);
+        return pl;
     }
+    ConvPlan plan3(const ConvW& w, const View& x, const View& y, const View* res, const View* skx = nullptr) const { return plan_conv(w, x, nullptr, y, 1, 1, 1, 1, 0, res, skx); }
+    static bool fuses_gn(const ConvPlan& pl) { return pl.kernel == CK_WINO || pl.kernel == CK_HALO || pl.kernel == CK_HALO_SEG; }
     void conv(Exec& ex, const ConvW& w, const View& x, const View* x1, const View& y, int stride, int pad_t, int pad_l, int up,
               int act, const View* res, float out_scale = 1.f, const float* xcoef = nullptr, int xact = RS_ACT_NONE,
-              const ConvW* skw = nullptr, const View* skx = nullptr) {
+              const ConvW* skw = nullptr, const View* skx = nullptr, const ConvPlan* plan = nullptr) {
         const int C1 = x1 ? x1->C : 0;
-        // split-K for launches that cannot fill the chip (8x8 / 16x16 UNet levels): fp32 slabs live in the arena
-        int splitk = 1;
-        float* partial = nullptr;
-        if (!w.direct) {
-            const int M = y.B * y.H * y.W;
-            int sk4 = 1;
-            // the halo kernel plans its own split-K (slices of the stage sequence); everything else asks the generic planner
-            if (!x1 && w.KH == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && up == 1 && halo_conv(w, x, y, res, &sk4, nullptr, skw != nullptr)) splitk = sk4;
-            else splitk = rs_igemm_splitk_plan(M, w.Cout, w.KH * w.KW * (x.C + C1), x.dt);
-            if (splitk > 1) partial = (float*)ex.raw((size_t)splitk * M * w.Cout * sizeof(float));
-        }
         // split storage has no two-source implicit GEMM: gather the channel concatenation once (only the first conv of the
         // feature-extractor configs, unet.py:882)
-        View xcat;
         if (!w.direct && x1 && x.dt == RS_F16S) {
-            xcat = ex.T(x.B, x.H, x.W, x.C + C1, x.dt);
+            View xcat = ex.T(x.B, x.H, x.W, x.C + C1, x.dt);
             if (!ex.dry) {
                 ex.check(rs_copy_channels_launch(x.p, x.ld, xcat.p, xcat.ld, x.C, x.pixels(), x.dt, ex.st), "concat copy");
                 ex.check(rs_copy_channels_launch(x1->p, x1->ld, xcat.slice(x.C, C1).p, xcat.ld, C1, x.pixels(), x.dt, ex.st), "concat copy");
@@ -1099,6 +1052,9 @@ struct rs_engine {
             conv(ex, w, xcat, nullptr, y, stride, pad_t, pad_l, up, act, res, out_scale);
             return;
         }
+        const ConvPlan pl = plan ? *plan : plan_conv(w, x, x1, y, stride, pad_t, pad_l, up, act, res, skw ? skx : nullptr);
+        // split-K for launches that cannot fill the chip (8x8 / 16x16 UNet levels): fp32 slabs live in the arena
+        float* const partial = pl.splitk > 1 ? (float*)ex.raw((size_t)pl.splitk * y.B * y.H * y.W * w.Cout * sizeof(float)) : nullptr;
         if (ex.dry) return;
         if (x.C + C1 != w.CinP) { if (!ex.err) { ex.err = -3; g_err = "conv input channels do not match the packed weights"; } return; }
         if (w.direct) {
@@ -1111,18 +1067,16 @@ struct rs_engine {
             ex.check(rs_direct_conv_launch(&p, x.dt, y.dt, ex.st), "direct_conv");
         } else {
             IGemmParams p = conv_params(w, x, x1, y, stride, pad_t, pad_l, up, act, res, out_scale);
-            p.no_halo = (x.dt == RS_F16S && big(w)) ? 1 : 0;   // (the launcher picks the kernel from the parameter block: tell it what halo_conv() decided)
-            p.splitk = splitk; p.partial = partial;
+            p.partial = partial;
             p.xcoef = xcoef; p.xact = xact;
-            if (skw) { p.sx = skx->p; p.sw = skw->w_for(x.dt); p.sbias = skw->bias; p.sC = skx->C; p.sld = skx->ld; p.ww = nullptr; }   // folded 1x1 shortcut (skip_fold()): the halo kernel's
-            if (y.st) {   // statistics for the consuming GroupNorm: the halo kernel's or the generic split kernel's epilogue (or their split-K reduce)
-                const bool halo = !x1 && w.KH == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && up == 1 && halo_conv(w, x, y, res, nullptr, nullptr, skw != nullptr);
-                if (halo || (!x1 && x.dt == RS_F16S && y.dt == RS_F16S)) { p.ystats = y.st; p.ystats_ld = y.stld; }
-                else { ex.err = -3; g_err = "output statistics requested from a conv whose kernel cannot produce them"; return; }
+            if (skw) { p.sx = skx->p; p.sw = skw->w_for(x.dt); p.sbias = skw->bias; p.sC = skx->C; p.sld = skx->ld; }   // folded 1x1 shortcut (skip_fold()): the halo kernel's
+            if (y.st) {   // statistics for the consuming GroupNorm: the kernel's epilogue or its split-K reduce (want_stats() asked the same plan)
+                if (!pl.stats_px) { ex.err = -3; g_err = "output statistics requested from a conv whose kernel cannot produce them"; return; }
+                p.ystats = y.st; p.ystats_ld = y.stld;
                 (void)ex.fill_tail(y.st_prod, y.B, p.tail);   // ... and that GroupNorm's coefficients too (gn_tail.h)
             }
             if (!p.w) { ex.err = -3; g_err = "weights for this precision were not packed (enable_f16/enable_f32/enable_split)"; return; }
-            ex.igemm(p, x.dt, y.dt, 1, "igemm");
+            ex.igemm(p, pl, x.dt, y.dt, 1, "igemm");
         }
     }
     void zero(Exec& ex, const View& v) {
@@ -1131,40 +1085,33 @@ struct rs_engine {
         ex.check(e == hipSuccess ? 0 : -1, "memset");
     }
     void conv3(Exec& ex, const ConvW& w, const View& x, const View& y, const View* res = nullptr, int act = 0, const float* xcoef = nullptr,
-               int xact = RS_ACT_NONE, const ConvW* skw = nullptr, const View* skx = nullptr) {
-        conv(ex, w, x, nullptr, y, 1, 1, 1, 1, act, res, 1.f, xcoef, xact, skw, skx);
+               int xact = RS_ACT_NONE, const ConvW* skw = nullptr, const View* skx = nullptr, const ConvPlan* plan = nullptr) {
+        conv(ex, w, x, nullptr, y, 1, 1, 1, 1, act, res, 1.f, xcoef, xact, skw, skx, plan);
     }
     // A ResBlock's 1x1 shortcut (models/unet.py:178-183,205-206; ldm/modules/diffusionmodules/model.py:121-127,148-149) as extra K columns
     // of its second 3x3 conv (IGemmParams::sx) instead of a GEMM launch + a tensor + a residual read: split storage on the halo kernel's
     // 8-wave big-plane tiles, whole 32-channel chunks of the block input, no weight that needs the unscaled path.  RS_SKIP_FOLD=0: off.
-    bool skip_fold(const Exec& ex, const ResBlockW& r, const View& X, const View& h1, const View& Y) const {
+    // `pl`: conv2's plan WITH the shortcut folded in (plan3(r.c2, h1, Y, nullptr, &X)).
+    bool skip_fold(const ResBlockW& r, const View& X, const View& Y, const ConvPlan& pl) const {
         static const bool on = []() { const char* e = getenv("RS_SKIP_FOLD"); return !(e && e[0] == '0'); }();
         static const bool fold = []() { const char* e = getenv("RS_GN_CONV_FOLD"); return !(e && e[0] == '0'); }();
         static const bool on16 = []() { const char* e = getenv("RS_SKIP_FOLD_F16"); return !(e && e[0] == '0'); }();   // (fp16 storage: the decoder's nin_shortcuts, the fp16 policy's UNet)
         if (!on || !fold || !r.has_skip || (X.dt != RS_F16S && !(X.dt == RS_F16 && on16)) || Y.dt != X.dt) return false;
         if (X.dt == RS_F16S && (big(r.skip) || big(r.c2))) return false;
         if (!r.skip.w_for(X.dt) || r.skip.KH != 1 || X.C != r.skip.CinP || (X.C % 32) || (X.ld % 8) || X.H != Y.H || X.W != Y.W) return false;
-        int sk = 1, seg = 0;
-        return halo_conv(r.c2, h1, Y, nullptr, &sk, &seg, true) && sk == 1 && seg == 0;   // (the HALO kernel's plan: the fold - a GEMM launch saved - beats the Winograd kernel's 10 %)
+        return pl.kernel == CK_HALO;   // (the HALO kernel's big-plane tiles, no split-K: the fold - a GEMM launch saved - beats the Winograd kernel's 10 %)
     }
-    // Attach a statistics buffer to a tensor that is about to be produced by conv `w` from `x` (+res) IF its kernel can leave them: the halo
+    // Attach a statistics buffer to a tensor that is about to be produced by the conv planned as `pl` IF its kernel can leave them: the halo
     // kernel (one partial set per 256- or 128-pixel tile of one image), the generic split-storage kernel (RS_GN_GEN_STATS, default on: one
     // set per 128- / 64-pixel tile), or - split-K launches of either - the reduce kernel (slabs of 256 pixels / the whole small image).
     // The buffer lives in the coefficient pool (reset per network body), so a block's output may carry it to whoever consumes it later
     // (the next block, the decoder's concatenation).
-    void want_stats(Exec& ex, const ConvW& w, const View& x, View& y, const View* res, int stride = 1, int pad = 1, int up = 1, bool folded = false) {
+    void want_stats(Exec& ex, const ConvPlan& pl, View& y) {
         static const bool on = []() { const char* e = getenv("RS_GN_EPI_STATS"); return !(e && e[0] == '0'); }();
         static const bool gen = []() { const char* e = getenv("RS_GN_GEN_STATS"); return !(e && e[0] == '0'); }();
-        const int HW = y.H * y.W;
+        const int HW = y.H * y.W, spx = pl.stats_px;
         y.st = nullptr; y.st2 = nullptr; y.st_prod = -1;
-        if (!on || w.direct) return;
-        const IGemmParams pp = conv_params(w, x, nullptr, y, stride, pad, pad, up, 0, res, 1.f);
-        int spx = 0;
-        bool wino = false;
-        if (w.KH == 3 && stride == 1 && pad == 1 && up == 1 && halo_conv(w, x, y, res, nullptr, nullptr, folded, &wino)) spx = wino ? rs_wino_stats_px() : rs_igemm4_stats_px(&pp, x.dt);
-        else if (gen && x.dt == RS_F16S && y.dt == RS_F16S && x.C == w.CinP)
-            spx = rs_igemm_split_stats_px(&pp, rs_igemm_splitk_plan(pp.M, w.Cout, w.KH * w.KW * x.C, x.dt));
-        if (spx <= 0 || (HW % spx)) return;
+        if (!on || (pl.kernel == CK_SPLIT && !gen) || spx <= 0 || (HW % spx)) return;
         y.stS = HW / spx; y.stld = y.C;
         y.st = ex.pool((size_t)y.B * y.stS * y.stld * 2 * sizeof(float));
         y.st_prod = ex.prod_seq++;
@@ -1172,18 +1119,18 @@ struct rs_engine {
     // GroupNorm (+FiLM) + SiLU + 3x3 conv (models/unet.py:128-147,198-203; ldm/modules/diffusionmodules/model.py:129-147): on the
     // halo kernel the GroupNorm only produces per-(image, channel) affine coefficients and the conv applies them to the RAW tensor
     // in LDS (bit-identical to normalising first); otherwise normalise into a scratch tensor and convolve that
-    void gn_silu_conv3(Exec& ex, const GNW& g, const ConvW& w, const View& X, const View& Y, float eps, const float* film, const View* res,
-                       const ConvW* skw = nullptr, const View* skx = nullptr) {
+    void gn_silu_conv3(Exec& ex, const ConvPlan& pl, const GNW& g, const ConvW& w, const View& X, const View& Y, float eps, const float* film,
+                       const View* res, const ConvW* skw = nullptr, const View* skx = nullptr) {
         static const bool fold = []() { const char* e = getenv("RS_GN_CONV_FOLD"); return !(e && e[0] == '0'); }();
-        if (fold && halo_conv(w, X, Y, res, nullptr, nullptr, skw != nullptr)) {
+        if (fold && fuses_gn(pl)) {
             const float* coef = gn_coef(ex, g, X, eps, film);
-            conv3(ex, w, X, Y, res, 0, coef, RS_ACT_SILU, skw, skx);
+            conv3(ex, w, X, Y, res, 0, coef, RS_ACT_SILU, skw, skx, &pl);
             return;
         }
         if (skw) { if (!ex.err) { ex.err = -3; g_err = "folded shortcut planned for a conv that does not run on the halo kernel"; } return; }
         View t = ex.T(X.B, X.H, X.W, X.C, X.dt);
         gn(ex, g, X, t, eps, RS_ACT_SILU, film);
-        conv3(ex, w, t, Y, res);
+        conv3(ex, w, t, Y, res);   // (another launch - the dense scratch tensor is its input: conv() plans it)
     }
     // GroupNorm + SiLU + conv3x3 to <= 4 channels (the UNet's `out`, Encoder / Decoder norm_out + conv_out) -> fp32 NHWC `o`: one fused pass
     // (gn_silu_head_conv_kernel) over the raw tensor with the GroupNorm as coefficients; RS_HEAD_FUSED=0: normalise, then
@@ -1200,6 +1147,12 @@ struct rs_engine {
         gn(ex, g, X, t, eps, RS_ACT_SILU);
         conv(ex, w, t, nullptr, o, 1, 1, 1, 1, 0, nullptr);
         ex.reset(mk);
+    }
+    // a conv whose epilogue also leaves the statistics (+ coefficients) for the GroupNorm that consumes y: one plan for want_stats() and conv()
+    void conv_st(Exec& ex, const ConvW& w, const View& x, View& y, int stride, int pad, int up, const View* res = nullptr, bool stats = true) {
+        const ConvPlan pl = plan_conv(w, x, nullptr, y, stride, pad, pad, up, 0, res);
+        if (stats) want_stats(ex, pl, y);
+        conv(ex, w, x, nullptr, y, stride, pad, pad, up, 0, res, 1.f, nullptr, RS_ACT_NONE, nullptr, nullptr, &pl);
     }
     void conv1(Exec& ex, const ConvW& w, const View& x, const View& y, const View* res = nullptr, int act = 0) {
         conv(ex, w, x, nullptr, y, 1, 0, 0, 1, act, res);
@@ -1266,55 +1219,38 @@ struct rs_engine {
     // models/unet.py:186-206 (use_scale_shift_norm path); eps 1e-5 (basic_ops.py:96 default GroupNorm eps)
     // `out_stats`: conv2's epilogue also leaves the statistics (and, when the dry pass planned it, the coefficients) for the GroupNorm that
     // consumes Y - the next block's in_layers[0], possibly through the decoder's concatenation
-    void resblock(Exec& ex, const ResBlockW& r, const View& X, View& Y, const float* film_row, bool out_stats = true) {
+    void resblock(Exec& ex, const ResBlockW& r, const View& X, View& Y, const float* film_row, bool out_stats = true, float eps = 1e-5f) {
         const size_t mk = ex.mark();
         View h1 = ex.T(X.B, X.H, X.W, r.Cout, X.dt);
-        want_stats(ex, r.c1, X, h1, nullptr);   // conv1's epilogue leaves the statistics norm2 needs
-        gn_silu_conv3(ex, r.n1, r.c1, X, h1, 1e-5f, nullptr, nullptr);
+        const ConvPlan p1 = plan3(r.c1, X, h1, nullptr);
+        want_stats(ex, p1, h1);   // conv1's epilogue leaves the statistics norm2 needs
+        gn_silu_conv3(ex, p1, r.n1, r.c1, X, h1, eps, nullptr, nullptr);
         ex.tr("conv1", h1);
         const float* film = film_row ? film_row + r.film_off : nullptr;
-        if (skip_fold(ex, r, X, h1, Y)) {
-            if (out_stats) want_stats(ex, r.c2, h1, Y, nullptr, 1, 1, 1, true);
-            gn_silu_conv3(ex, r.n2, r.c2, h1, Y, 1e-5f, film, nullptr, &r.skip, &X);
-        } else if (r.has_skip) {
-            View sk = ex.T(X.B, X.H, X.W, r.Cout, X.dt);
+        // the shortcut: folded into conv2 (skip_fold()), a 1x1 conv whose output conv2 adds, or the block input itself
+        const View* res = &X;
+        View sk;
+        ConvPlan p2 = r.has_skip ? plan3(r.c2, h1, Y, nullptr, &X) : ConvPlan{};
+        const bool folded = r.has_skip && skip_fold(r, X, Y, p2);
+        if (folded) res = nullptr;
+        else if (r.has_skip) {
+            sk = ex.T(X.B, X.H, X.W, r.Cout, X.dt);
             conv1(ex, r.skip, X, sk);
-            if (out_stats) want_stats(ex, r.c2, h1, Y, &sk);
-            gn_silu_conv3(ex, r.n2, r.c2, h1, Y, 1e-5f, film, &sk);
-        } else {
-            if (out_stats) want_stats(ex, r.c2, h1, Y, &X);
-            gn_silu_conv3(ex, r.n2, r.c2, h1, Y, 1e-5f, film, &X);
+            res = &sk;
         }
+        if (!folded) p2 = plan3(r.c2, h1, Y, res);
+        if (out_stats) want_stats(ex, p2, Y);
+        gn_silu_conv3(ex, p2, r.n2, r.c2, h1, Y, eps, film, res, folded ? &r.skip : nullptr, folded ? &X : nullptr);
         ex.reset(mk);
     }
     // ldm/modules/diffusionmodules/model.py:129-149 (temb=None), GroupNorm eps 1e-6 (model.py:46-47)
-    void resnet(Exec& ex, const ResBlockW& r, const View& X, View& Y, bool out_stats = true) {
-        const size_t mk = ex.mark();
-        View h1 = ex.T(X.B, X.H, X.W, r.Cout, X.dt);
-        want_stats(ex, r.c1, X, h1, nullptr);
-        gn_silu_conv3(ex, r.n1, r.c1, X, h1, 1e-6f, nullptr, nullptr);
-        ex.tr("conv1", h1);
-        if (skip_fold(ex, r, X, h1, Y)) {
-            if (out_stats) want_stats(ex, r.c2, h1, Y, nullptr, 1, 1, 1, true);
-            gn_silu_conv3(ex, r.n2, r.c2, h1, Y, 1e-6f, nullptr, nullptr, &r.skip, &X);
-        } else if (r.has_skip) {
-            View sk = ex.T(X.B, X.H, X.W, r.Cout, X.dt);
-            conv1(ex, r.skip, X, sk);
-            if (out_stats) want_stats(ex, r.c2, h1, Y, &sk);
-            gn_silu_conv3(ex, r.n2, r.c2, h1, Y, 1e-6f, nullptr, &sk);
-        } else {
-            if (out_stats) want_stats(ex, r.c2, h1, Y, &X);
-            gn_silu_conv3(ex, r.n2, r.c2, h1, Y, 1e-6f, nullptr, &X);
-        }
-        ex.reset(mk);
-    }
+    void resnet(Exec& ex, const ResBlockW& r, const View& X, View& Y, bool out_stats = true) { resblock(ex, r, X, Y, nullptr, out_stats, 1e-6f); }
     // models/swin_transformer.py:427-442 with the two SwinTransformerBlocks (:238-281) inlined
     void basiclayer(Exec& ex, const BasicLayerW& b, const View& X, View& Y, bool out_stats = true) {
         const size_t mk = ex.mark();
         const int E = b.E, heads = cfg.unet.num_heads;
         View e = ex.T(X.B, X.H, X.W, E, X.dt);
-        want_stats(ex, b.embed, X, e, nullptr, 1, 0, 1);   // patch_embed's epilogue: statistics (+ coefficients) for the first block's norm1
-        conv1(ex, b.embed, X, e);
+        conv_st(ex, b.embed, X, e, 1, 0, 1);   // patch_embed's epilogue: statistics (+ coefficients) for the first block's norm1
         ex.tr("embed", e);
         int bi = 0;
         for (const SwinBlockW& s : b.blocks) {
@@ -1440,8 +1376,7 @@ struct rs_engine {
             ex.tr(bp + "out", e3);
             e = e3;
         }
-        if (out_stats) want_stats(ex, b.unembed, e, Y, nullptr, 1, 0, 1);
-        conv1(ex, b.unembed, e, Y);
+        conv_st(ex, b.unembed, e, Y, 1, 0, 1, nullptr, out_stats);
         ex.reset(mk);
     }
     // model.py:179-203: x + proj_out(softmax(q k^T / sqrt(C)) v); S is materialised in fp32 per image chunk
@@ -1469,8 +1404,7 @@ struct rs_engine {
                 ex.ae_flash(q.p, q.ld, k.p, k.ld, vTa, a.v.bias, o.p, o.ld, X.B, T, C, 1.0f / std::sqrt((float)C), dt);
             }
             ex.tr("o", o);
-            want_stats(ex, a.proj, o, Y, &X, 1, 0, 1);
-            conv1(ex, a.proj, o, Y, &X);
+            conv_st(ex, a.proj, o, Y, 1, 0, 1, &X);
             ex.reset(mk);
             return;
         }
@@ -1507,8 +1441,7 @@ struct rs_engine {
             }
         }
         ex.tr("o", o);
-        want_stats(ex, a.proj, o, Y, &X, 1, 0, 1);
-        conv1(ex, a.proj, o, Y, &X);
+        conv_st(ex, a.proj, o, Y, 1, 0, 1, &X);
         ex.reset(mk);
     }
     // y[z][m][n] = scale * sum_k A[z][m][k] B[z][n][k] (+bias[n])
@@ -1519,7 +1452,9 @@ struct rs_engine {
         p.x0 = A; p.w = Bm; p.bias = bias; p.y = y; p.C0 = K; p.ld0 = K; p.B = 1; p.Hs = M; p.Ws = 1; p.up = 1; p.Ho = M; p.Wo = 1;
         p.KH = 1; p.KW = 1; p.stride = 1; p.Cout = N; p.ldy = N; p.M = M; p.Ktot = K; p.out_scale = scale;
         p.bs_x0 = bsA; p.bs_w = bsB; p.bs_y = bsY;
-        ex.igemm(p, in_dt, out_dt, nz, "gemm_nt");
+        ConvPlan pl{};
+        (void)rs_conv_plan(&p, in_dt, out_dt, nz, &pl);
+        ex.igemm(p, pl, in_dt, out_dt, nz, "gemm_nt");
     }
 
     // ---------------------------------------------------------------- FiLM cache
@@ -1618,8 +1553,7 @@ struct rs_engine {
                     if (cl) ex.check(rs_nchw_to_nhwc_launch(lq_nchw, in0.p, dt, B, 3, H * W, in0.ld, Cz, 1.f, ex.st), "lq->nhwc");
                     if (cl == 4) ex.check(rs_nchw_to_nhwc_launch(mask_nchw, in0.p, dt, B, 1, H * W, in0.ld, Cz + 3, 1.f, ex.st), "mask->nhwc");
                 }
-                want_stats(ex, in_blocks[0].conv, in0, y0, nullptr);
-                conv(ex, in_blocks[0].conv, in0, nullptr, y0, 1, 1, 1, 1, 0, nullptr);
+                conv_st(ex, in_blocks[0].conv, in0, y0, 1, 1, 1);
             } else {
                 // conditioning goes through the strided-conv feature extractor (unet.py:693-702); lq_feat precomputed
                 View xin = ex.T(B, H, W, Cz, dt);
@@ -1640,8 +1574,7 @@ struct rs_engine {
             const size_t mk = ex.mark();
             View y = skip_view(i);
             if (b.has_down) {
-                want_stats(ex, b.conv, h, y, nullptr, 2, 1, 1);
-                conv(ex, b.conv, h, nullptr, y, 2, 1, 1, 1, 0, nullptr);
+                conv_st(ex, b.conv, h, y, 2, 1, 1);
                 ex.tr("in." + std::to_string(i), y);
             } else if (b.has_swin) {
                 View r = ex.T(B, h.H, h.W, b.out_ch, dt);
@@ -1721,11 +1654,11 @@ struct rs_engine {
                 }
                 if (b.has_up) {
                     if (b.has_upf && upfold_ok(ex, b.upf, cur, y)) {
-                        upfold_want_stats(ex, b.upf, cur, y);
-                        upfold_conv(ex, b.upf, cur, y);
+                        const ConvPlan pl = upfold_plan(b.upf, cur, y);
+                        upfold_want_stats(ex, pl, cur, y);
+                        upfold_conv(ex, pl, b.upf, cur, y);
                     } else {
-                        want_stats(ex, b.conv, cur, y, nullptr, 1, 1, 2);
-                        conv(ex, b.conv, cur, nullptr, y, 1, 1, 1, 2, 0, nullptr);  // nearest x2 folded into the conv's addressing
+                        conv_st(ex, b.conv, cur, y, 1, 1, 2);  // nearest x2 folded into the conv's addressing
                     }
                 }
             }
@@ -1769,8 +1702,7 @@ struct rs_engine {
         ex.pool_off = 0;
         const int B = in_nhwc.B;
         View h = ex.T(B, in_nhwc.H, in_nhwc.W, a.ch, dt);
-        want_stats(ex, enc_in, in_nhwc, h, nullptr);
-        conv(ex, enc_in, in_nhwc, nullptr, h, 1, 1, 1, 1, 0, nullptr);
+        conv_st(ex, enc_in, in_nhwc, h, 1, 1, 1);
         // debug-trace names: the blocks of oracle.resshift_oracle.ae_encode_plan, inner records under their block's prefix
         ex.tr("enc.in", h);
         auto block = [&](const std::string& nm, const ResBlockW& r, const View& x, View& y) {
@@ -1791,8 +1723,7 @@ struct rs_engine {
             if (L.has_resample) {
                 // F.pad(x,(0,1,0,1)) + conv stride 2 pad 0 (model.py:80-84)
                 View y = ex.T(B, h.H / 2, h.W / 2, h.C, dt);
-                want_stats(ex, L.resample, h, y, nullptr, 2, 0, 1);
-                conv(ex, L.resample, h, nullptr, y, 2, 0, 0, 1, 0, nullptr);
+                conv_st(ex, L.resample, h, y, 2, 0, 1);
                 ex.tr(lv + ".ds", y);
                 h = y;
             }
@@ -1860,7 +1791,7 @@ struct rs_engine {
             }
             if (L.has_resample) {
                 View y = ex.T(B, h.H * 2, h.W * 2, h.C, dt);
-                if (L.has_upf && upfold_ok(ex, L.upf, h, y)) upfold_conv(ex, L.upf, h, y);
+                if (L.has_upf && upfold_ok(ex, L.upf, h, y)) upfold_conv(ex, upfold_plan(L.upf, h, y), L.upf, h, y);
                 else conv(ex, L.resample, h, nullptr, y, 1, 1, 1, 2, 0, nullptr);
                 ex.tr(lv + ".us", y);
                 h = y;
@@ -2227,9 +2158,10 @@ int rs_profile_get(rs_engine* e, double* out) {
     return 0;
 }
 
-// per kernel family of the MFMA path, in this order: halo conv fp16 (igemm4), halo conv split, implicit GEMM fp16 (igemm2 / igemm3 /
-// igemm), implicit GEMM split, implicit GEMM fp32, fused qkv + window attention + projection, fused Swin MLP, their split-storage
-// variants, streaming AE attention:
+// per kernel family of the MFMA path, in the order of Exec::Fam: halo conv fp16 (igemm4), halo conv split, implicit GEMM fp16 (igemm2 /
+// igemm3 / igemm), implicit GEMM split, implicit GEMM fp32, fused qkv + window attention + projection, fused Swin MLP, their
+// split-storage variants, streaming AE attention and its split variant, Winograd conv (split).  A conv launch is booked under the family
+// of the kernel its plan names (ConvPlan::kernel), so the launch counts are the routing decisions:
 // out[3 f + 0] = algorithmic FLOPs, out[3 f + 1] = kernel ms (0 unless profiling was on), out[3 f + 2] = launches.  Returns the family count.
 int rs_profile_families(rs_engine* e, double* out, int cap) {
     if (!e || !out || cap < 3 * Exec::F_COUNT) return -1;
@@ -2540,6 +2472,33 @@ static void* dev_copy(const void* host, size_t bytes) {
     return d;
 }
 
+// The op-level conv entries: plan the launch (rs_conv_plan), give it its split-K slab, launch it once and - `timed` - `reps` more times
+// between two hipEvents (*ms_out = their average milliseconds), free the slab.  `halo_only`: fail unless the plan is the halo kernel's.
+static int op_conv_run(IGemmParams p, int in_prec, int out_prec, hipStream_t st, bool halo_only = false, bool timed = false, int reps = 0, float* ms_out = nullptr) {
+    ConvPlan pl{};
+    (void)rs_conv_plan(&p, in_prec, out_prec, 1, &pl);
+    if (halo_only && pl.kernel != CK_HALO && pl.kernel != CK_HALO_SEG) return fail("shape is not eligible for the halo kernel");
+    float* part = nullptr;
+    if (pl.splitk > 1) { (void)hipMalloc((void**)&part, (size_t)pl.splitk * p.M * p.Cout * sizeof(float)); p.partial = part; }
+    int rc = rs_conv_launch(&p, in_prec, out_prec, 1, &pl, st);
+    if (rc) fail("igemm launch rejected the shape");
+    else if (timed) {
+        hipEvent_t e0, e1;
+        (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+        (void)hipEventRecord(e0, st);
+        for (int i = 0; i < reps; ++i) rc |= rs_conv_launch(&p, in_prec, out_prec, 1, &pl, st);
+        (void)hipEventRecord(e1, st);
+        (void)hipEventSynchronize(e1);
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        if (ms_out) *ms_out = ms / (float)std::max(1, reps);
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    }
+    (void)hipStreamSynchronize(st);
+    if (part) (void)hipFree(part);
+    return rc;
+}
+
 int rs_op_conv2d(const void* x0, const void* x1, const float* w_ref_host, const float* bias_host, const void* res, void* y, int B, int Hs,
                  int Ws, int C0, int C1, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, int up, int act,
                  int in_prec, int out_prec, int force_direct, void* stream) {
@@ -2591,17 +2550,7 @@ int rs_op_conv2d(const void* x0, const void* x1, const float* w_ref_host, const 
         p.x0 = x0; p.x1 = x1; p.w = wdev; p.bias = bias; p.res = res; p.y = y; p.C0 = C0; p.C1 = C1; p.ld0 = C0; p.ld1 = C1;
         p.B = B; p.Hs = Hs; p.Ws = Ws; p.up = up; p.Ho = Ho; p.Wo = Wo; p.KH = KH; p.KW = KW; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
         p.Cout = Cout; p.ldy = Cout; p.ldres = Cout; p.M = B * Ho * Wo; p.Ktot = (int)K; p.act = act; p.out_scale = 1.f;
-        {
-            int tw4, bc4, seg4, sk4;   // the halo kernel plans its own split-K (as Engine::conv does)
-            if (rs_igemm4_plan(&p, in_prec, out_prec, 1, &tw4, &bc4, &seg4, &sk4)) p.splitk = sk4;
-            else p.splitk = rs_igemm_splitk_plan(p.M, Cout, (int)K, in_prec);
-        }
-        float* part = nullptr;
-        if (p.splitk > 1) { (void)hipMalloc((void**)&part, (size_t)p.splitk * p.M * Cout * sizeof(float)); p.partial = part; }
-        rc = rs_igemm_launch(&p, in_prec, out_prec, 1, st);
-        if (rc) fail("igemm launch rejected the shape");
-        (void)hipStreamSynchronize(st);
-        if (part) (void)hipFree(part);
+        rc = op_conv_run(p, in_prec, out_prec, st);
     }
     (void)hipStreamSynchronize(st);
     if (wdev) (void)hipFree(wdev);
@@ -2619,27 +2568,7 @@ int rs_op_conv2d_bench(const void* x0, const void* w_packed_dev, const float* bi
     p.x0 = x0; p.w = w_packed_dev; p.bias = bias_dev; p.res = res; p.y = y; p.C0 = Cin; p.ld0 = Cin;
     p.B = B; p.Hs = Hs; p.Ws = Ws; p.up = up; p.Ho = Ho; p.Wo = Wo; p.KH = KH; p.KW = KW; p.stride = stride; p.pad_t = pad; p.pad_l = pad;
     p.Cout = Cout; p.ldy = Cout; p.ldres = Cout; p.M = B * Ho * Wo; p.Ktot = KH * KW * Cin; p.act = act; p.out_scale = 1.f;
-    {
-        int tw4, bc4, seg4, sk4;
-        if (rs_igemm4_plan(&p, in_prec, out_prec, 1, &tw4, &bc4, &seg4, &sk4)) p.splitk = sk4;
-        else p.splitk = rs_igemm_splitk_plan(p.M, Cout, p.Ktot, in_prec);
-    }
-    float* part = nullptr;
-    if (p.splitk > 1) { (void)hipMalloc((void**)&part, (size_t)p.splitk * p.M * Cout * sizeof(float)); p.partial = part; }
-    int rc = rs_igemm_launch(&p, in_prec, out_prec, 1, st);  // warm-up
-    if (rc) return fail("igemm launch rejected the shape");
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, st);
-    for (int i = 0; i < reps; ++i) rc |= rs_igemm_launch(&p, in_prec, out_prec, 1, st);
-    (void)hipEventRecord(e1, st);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    if (ms_out) *ms_out = ms / (float)std::max(1, reps);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (part) (void)hipFree(part);
-    return rc;
+    return op_conv_run(p, in_prec, out_prec, st, false, true, reps, ms_out);
 }
 
 // GroupNorm-affine + SiLU + 3x3 conv on the halo kernel (igemm4.hip): x raw fp16 NHWC, coef_dev [B][2][Cin] fp32 (scale row,
@@ -2667,17 +2596,8 @@ int rs_op_conv3x3_halo(const void* x, const float* coef_dev, int act_in, const f
     p.x0 = x; p.w = wdev; p.bias = bias; p.res = res; p.y = y; p.C0 = Cin; p.ld0 = Cin; p.B = B; p.Hs = H; p.Ws = W; p.up = 1; p.Ho = H; p.Wo = W;
     p.KH = 3; p.KW = 3; p.stride = 1; p.pad_t = 1; p.pad_l = 1; p.Cout = Cout; p.ldy = Cout; p.ldres = Cout; p.M = B * H * W; p.Ktot = (int)K;
     p.out_scale = 1.f; p.splitk = 1; p.xcoef = coef_dev; p.xact = act_in;
-    int tw, bc, seg, sk, rc;
-    float* part = nullptr;
-    if (!rs_igemm4_plan(&p, prec, prec, 1, &tw, &bc, &seg, &sk)) rc = fail("shape is not eligible for the halo kernel");
-    else {
-        p.splitk = sk;
-        if (sk > 1) { (void)hipMalloc((void**)&part, (size_t)sk * p.M * Cout * sizeof(float)); p.partial = part; }
-        p.ystats = ystats_dev; p.ystats_ld = Cout;
-        rc = rs_igemm_launch(&p, prec, prec, 1, st);
-    }
-    (void)hipStreamSynchronize(st);
-    if (part) (void)hipFree(part);
+    p.ystats = ystats_dev; p.ystats_ld = Cout;
+    const int rc = op_conv_run(p, prec, prec, st, true);
     if (wdev) (void)hipFree(wdev);
     if (bias) (void)hipFree(bias);
     return rc;
@@ -2705,9 +2625,11 @@ int rs_op_conv3x3_wino(const void* x, const float* coef_dev, int act_in, const f
     p.dbg = 64;   // (an op-level entry: no fill-the-chip threshold)
     if (const char* ab = getenv("RS_WINO_ABL")) p.dbg |= atoi(ab);   // (-DRS_WINO_PHASES builds: timing ablations, wino.hip)
     if (getenv("RS_WINO_STAMPS")) { (void)hipMalloc((void**)&stamps, (size_t)ntile * 16 * sizeof(float)); (void)hipMemset(stamps, 0, (size_t)ntile * 16 * sizeof(float)); p.partial = stamps; }
-    if (!rs_wino_plan(&p, RS_F16S, RS_F16S, 1)) rc = fail("shape is not eligible for the wino kernel");
+    ConvPlan pl{};
+    (void)rs_conv_plan(&p, RS_F16S, RS_F16S, 1, &pl);
+    if (pl.kernel != CK_WINO) rc = fail("shape is not eligible for the wino kernel");
     else {
-        rc = rs_wino_launch(&p, st);
+        rc = rs_conv_launch(&p, RS_F16S, RS_F16S, 1, &pl, st);
         if (rc) fail("wino launch failed");
         if (stamps) {
             (void)hipStreamSynchronize(st);
@@ -2730,7 +2652,7 @@ int rs_op_conv3x3_wino(const void* x, const float* coef_dev, int act_in, const f
             hipEvent_t e0, e1;
             (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
             (void)hipEventRecord(e0, st);
-            for (int i = 0; i < reps; ++i) rc |= rs_wino_launch(&p, st);
+            for (int i = 0; i < reps; ++i) rc |= rs_conv_launch(&p, RS_F16S, RS_F16S, 1, &pl, st);
             (void)hipEventRecord(e1, st);
             (void)hipEventSynchronize(e1);
             float ms = 0.f;
@@ -2752,7 +2674,9 @@ int rs_op_conv3x3_halo_stats_px(int B, int H, int W, int Cin, int Cout, int prec
     IGemmParams p{};
     p.C0 = Cin; p.ld0 = Cin; p.B = B; p.Hs = H; p.Ws = W; p.up = 1; p.Ho = H; p.Wo = W;
     p.KH = 3; p.KW = 3; p.stride = 1; p.pad_t = 1; p.pad_l = 1; p.Cout = Cout; p.ldy = Cout; p.ldres = Cout; p.M = B * H * W; p.Ktot = 9 * Cin;
-    return rs_igemm4_stats_px(&p, prec);
+    ConvPlan pl{};
+    (void)rs_conv_plan(&p, prec, prec, 1, &pl);
+    return (pl.kernel == CK_HALO || pl.kernel == CK_HALO_SEG) ? pl.stats_px : 0;
 }
 
 int rs_op_gemm_nt(const void* a, const void* b, const float* bias_dev, void* y, int nz, int M, int N, int K, float scale, int in_prec,
@@ -2761,7 +2685,9 @@ int rs_op_gemm_nt(const void* a, const void* b, const float* bias_dev, void* y, 
     p.x0 = a; p.w = b; p.bias = bias_dev; p.y = y; p.C0 = K; p.ld0 = K; p.B = 1; p.Hs = M; p.Ws = 1; p.up = 1; p.Ho = M; p.Wo = 1;
     p.KH = 1; p.KW = 1; p.stride = 1; p.Cout = N; p.ldy = N; p.M = M; p.Ktot = K; p.out_scale = scale;
     p.bs_x0 = (long long)M * K; p.bs_w = (long long)N * K; p.bs_y = (long long)M * N;
-    const int rc = rs_igemm_launch(&p, in_prec, out_prec, nz, (hipStream_t)stream);
+    ConvPlan pl{};
+    (void)rs_conv_plan(&p, in_prec, out_prec, nz, &pl);
+    const int rc = rs_conv_launch(&p, in_prec, out_prec, nz, &pl, (hipStream_t)stream);
     if (rc) fail("igemm launch rejected the shape");
     return rc;
 }

@@ -348,9 +348,7 @@ hipError_t launch_cfg(const IGemmParams& p, int nz, hipStream_t st) {
 }
 
 template <typename TI, typename TO>
-hipError_t launch_t(const IGemmParams& p, int nz, hipStream_t st) {
-    int BP, BC;
-    pick_tile(p.M, p.Cout, BP, BC);
+hipError_t launch_t(const IGemmParams& p, int BP, int BC, int nz, hipStream_t st) {
     const bool small_m = BP == 64;
     switch (BC) {
         case 64: return small_m ? launch_cfg<TI, TO, 64, 64>(p, nz, st) : launch_cfg<TI, TO, 128, 64>(p, nz, st);
@@ -362,16 +360,18 @@ hipError_t launch_t(const IGemmParams& p, int nz, hipStream_t st) {
 
 }  // namespace
 
+// per-kernel eligibility / tile rules (next to their kernels) and launchers: used by rs_conv_plan / rs_conv_launch below, nowhere else
 extern "C" int rs_igemm2_pick(int M, int Cout, int Kbytes, int nz, int* BP, int* BC);
+extern "C" int rs_igemm2_tile_px(int BP);
 extern "C" int rs_igemm2_launch(const IGemmParams* pp, int in_dt, int out_dt, int BP, int BC, int nz, hipStream_t st);
 extern "C" int rs_igemm3_pick(int M, int Cout, int Ktot, int in_dt, int nz, int splitk, int* BC);
 extern "C" int rs_igemm3_launch(const IGemmParams* pp, int out_dt, int BC, hipStream_t st);
-extern "C" int rs_igemm4_pick(const IGemmParams* pp, int in_dt, int out_dt, int nz, int* TW, int* BC);
-extern "C" int rs_igemm4_launch(const IGemmParams* pp, int in_dt, int TW, int BC, hipStream_t st);
-extern "C" int rs_wino_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz);
+extern "C" int rs_igemm4_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz, ConvPlan* pl);
+extern "C" int rs_igemm4_launch(const IGemmParams* pp, int in_dt, const ConvPlan* pl, hipStream_t st);
+extern "C" int rs_wino_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz, ConvPlan* pl);
 extern "C" int rs_wino_launch(const IGemmParams* pp, hipStream_t st);
-extern "C" void rs_igemm_split_pick(int M, int Cout, int nz, int* BP, int* BC);
-extern "C" int rs_igemm_split_launch(const IGemmParams* pp, int out_dt, int nz, hipStream_t st);
+extern "C" void rs_igemm_split_plan(const IGemmParams* pp, int out_dt, int nz, int can_split, ConvPlan* pl);
+extern "C" int rs_igemm_split_launch(const IGemmParams* pp, int out_dt, int nz, const ConvPlan* pl, hipStream_t st);
 
 extern "C" int rs_splitk_reduce_launch(const IGemmParams* pp, int out_dt, hipStream_t st) {
     const IGemmParams& p = *pp;
@@ -383,70 +383,79 @@ extern "C" int rs_splitk_reduce_launch(const IGemmParams* pp, int out_dt, hipStr
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// Split-K planner: returns the number of K slices (1 = no split) for a single (non-batched) launch.  The caller owns the
-// fp32 workspace of splitk * M * Cout floats (IGemmParams::partial).
-extern "C" int rs_igemm_splitk_plan(int M, int Cout, int Ktot, int in_dt) {
-    int BP, BC;
-    if (in_dt == RS_F16S) {   // split storage (igemm_split.hip): one workgroup per CU, so aim at one round of workgroups
-        rs_igemm_split_pick(M, Cout, 1, &BP, &BC);
-        const int tiles = ((M + BP - 1) / BP) * ((Cout + BC - 1) / BC);
-        const int nk = (Ktot + 63) / 64;
-        if (tiles >= 200 || nk < 16 || (Cout & 3)) return 1;
-        int s = std::min((256 + tiles - 1) / tiles, 16);
-        s = std::min(s, nk / 8);
-        return std::max(s, 1);
-    }
-    pick_tile(M, Cout, BP, BC);
-    if (Cout > 64) {          // igemm2 takes every single-source launch with more than 64 channels: ask it for its tile
-        int bp2 = 0, bc2 = 0;
-        if (rs_igemm2_pick(M, Cout, Ktot * (in_dt == RS_F16 ? 2 : 4), 1, &bp2, &bc2)) { BP = bp2 == 133 ? 64 : (bp2 == 256 || bp2 == 131) ? 256 : 128; BC = bc2; }
-    }
-    const int tiles = ((M + BP - 1) / BP) * ((Cout + BC - 1) / BC);
-    const int bk = in_dt == RS_F16 ? 64 : 32;
-    const int nk = (Ktot + bk - 1) / bk;
-    if (tiles >= (BP == 64 ? 400 : 200) || nk < 16 || (Cout & 3)) return 1;
-    // aim at ~3 workgroups per CU, keep >= 6 K stages per slice (RS_SPLITK_TARGET / RS_SPLITK_MINSTAGES override for tuning)
-    static const int target = []() { const char* e = getenv("RS_SPLITK_TARGET"); return e ? atoi(e) : 512; }();
-    static const int minst = []() { const char* e = getenv("RS_SPLITK_MINSTAGES"); return e ? atoi(e) : 8; }();
-    int s = (target + tiles - 1) / tiles;
-    s = std::min(s, 16);
-    s = std::min(s, nk / minst);
-    return std::max(s, 1);
-}
-
+// THE decision which kernel runs a launch, and how (ConvPlan, common.h): every caller plans a launch once with this function and hands
+// the plan to rs_conv_launch; nothing else picks a kernel, a tile or a split-K factor.  Returns 0, or -2 (plan.kernel = CK_NONE) when no
+// kernel takes the launch.
 // in_dt: storage type of x/w; out_dt: storage type of y/res.  Supported: (F16,F16) (F16,F32) (F32,F32) (F16S,F16S) (F16S,F32).
-// Requirements: (C0+C1) and C0 multiples of the 16-byte chunk (8 halfs / 4 floats); ld0/ld1 likewise;
-// source base pointers 16-byte aligned.  p.splitk > 1 requires nz == 1 and p.partial.
-extern "C" int rs_igemm_launch(const IGemmParams* pp, int in_dt, int out_dt, int nz, hipStream_t st) {
-    IGemmParams p = *pp;
+// Requirements: (C0+C1) and C0 multiples of the 16-byte chunk (8 halfs / 4 floats); ld0/ld1 likewise.
+// Order: the Winograd kernel (wino.hip), the halo kernel with its own split-K and tile geometry (igemm4.hip), split storage
+// (igemm_split.hip), then igemm3 / igemm2 / igemm with the generic split-K factor.  Split-K (fp32 slabs in IGemmParams::partial, owned by
+// the caller) is planned for single launches only: not for batched GEMMs (nz > 1 or batch strides set) nor for scattered rows.
+extern "C" int rs_conv_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz, ConvPlan* pl) {
+    const IGemmParams& p = *pp;
+    *pl = ConvPlan{CK_NONE, 0, 0, 0, 1, 0};
     const int ch = in_dt == RS_F32 ? 4 : 8;
     if ((p.C0 % ch) || (p.C1 % ch) || (p.ld0 % ch) || (p.C1 && (p.ld1 % ch)) || p.M <= 0 || p.Cout <= 0) return -2;
     if (p.up != 1 && p.up != 2) return -2;
-    if (p.splitk < 1) p.splitk = 1;
-    if (p.splitk > 1 && (nz != 1 || !p.partial || (p.Cout & 3))) return -2;
     // scattered rows (sub-pixel form of an upsampling conv, IGemmParams::osc): plain single launches only - the residual, the output
     // statistics and the split-K slabs are all indexed by the GEMM row
     // (output statistics: the split-storage kernel only - its four launches fill one slab array and share the GroupNorm tail's ticket)
-    if (p.osc != 0 && p.osc != 1 && (p.osc != 2 || p.res || (p.ystats && in_dt != RS_F16S) || p.splitk > 1 || nz != 1 || p.up != 1 || p.stride != 1 || p.C1 != 0)) return -2;
-    // Winograd F(2x2,3x3) kernel (split storage, big planes; carries the halo kernel's input transform / statistics / tail): wino.hip
-    if (rs_wino_plan(&p, in_dt, out_dt, nz)) return rs_wino_launch(&p, st);
-    {   // halo-tile kernel (3x3 stride-1 convs, optional fused GroupNorm affine + SiLU on the input): igemm4.hip
-        int tw4 = 0, bc4 = 0;
-        if (rs_igemm4_pick(&p, in_dt, out_dt, nz, &tw4, &bc4)) return rs_igemm4_launch(&p, in_dt, tw4, bc4, st);
-        if (p.xcoef || p.sx) return -2;   // only the halo kernel applies an input transform / carries a folded shortcut: the caller must ask rs_igemm4_pick first
+    if (p.osc != 0 && p.osc != 1 && (p.osc != 2 || p.res || nz != 1 || p.up != 1 || p.stride != 1 || p.C1 != 0)) return -2;
+    // Winograd F(2x2,3x3) kernel (split storage, big planes; carries the halo kernel's input transform / statistics / tail)
+    if (rs_wino_plan(&p, in_dt, out_dt, nz, pl)) return 0;
+    // halo-tile kernel (3x3 stride-1 convs, optional fused GroupNorm affine + SiLU on the input)
+    if (rs_igemm4_plan(&p, in_dt, out_dt, nz, pl)) return 0;
+    if (p.sC) return -2;   // only the halo kernel carries a folded shortcut
+    const int can_split = nz == 1 && p.osc != 2 && p.bs_y == 0;
+    if (in_dt == RS_F16S) {   // split storage: single source
+        if (p.C1 != 0 || (out_dt != RS_F16S && out_dt != RS_F32)) return -2;
+        rs_igemm_split_plan(&p, out_dt, nz, can_split, pl);
+        return 0;
     }
-    if (in_dt == RS_F16S) return rs_igemm_split_launch(&p, out_dt, nz, st);   // split storage: igemm_split.hip (single source)
+    if (!(in_dt == RS_F16 && (out_dt == RS_F16 || out_dt == RS_F32)) && !(in_dt == RS_F32 && out_dt == RS_F32)) return -2;
     // second-generation kernel (LDS-DMA ring) for everything that fills the chip; RS_IGEMM_V2=0 forces the first one
     static const bool use_v2 = []() { const char* e = getenv("RS_IGEMM_V2"); return !(e && e[0] == '0'); }();
-    int bp2 = 0, bc2 = 0;
+    const bool v2 = use_v2 && p.C1 == 0;
+    const int kbytes = p.Ktot * (in_dt == RS_F16 ? 2 : 4);
+    int BP, BC, bp2 = 0, bc2 = 0, bc3 = 0, sk = 1;
+    pick_tile(p.M, p.Cout, BP, BC);
+    if (can_split) {   // the tile a single launch will run on: igemm2's wherever it takes the launch (every one with more than 64 channels)
+        const bool on2 = v2 && rs_igemm2_pick(p.M, p.Cout, kbytes, 1, &bp2, &bc2);
+        const int px = on2 ? rs_igemm2_tile_px(bp2) : BP, bc = on2 ? bc2 : BC;
+        const int tiles = ((p.M + px - 1) / px) * ((p.Cout + bc - 1) / bc);
+        const int bk = in_dt == RS_F16 ? 64 : 32;
+        const int nk = (p.Ktot + bk - 1) / bk;
+        // aim at ~3 workgroups per CU, keep >= 6 K stages per slice (RS_SPLITK_TARGET / RS_SPLITK_MINSTAGES override for tuning)
+        static const int target = []() { const char* e = getenv("RS_SPLITK_TARGET"); return e ? atoi(e) : 512; }();
+        static const int minst = []() { const char* e = getenv("RS_SPLITK_MINSTAGES"); return e ? atoi(e) : 8; }();
+        if (tiles < (px == 64 ? 400 : 200) && nk >= 16 && !(p.Cout & 3)) sk = std::max(1, std::min(std::min((target + tiles - 1) / tiles, 16), nk / minst));
+    }
     // third generation (256-pixel tiles, one workgroup per CU, register-pipelined fragments) for the long-K fp16 layers that fill the chip
-    int bc3 = 0;
-    if (use_v2 && p.C1 == 0 && (out_dt == RS_F16 || out_dt == RS_F32) && rs_igemm3_pick(p.M, p.Cout, p.Ktot, in_dt, nz, p.splitk, &bc3)) return rs_igemm3_launch(&p, out_dt, bc3, st);
-    if (use_v2 && p.C1 == 0 && rs_igemm2_pick(p.M, p.Cout, p.Ktot * (in_dt == RS_F16 ? 2 : 4), nz * p.splitk, &bp2, &bc2)) return rs_igemm2_launch(&p, in_dt, out_dt, bp2, bc2, nz, st);
+    if (v2 && rs_igemm3_pick(p.M, p.Cout, p.Ktot, in_dt, nz, sk, &bc3)) *pl = ConvPlan{CK_IGEMM3, 256, bc3, 0, sk, 0};
+    else if (v2 && rs_igemm2_pick(p.M, p.Cout, kbytes, nz * sk, &bp2, &bc2)) *pl = ConvPlan{CK_IGEMM2, bp2, bc2, 0, sk, 0};
+    else *pl = ConvPlan{CK_IGEMM, BP, BC, 0, sk, 0};
+    return 0;
+}
+
+// Executes a plan: only the checks that need the real pointers are left (the kernels' base alignments in their own launchers).
+// Source base pointers 16-byte aligned.  plan.splitk > 1 requires p.partial.
+extern "C" int rs_conv_launch(const IGemmParams* pp, int in_dt, int out_dt, int nz, const ConvPlan* pl, hipStream_t st) {
+    IGemmParams p = *pp;
+    p.splitk = pl->splitk;
+    if (pl->kernel == CK_NONE || (p.splitk > 1 && !p.partial)) return -2;
+    if (p.ystats && !pl->stats_px) return -2;                  // this kernel cannot leave output statistics
+    if (p.xcoef && pl->kernel > CK_HALO_SEG) return -2;        // only the Winograd and halo kernels apply an input transform
     hipError_t e;
-    if (in_dt == RS_F16 && out_dt == RS_F16) e = launch_t<f16, f16>(p, nz, st);
-    else if (in_dt == RS_F16 && out_dt == RS_F32) e = launch_t<f16, float>(p, nz, st);
-    else if (in_dt == RS_F32 && out_dt == RS_F32) e = launch_t<float, float>(p, nz, st);
-    else return -2;
+    switch (pl->kernel) {
+        case CK_WINO: return rs_wino_launch(&p, st);
+        case CK_HALO: case CK_HALO_SEG: return rs_igemm4_launch(&p, in_dt, pl, st);
+        case CK_SPLIT: return rs_igemm_split_launch(&p, out_dt, nz, pl, st);
+        case CK_IGEMM3: return rs_igemm3_launch(&p, out_dt, pl->BC, st);
+        case CK_IGEMM2: return rs_igemm2_launch(&p, in_dt, out_dt, pl->BP, pl->BC, nz, st);
+        default: break;
+    }
+    if (in_dt == RS_F16 && out_dt == RS_F16) e = launch_t<f16, f16>(p, pl->BP, pl->BC, nz, st);
+    else if (in_dt == RS_F16 && out_dt == RS_F32) e = launch_t<f16, float>(p, pl->BP, pl->BC, nz, st);
+    else e = launch_t<float, float>(p, pl->BP, pl->BC, nz, st);
     return e == hipSuccess ? 0 : -1;
 }

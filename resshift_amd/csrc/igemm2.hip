@@ -534,6 +534,9 @@ extern "C" int rs_igemm2_pick(int M, int Cout, int Kbytes, int nz, int* BP, int*
     return 1;
 }
 
+// pixels per tile of the variant code rs_igemm2_pick returns in *BP (launch2_t)
+extern "C" int rs_igemm2_tile_px(int BP) { return BP == 133 ? 64 : (BP == 256 || BP == 131) ? 256 : 128; }
+
 extern "C" int rs_igemm2_launch(const IGemmParams* pp, int in_dt, int out_dt, int BP, int BC, int nz, hipStream_t st) {
     const IGemmParams& p = *pp;
     hipError_t e;

@@ -120,8 +120,8 @@ extern "C" int rs_splitk_reduce_stats_launch(const IGemmParams* p, int out_dt, h
 // the small planes of the 16 x 16 / 8 x 8 UNet levels (SEG = 16: one 16 x 16 image per tile; SEG = 8: four 8 x 8 images per tile, batch
 // a multiple of 4) with split-K over stages chosen so that tiles x slices fill the chip once (SK).  RS_IGEMM_V4=0 disables the kernel
 // (1: fp16 only, 2: split only); RS_IGEMM_V4_SEG=0 keeps the small planes on the generic kernels (A/B runs).
-// *SEG carries the tile variant: 0 = 256-pixel tiles on 8 waves, 8 / 16 = the small-plane geometries.
-extern "C" int rs_igemm4_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz, int* TW, int* BC, int* SEG, int* SK) {
+// Fills the plan (kernel, TW in BP, BC, SEG, splitk, stats_px) and returns 1, or returns 0: not a halo-kernel launch.  Called by rs_conv_plan only.
+extern "C" int rs_igemm4_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz, ConvPlan* pl) {
     static const int on = []() { const char* e = getenv("RS_IGEMM_V4"); return e ? atoi(e) : 3; }();
     // bit 0: fp16, bit 1: split storage, bit 2: the 16 x 16 planes as well.  Default 2 = the 8 x 8 planes in split storage - measured
     // (profiles/r3_small_planes.txt, us per launch at batch 32, generic kernel -> halo kernel): split 8 x 8, 640 -> 640: 96 -> 62, 1280 ->
@@ -133,12 +133,11 @@ extern "C" int rs_igemm4_plan(const IGemmParams* pp, int in_dt, int out_dt, int 
     static const int sk_target = []() { const char* e = getenv("RS_IGEMM_V4_SKTARGET"); return e ? atoi(e) : 256; }();
     static const int sk_minst = []() { const char* e = getenv("RS_IGEMM_V4_SKMINSTAGES"); return e ? atoi(e) : 6; }();
     const IGemmParams& p = *pp;
-    if (in_dt != out_dt || nz != 1 || p.C1 != 0 || p.no_halo) return 0;
+    if (in_dt != out_dt || nz != 1 || p.C1 != 0 || p.unscaled_w) return 0;
     if (!((in_dt == RS_F16 && (on & 1)) || (in_dt == RS_F16S && (on & 2)))) return 0;
     if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad_t != 1 || p.pad_l != 1 || p.up != 1 || p.Ho != p.Hs || p.Wo != p.Ws) return 0;
     // (fp16 storage fetches the residual as 16-byte row pieces: 8-channel alignment of its stride; the BASE alignment is checked at launch -
-    // eligibility must be a function of the layout alone, never of a pointer value: the engine asks this planner in its dry sizing pass, in
-    // want_stats and again at launch, and the three answers have to agree)
+    // a plan is a function of the layout alone, never of a pointer value: see ConvPlan)
     if ((p.C0 % 32) || (p.ld0 % 8) || (p.Cout % 8) || (p.ldy % 8) || (p.res && (p.ldres % 8))) return 0;
     auto waste = [&](int bc) { return ((p.Cout + bc - 1) / bc) * bc - p.Cout; };
     int best = 128, bw = waste(128);
@@ -160,7 +159,10 @@ extern "C" int rs_igemm4_plan(const IGemmParams* pp, int in_dt, int out_dt, int 
             const int per = (nst + sk - 1) / sk;
             sk = (nst + per - 1) / per;   // no empty slice
         }
-        *TW = 32; *BC = best; *SEG = seg; *SK = sk;
+        // statistics: a split-K launch's reduce kernel produces them per 256 consecutive pixels / whole small image; the tile epilogue of
+        // the 8 x 8 geometry (four images per tile) cannot
+        const int HW = p.Ho * p.Wo;
+        *pl = ConvPlan{CK_HALO_SEG, 32, best, seg, sk, sk > 1 ? std::min(HW, 256) : (seg == 8 ? 0 : 256)};
         return 1;
     }
     if (waste(192) < bw) { best = 192; bw = waste(192); }
@@ -174,21 +176,13 @@ extern "C" int rs_igemm4_plan(const IGemmParams* pp, int in_dt, int out_dt, int 
     if (p.Cout < 96 || (in_dt == RS_F16S && best == 192)) return 0;   // (split, BC = 192: over the register budget; no 3x3 conv of the models needs it)
     const long long tiles = (long long)p.B * (p.Ho / th) * (p.Wo / tw) * ((p.Cout + best - 1) / best);
     if (tiles < min_tiles) return 0;
-    *TW = tw; *BC = best; *SEG = 0; *SK = 1;
+    *pl = ConvPlan{CK_HALO, tw, best, 0, 1, 256};   // (statistics: one slab per 256-pixel tile)
     return 1;
 }
 
-// launch-time view of the plan: the parameter block must carry the plan's split-K factor (the engine asks rs_igemm4_plan first and
-// sizes IGemmParams::partial for it); a block with another split-K factor is not a halo-kernel launch
-extern "C" int rs_igemm4_pick(const IGemmParams* pp, int in_dt, int out_dt, int nz, int* TW, int* BC) {
-    int seg = 0, sk = 1;
-    if (!rs_igemm4_plan(pp, in_dt, out_dt, nz, TW, BC, &seg, &sk)) return 0;
-    return (pp->splitk > 1 ? pp->splitk : 1) == sk ? 1 : 0;
-}
-
-extern "C" int rs_igemm4_launch(const IGemmParams* pp, int in_dt, int TW, int BC, hipStream_t st) {
-    int tw = 0, bc = 0, seg = 0, sk = 1;
-    if (!rs_igemm4_plan(pp, in_dt, in_dt, 1, &tw, &bc, &seg, &sk) || tw != TW || bc != BC || (pp->splitk > 1 ? pp->splitk : 1) != sk) return -2;
+// executes a CK_HALO / CK_HALO_SEG plan: only the checks that need the real pointers are left
+extern "C" int rs_igemm4_launch(const IGemmParams* pp, int in_dt, const ConvPlan* pl, hipStream_t st) {
+    const int TW = pl->BP, BC = pl->BC, seg = pl->SEG, sk = pl->splitk;
     if (sk > 1 && !pp->partial) return -2;
     if (((size_t)pp->x0 & 15) || ((size_t)pp->y & 15) || ((size_t)pp->res & 15)) return -2;   // 16-byte row pieces: a view whose channel offset is not a multiple of 8
     IGemmParams p = *pp;
@@ -196,22 +190,10 @@ extern "C" int rs_igemm4_launch(const IGemmParams* pp, int in_dt, int TW, int BC
     const GNTail want_tail = p.tail;
     if (want_tail.coef && !want_stats) return -2;   // a tail finishes statistics this launch produces
     if (sk > 1) { p.ystats = nullptr; p.tail.coef = nullptr; }   // slices cannot see the final values: the reduce kernel produces the statistics (and carries the tail)
-    if (seg == 8 && want_stats && sk == 1) return -2;   // four images per tile: no per-image statistics from the tile epilogue
     int rc;
     if (seg) rc = rs_igemm4_seg_launch(&p, in_dt, seg, BC, st);
     else rc = (in_dt == RS_F16S ? launch4_t<true>(p, TW, BC, st) : launch4_t<false>(p, TW, BC, st)) == hipSuccess ? 0 : -1;
     if (rc != 0 || sk == 1) return rc;
     p.ystats = want_stats; p.tail = want_tail;
     return want_stats ? reduce_stats_launch(p, in_dt, st) : rs_splitk_reduce_launch(&p, in_dt, st);
-}
-
-// pixels per statistics slab of a halo-kernel launch that is asked for IGemmParams::ystats (0: this launch cannot produce them): the tile
-// of the kernel variant, or - for split-K launches, whose reduce kernel produces them - 256 consecutive pixels / the whole small image
-extern "C" int rs_igemm4_stats_px(const IGemmParams* pp, int in_dt) {
-    int tw = 0, bc = 0, seg = 0, sk = 1;
-    if (!rs_igemm4_plan(pp, in_dt, in_dt, 1, &tw, &bc, &seg, &sk)) return 0;
-    const int HW = pp->Ho * pp->Wo;
-    if (sk > 1) return (HW > 256 && (HW % 256)) ? 0 : std::min(HW, 256);
-    if (seg == 8) return 0;
-    return 256;
 }

@@ -530,7 +530,7 @@ hipError_t launch_cfg2(IGemmParams p, int nz, hipStream_t st) {
         if (!std::is_same<TO, h2s>::value || nz != 1) return hipErrorInvalidValue;
         if (p.splitk > 1) { p.ystats = nullptr; p.tail.coef = nullptr; }
         else {
-            if ((p.M % BP) || (hw % BP)) return hipErrorInvalidValue;   // whole tiles inside one image (rs_igemm_split_stats_px)
+            if ((p.M % BP) || (hw % BP)) return hipErrorInvalidValue;   // whole tiles inside one image (ConvPlan::stats_px)
             if (p.tail.coef) {
                 if (p.tail.C > 2048 || p.tail.groups < 1 || p.tail.groups > 64 || (p.tail.C % p.tail.groups)) return hipErrorInvalidValue;   // (the finish's LDS scratch: 2 C + 2 groups floats)
                 const int classes = p.osc == 2 ? 4 : 1;   // (scattered launches: the four parity classes share one ticket and one slab array)
@@ -587,7 +587,7 @@ hipError_t launch_t(const IGemmParams& p, int BP, int BC, int nz, hipStream_t st
 
 // tile choice: channel tile with the least padding (64 for the 3-channel heads), 64-pixel tiles on 4 waves where 128-pixel
 // tiles would leave most CUs idle (the 16x16 / 8x8 UNet levels at batch 32: M <= 8192)
-extern "C" void rs_igemm_split_pick(int M, int Cout, int nz, int* BP, int* BC) {
+static void split_pick(int M, int Cout, int nz, int* BP, int* BC) {
     auto waste = [&](int bc) { return ((Cout + bc - 1) / bc) * bc - Cout; };
     int best = 128, bw = waste(128);
     if (waste(160) < bw) { best = 160; bw = waste(160); }
@@ -604,16 +604,22 @@ extern "C" void rs_igemm_split_pick(int M, int Cout, int nz, int* BP, int* BC) {
     if (bp128_min > 0 && nz == 1 && tiles128 >= bp128_min) *BP = 128;
 }
 
-// pixels per statistics slab of an igemm_split launch that is asked for IGemmParams::ystats (0: it cannot produce them): the pixel tile,
-// or - split-K launches, whose reduce kernel produces them - 256 consecutive pixels / the whole small image (as rs_igemm4_stats_px)
-extern "C" int rs_igemm_split_stats_px(const IGemmParams* pp, int splitk) {
+// The split-storage plan (called by rs_conv_plan only): the tile above; split-K (`can_split`) - one workgroup per CU, so aim at one round of
+// workgroups; pixels per statistics slab (0: none) - the pixel tile when whole tiles lie inside one image, or, for split-K launches,
+// whose reduce kernel produces the statistics, 256 consecutive pixels / the whole small image (as the halo kernel's).
+extern "C" void rs_igemm_split_plan(const IGemmParams* pp, int out_dt, int nz, int can_split, ConvPlan* pl) {
     const IGemmParams& p = *pp;
-    if (p.C1 != 0 || (p.Cout & 3) || (p.ldy & 3)) return 0;
+    int BP, BC, sk = 1;
+    split_pick(p.M, p.Cout, nz, &BP, &BC);
+    const int tiles = ((p.M + BP - 1) / BP) * ((p.Cout + BC - 1) / BC), nk = (p.Ktot + 63) / 64;
+    if (can_split && tiles < 200 && nk >= 16 && !(p.Cout & 3)) sk = std::max(1, std::min(std::min((256 + tiles - 1) / tiles, 16), nk / 8));
     const int hw = p.Ho * p.Wo;
-    if (splitk > 1) return (hw > 256 && (hw % 256)) ? 0 : std::min(hw, 256);
-    int BP, BC;
-    rs_igemm_split_pick(p.M, p.Cout, 1, &BP, &BC);
-    return ((p.M % BP) || (hw % BP)) ? 0 : BP;
+    int spx = 0;
+    if (out_dt == RS_F16S && nz == 1 && !(p.Cout & 3) && !(p.ldy & 3)) {
+        if (sk > 1) spx = (hw > 256 && (hw % 256)) ? 0 : std::min(hw, 256);
+        else spx = ((p.M % BP) || (hw % BP)) ? 0 : BP;
+    }
+    *pl = ConvPlan{CK_SPLIT, BP, BC, 0, sk, spx};
 }
 
 // in: split storage; out_dt: RS_F16S or RS_F32.  Single source only (C1 == 0), C0 / ld0 / Ktot multiples of 8.
@@ -631,14 +637,11 @@ extern "C" int rs_igemm_split_phase_cycles(int nwg, double* out3) {
 }
 #endif
 
-extern "C" int rs_igemm_split_launch(const IGemmParams* pp, int out_dt, int nz, hipStream_t st) {
+extern "C" int rs_igemm_split_launch(const IGemmParams* pp, int out_dt, int nz, const ConvPlan* pl, hipStream_t st) {
     const IGemmParams& p = *pp;
-    if (p.C1 != 0 || (p.C0 % 8) || (p.ld0 % 8) || (p.Ktot % 8)) return -2;
-    int BP, BC;
-    rs_igemm_split_pick(p.M, p.Cout, nz, &BP, &BC);   // (same arguments as the split-K planner: identical tile choice)
     hipError_t e;
-    if (out_dt == RS_F16S) e = launch_t<h2s>(p, BP, BC, nz, st);
-    else if (out_dt == RS_F32) e = launch_t<float>(p, BP, BC, nz, st);
+    if (out_dt == RS_F16S) e = launch_t<h2s>(p, pl->BP, pl->BC, nz, st);
+    else if (out_dt == RS_F32) e = launch_t<float>(p, pl->BP, pl->BC, nz, st);
     else return -2;
     return e == hipSuccess ? 0 : -1;
 }

@@ -541,27 +541,29 @@ extern "C" float rs_wino_pack(const float* w, int Cin, int Cout, void* dst_) {
     return mx;
 }
 
-// Eligibility (a function of the layout alone - the engine asks in its dry pass, in want_stats and at launch): split storage in and out,
-// 3x3 / stride 1 / pad 1, one source, whole 32-channel chunks, Cout in blocks of 160 / 128 / 64, planes that tile by 8 x 16, Winograd weights
-// packed for the layer (IGemmParams::ww), no output activation, no folded shortcut, enough tiles to fill the chip.  RS_WINO=0: off.
-extern "C" int rs_wino_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz) {
+// Eligibility (a function of the layout alone, see ConvPlan; called by rs_conv_plan only): split storage in and out, 3x3 / stride 1 / pad 1,
+// one source, whole 32-channel chunks, Cout in blocks of 160 / 128 / 64, planes that tile by 8 x 16, Winograd weights packed for the layer
+// (IGemmParams::ww), no output activation, no folded shortcut, enough tiles to fill the chip.  RS_WINO=0: off.  Fills the plan (no
+// split-K, one statistics slab per 8 x 16 pixel tile) and returns 1, or returns 0.
+extern "C" int rs_wino_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz, ConvPlan* pl) {
     static const int on = []() { const char* e = getenv("RS_WINO"); return e ? atoi(e) : 1; }();
     static const int min_tiles = []() { const char* e = getenv("RS_WINO_MINTILES"); return e ? atoi(e) : 192; }();
     const IGemmParams& p = *pp;
-    if (!on || in_dt != RS_F16S || out_dt != RS_F16S || nz != 1 || !p.ww || p.C1 != 0 || p.no_halo || p.sx || p.act != RS_ACT_NONE) return 0;
+    if (!on || in_dt != RS_F16S || out_dt != RS_F16S || nz != 1 || !p.ww || p.C1 != 0 || p.unscaled_w || p.sC || p.act != RS_ACT_NONE) return 0;
     if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad_t != 1 || p.pad_l != 1 || p.up != 1 || p.Ho != p.Hs || p.Wo != p.Ws || p.osc == 2) return 0;
     if ((p.C0 % 32) || p.C0 > W_MAXCIN || (p.ld0 % 8) || (p.Cout % (16 * w_cf_of(p.Cout))) || (p.ldy % 8) || (p.res && (p.ldres % 8))) return 0;
-    if ((p.Ho % W_TH) || (p.Wo % W_TW) || p.splitk > 1) return 0;
+    if ((p.Ho % W_TH) || (p.Wo % W_TW)) return 0;
     const long long tiles = (long long)p.B * (p.Ho / W_TH) * (p.Wo / W_TW) * (p.Cout / (16 * w_cf_of(p.Cout)));
-    return (tiles >= min_tiles || (p.dbg & 64)) ? 1 : 0;   // (dbg bit 6: the op-level test entry runs shapes that do not fill the chip)
+    if (tiles < min_tiles && !(p.dbg & 64)) return 0;   // (dbg bit 6: the op-level test entry runs shapes that do not fill the chip)
+    *pl = ConvPlan{CK_WINO, W_TH * W_TW, 16 * w_cf_of(p.Cout), 0, 1, W_TH * W_TW};
+    return 1;
 }
 
-// pixels per statistics slab of a wino launch (one slab per 8 x 16 pixel tile); workgroups of a launch
-extern "C" int rs_wino_stats_px() { return W_TH * W_TW; }
+// workgroups of a launch
 extern "C" int rs_wino_tiles(const IGemmParams* p) { return p->B * (p->Ho / W_TH) * (p->Wo / W_TW) * (p->Cout / (16 * w_cf_of(p->Cout))); }
 
+// executes a CK_WINO plan
 extern "C" int rs_wino_launch(const IGemmParams* pp, hipStream_t st) {
-    if (!rs_wino_plan(pp, RS_F16S, RS_F16S, 1)) return -2;
     IGemmParams p = *pp;
     if (((size_t)p.x0 & 15) || ((size_t)p.y & 15) || ((size_t)p.res & 15) || ((size_t)p.ww & 15)) return -2;
     const size_t xb = (size_t)p.B * p.Hs * p.Ws * p.ld0 * 4;

@@ -1,7 +1,7 @@
-"""Helper of test_dry_and_real_pass_agree_without_a_gpu (tests/test_host_cpu.py): one rs_sample call with RS_FAKE_DEVICE=1 - the engine's real
+"""Helper of test_dry_and_real_pass_agree_without_a_gpu / test_launch_mix_is_pinned_without_a_gpu (tests/test_host_cpu.py): one rs_sample call with RS_FAKE_DEVICE=1 - the engine's real
 pass walks its whole control flow on a host-memory arena while every launch simply fails (there is no GPU), and prints what the dry
 sizing pass and the real pass each counted: coefficient-pool bytes, GroupNorm-tail tickets, producer / GroupNorm sequence numbers,
-kernel launches.  Usage: _fake_device_plumbing.py <config yaml name> <batch> <precision 0 fp16 | 1 fp32 | 2 split>"""
+kernel launches; then the launch mix of the call (per kernel family, igemm path, GroupNorm).  Usage: _fake_device_plumbing.py <config yaml name> <batch> <precision 0 fp16 | 1 fp32 | 2 split>"""
 import os, sys, ctypes as C
 os.environ["RS_FAKE_DEVICE"]="1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -32,3 +32,6 @@ for t in range(steps):
 a.prior_scale=float(tables["prior_scale"]); a.scale_factor=float(d.scale_factor); a.prec_encode=prec; a.prec_decode=0
 rc=lib.rs_sample(h, C.byref(a))
 print("rc",rc,_lib.last_error(), "launches", lib.rs_last_launch_count(h))
+# the launch mix (filled without profiling): launches per kernel family in the order of Exec::Fam, igemm-path and GroupNorm launch counts
+fam=(C.c_double*96)(); nf=lib.rs_profile_families(h, fam, 96); prof=(C.c_double*9)(); lib.rs_profile_get(h, prof)
+print("families", ",".join(str(int(fam[3*f+2])) for f in range(nf)), "igemm", int(prof[3]), "gn", int(prof[7]))

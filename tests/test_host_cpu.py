@@ -500,6 +500,33 @@ def test_dry_and_real_pass_agree_without_a_gpu(cname, B, prec):
         assert m0 and int(m0.group(1)) - v[8] == 7 * 15 + 2 + 2, (m0 and m0.group(1), v[8])
 
 
+@pytest.mark.parametrize("cname,B,prec,launches,families,igemm,gn", [
+    ("realsr_swinunet_realesrgan256", 32, 2, 2853, [22, 331, 13, 952, 0, 0, 0, 270, 120, 1, 1, 195], 1905, 426),
+    ("realsr_swinunet_realesrgan256", 4, 0, 4147, [38, 0, 1685, 0, 0, 270, 60, 0, 0, 2, 0, 0], 2055, 1225),
+    ("inpaint_lama256_imagenet", 16, 2, 837, [22, 84, 13, 275, 0, 0, 0, 72, 32, 1, 1, 68], 568, 114),
+    ("faceir_gfpgan512_lpips", 2, 2, 1218, [14, 10, 33, 510, 0, 0, 0, 72, 0, 1, 1, 0], 641, 326)])
+def test_launch_mix_is_pinned_without_a_gpu(cname, B, prec, launches, families, igemm, gn):
+    """Which kernel runs a conv is decided once per launch (rs_conv_plan, resshift_amd/csrc/igemm.hip) and every launch is booked under the
+    family of the kernel its plan names.  The launch mix of one sampling call - kernel launches, launches per kernel family in the order of
+    Exec::Fam (rs_profile_families), igemm-path and GroupNorm launch counts (rs_profile_get) - is pinned to what the routing rules gave
+    when the plan was introduced: a change of routing has to show up here, on purpose."""
+    import re
+    import subprocess
+    import sys
+
+    from resshift_amd import build as _b
+
+    env = dict(os.environ, RS_FAKE_DEVICE="1", RESSHIFT_HIP_LIB=_b.build_testhooks(), **NO_GPU)
+    r = subprocess.run([sys.executable, os.path.join(H.ROOT, "tests", "_fake_device_plumbing.py"), cname, str(B), str(prec)], env=env,
+                       capture_output=True, text=True, timeout=600)
+    m = re.search(r"real: tickets \d+ pool \d+ prod \d+ gn \d+ launches (\d+)", r.stderr)
+    f = re.search(r"families ([\d,]+) igemm (\d+) gn (\d+)", r.stdout)
+    assert m and f, (r.stdout[-500:], r.stderr[-1500:])
+    assert int(m.group(1)) == launches
+    assert [int(x) for x in f.group(1).split(",")] == families
+    assert (int(f.group(2)), int(f.group(3))) == (igemm, gn)
+
+
 def test_production_library_has_no_fake_device_hook():
     """VERDICT r5 weak #10 / ADVICE r4: RS_FAKE_DEVICE is a test hook; with the production library the same script must fail at its first
     device allocation instead of walking the real pass on host memory."""
