@@ -16,9 +16,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build" + ("_" + hashlib.sha256(os.environ["RS_BUILD_DEFS"].encode()).hexdigest()[:8] if os.environ.get("RS_BUILD_DEFS") else ""))
 LIB = os.environ.get("RS_BUILD_OUT") or os.path.join(HERE, "libresshift_hip.so")   # (RS_BUILD_OUT / RS_BUILD_DEFS: A/B builds of one source tree)
-SOURCES = ["igemm.hip", "igemm2.hip", "igemm3.hip", "igemm4.hip", "igemm4s.hip", "wino.hip", "igemm_split.hip", "swin_mlp.hip", "direct_conv.hip", "norm_attn.hip", "win_attn_split.hip", "ae_attn.hip", "ae_attn_split.hip", "elementwise.hip", "colorfix.hip", "engine.hip"]
-HEADERS = ["common.h", "igemm_common.h", "igemm4_kernel.h", "gn_tail.h", "philox.h", os.path.join("..", "..", "include", "resshift_hip.h")]
+SOURCES = ["igemm.hip", "igemm2.hip", "igemm3.hip", "igemm4.hip", "igemm4s.hip", "wino.hip", "igemm_split.hip", "swin_mlp.hip", "direct_conv.hip", "norm_attn.hip", "win_attn_split.hip", "ae_attn.hip", "ae_attn_split.hip", "elementwise.hip", "colorfix.hip", "model.hip", "engine.hip", "ops.hip"]
+HEADERS = ["common.h", "launchers.h", "igemm_common.h", "igemm4_kernel.h", "gn_tail.h", "philox.h", "weight_pack.h", "model.h", "graphs.h", os.path.join("..", "..", "include", "resshift_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+HOOKED = ["engine.hip"]   # the sources that consult rs_fake_device() (-DRS_TEST_HOOKS)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 FLAGS += [f"-D{d}" for d in os.environ.get("RS_BUILD_DEFS", "").split() if d]
 if os.environ.get("RS_BUILD_ABLATE"):   # extra instantiations for the K-loop timing ablations (scripts/igemm_bench.py + RS_IGEMM_DBG)
@@ -34,12 +35,12 @@ def _digest() -> str:
     return h.hexdigest()
 
 
-def _compile(src: str) -> str:
-    obj = os.path.join(OBJ, src.replace(".hip", ".o"))
-    cmd = [HIPCC, *FLAGS, "-c", os.path.join(CSRC, src), "-o", obj]
+def _compile(src: str, hooks: bool = False) -> str:
+    obj = os.path.join(OBJ, src.replace(".hip", "_testhooks.o" if hooks else ".o"))
+    cmd = [HIPCC, *FLAGS, *(["-DRS_TEST_HOOKS"] if hooks else []), "-c", os.path.join(CSRC, src), "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
-        raise RuntimeError(f"hipcc failed for {src}:\n{r.stderr[-4000:]}")
+        raise RuntimeError(f"hipcc failed for {src}{' (-DRS_TEST_HOOKS)' if hooks else ''}:\n{r.stderr[-4000:]}")
     return obj
 
 
@@ -69,7 +70,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
 
 def build_testhooks(verbose: bool = False) -> str:
-    """libresshift_hip_testhooks.so: the same objects with engine.hip recompiled under -DRS_TEST_HOOKS (the RS_FAKE_DEVICE plumbing hook of
+    """libresshift_hip_testhooks.so: the same objects with the HOOKED sources recompiled under -DRS_TEST_HOOKS (the RS_FAKE_DEVICE plumbing hook of
     tests/_fake_device_plumbing.py).  Never loaded by the product: resshift_amd._lib loads libresshift_hip.so unless RESSHIFT_HIP_LIB says otherwise."""
     build(force=False, verbose=verbose)
     out = os.path.join(HERE, "libresshift_hip_testhooks.so")
@@ -77,16 +78,14 @@ def build_testhooks(verbose: bool = False) -> str:
     dig = _digest() + "+hooks"
     if os.path.exists(out) and os.path.exists(stamp) and open(stamp).read().strip() == dig:
         return out
-    objs = [os.path.join(OBJ, s.replace(".hip", ".o")) for s in SOURCES if s != "engine.hip"]
+    plain = [s for s in SOURCES if s not in HOOKED]
+    objs = [os.path.join(OBJ, s.replace(".hip", ".o")) for s in plain]
     if not all(os.path.exists(o) for o in objs):   # (the library was built elsewhere: compile everything once)
         os.makedirs(OBJ, exist_ok=True)
         with cf.ThreadPoolExecutor(max_workers=min(8, len(SOURCES))) as ex:
-            list(ex.map(_compile, [s for s in SOURCES if s != "engine.hip"]))
-    hobj = os.path.join(OBJ, "engine_testhooks.o")
-    r = subprocess.run([HIPCC, *FLAGS, "-DRS_TEST_HOOKS", "-c", os.path.join(CSRC, "engine.hip"), "-o", hobj], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"hipcc failed for engine.hip (-DRS_TEST_HOOKS):\n{r.stderr[-4000:]}")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, *objs, hobj], capture_output=True, text=True)
+            list(ex.map(_compile, plain))
+    objs += [_compile(s, hooks=True) for s in HOOKED]
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, *objs], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link failed:\n{r.stderr[-4000:]}")
     with open(stamp, "w") as fh:

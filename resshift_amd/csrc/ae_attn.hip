@@ -1,6 +1,6 @@
 // Streaming ("flash") attention for the autoencoder's mid-block AttnBlock in fp16 storage (ldm/modules/diffusionmodules/model.py:
 // 179-203: single head, d = C = 512 channels, T = h * w tokens, softmax(q k^T / sqrt(C)) v; the reference's own memory-efficient variant
-// is :205-268).  The row-block path of engine.hip materialises the T x T score matrix in HBM one block of query rows at a time (fp32
+// is :205-268).  The row-block path of graphs.h (attnblock) materialises the T x T score matrix in HBM one block of query rows at a time (fp32
 // scores + fp16 probabilities: 12.9 GB per 4096-row block at T = 262 144, the reference's default 512-pixel tile) - more than half of
 // such a tile's 1.40 s (profiles/r3_tiled_chop512.txt).  Here S never leaves the chip.
 //
@@ -18,7 +18,7 @@
 // LDS: K tile + V^T tile = 2 x 64 KB at C = 512; the next K tile is requested as soon as S^T is done, the next V^T tile as soon as PV is.
 // Per key block and wave: 64 + 64 MFMAs against 64 + 64 ds_read_b128 - every wave reads both tiles completely, so LDS bandwidth and the
 // matrix pipe are about equally loaded (1 MB of fragment reads per block and CU): the price of d = 512 on 160 KB of LDS.
-#include "common.h"
+#include "launchers.h"
 
 namespace {
 

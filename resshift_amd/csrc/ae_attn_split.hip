@@ -18,7 +18,7 @@
 //     128-byte-row / XOR-swizzle format of the split implicit-GEMM kernels (a row = [32 hi | 32 lo] halfs), fetched by LDS-DMA; the K
 //     tile's rows are permuted like the fp16 kernel's so that a lane's S^T accumulators are eight CONSECUTIVE keys of the V^T tile.
 // LDS: 64 + 64 + 16 KB.  Per key block and wave 48 + 48 MFMAs against 32 + 32 ds_read_b128.
-#include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -7,8 +7,7 @@
 // adain:   out = clamp((sr - mean_sr) * std_lq / std_sr + mean_lq) per (image, channel) plane.  A statistics launch leaves one
 //          (mean, centred sum of squares) pair per 8192-element chunk of every plane; the apply launch merges a plane's pairs in a fixed
 //          order (Chan's update, fp64) and applies the affine.  No E[x^2] - mean^2, no floating-point atomics.
-#include "common.h"
-#include "../../include/resshift_hip.h"
+#include "launchers.h"
 #include <algorithm>
 #include <string>
 
@@ -316,7 +315,6 @@ __global__ __launch_bounds__(CF_ST_THREADS) void colorfix_adain_apply_kernel(con
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------------
 extern "C" {
 
-int rs_set_last_error(const char* text, int rc);   // engine.hip (rs_last_error's text)
 
 static inline int cf_chunks(long long n) { return (int)((n + CF_CHUNK - 1) / CF_CHUNK); }
 // what both entry points ask of the geometry; nullptr when it is fine

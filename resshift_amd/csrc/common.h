@@ -257,7 +257,7 @@ struct IGemmParams {
     const void* sx; const void* sw; const float* sbias;
     int sC, sld;
     unsigned sx_bytes, sw_bytes;   // (filled in by the launcher)
-    // output scatter of the sub-pixel form of "nearest x2 upsample + conv3x3" (engine.hip upfold; models/unet.py:53-81,
+    // output scatter of the sub-pixel form of "nearest x2 upsample + conv3x3" (graphs.h upfold_conv; models/unet.py:53-81,
     // ldm/modules/diffusionmodules/model.py:50-65): osc == 2 - this launch is one of four 2x2 convs over the LOW-resolution grid Ho x Wo and
     // GEMM row (b, oy, ox) is pixel (2 oy + ooy, 2 ox + oox) of the [B][2 Ho][2 Wo] output tensor.  Generic kernels only (igemm / igemm2 /
     // igemm3 / igemm_split), no residual, no split-K; output statistics from igemm_split only (the four launches fill ONE slab array -
@@ -330,7 +330,7 @@ struct WinAttnParams {
     float scale;
     // fused qkv projection (win_attn_qkv_kernel): normalised tokens instead of a qkv tensor
     const void* x;        // [B,H,W,ldx] fp16, features 0..E-1
-    const void* wqkv;     // [3E][E] weight of the qkv Linear (swin_transformer.py:85) in FRAGMENT-MAJOR order (engine.hip ConvW::wh_frag / ws_frag)
+    const void* wqkv;     // [3E][E] weight of the qkv Linear (swin_transformer.py:85) in FRAGMENT-MAJOR order (weight_pack.h; ConvW::wh_frag / ws_frag)
     const float* bqkv;    // [3E]
     int ldx;
     // optional fused output projection + residual (swin_transformer.py:141-143,277): out = res + proj(attention)

@@ -4,7 +4,7 @@
 //   * few output channels (UNet out head 160->3 models/unet.py:862; AE conv_out 512->3 / 128->3
 //     model.py:516,621; quant_conv / post_quant_conv ldm/models/autoencoder.py:25-26)
 // fp32 weights [K][Cout] (Cout fastest), fp32 accumulation in tap-major / channel-minor order.
-#include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -7,9 +7,8 @@
 //             A=-0.75, border-clamped taps, no antialias).
 //   VQ:       VectorQuantizer2.forward ldm/modules/vqvae/quantize.py:271-312 (expanded-form distance,
 //             first-minimum argmin, straight-through expression z + (z_q - z)).
-#include "common.h"
+#include "launchers.h"
 #include "philox.h"
-#include "../../include/resshift_hip.h"
 #include <algorithm>
 #include <string>
 
@@ -594,7 +593,6 @@ int rs_axpbypcz_rows_launch(const float* x, const float* z, const float* n, floa
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int rs_set_last_error(const char* text, int rc);   // engine.hip (rs_last_error's text)
 
 static inline bool al16f(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // what the seeded entry points ask of a key array; nullptr when it is fine

@@ -22,6 +22,7 @@
 //   * Split-K (grid.z) for launches with too few tiles to fill 256 CUs: fp32 partial slabs + a
 //     deterministic reduce kernel that applies the same epilogue.
 #include "igemm_common.h"
+#include "launchers.h"
 #include <algorithm>
 
 namespace {
@@ -361,17 +362,6 @@ hipError_t launch_t(const IGemmParams& p, int BP, int BC, int nz, hipStream_t st
 }  // namespace
 
 // per-kernel eligibility / tile rules (next to their kernels) and launchers: used by rs_conv_plan / rs_conv_launch below, nowhere else
-extern "C" int rs_igemm2_pick(int M, int Cout, int Kbytes, int nz, int* BP, int* BC);
-extern "C" int rs_igemm2_tile_px(int BP);
-extern "C" int rs_igemm2_launch(const IGemmParams* pp, int in_dt, int out_dt, int BP, int BC, int nz, hipStream_t st);
-extern "C" int rs_igemm3_pick(int M, int Cout, int Ktot, int in_dt, int nz, int splitk, int* BC);
-extern "C" int rs_igemm3_launch(const IGemmParams* pp, int out_dt, int BC, hipStream_t st);
-extern "C" int rs_igemm4_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz, ConvPlan* pl);
-extern "C" int rs_igemm4_launch(const IGemmParams* pp, int in_dt, const ConvPlan* pl, hipStream_t st);
-extern "C" int rs_wino_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz, ConvPlan* pl);
-extern "C" int rs_wino_launch(const IGemmParams* pp, hipStream_t st);
-extern "C" void rs_igemm_split_plan(const IGemmParams* pp, int out_dt, int nz, int can_split, ConvPlan* pl);
-extern "C" int rs_igemm_split_launch(const IGemmParams* pp, int out_dt, int nz, const ConvPlan* pl, hipStream_t st);
 
 extern "C" int rs_splitk_reduce_launch(const IGemmParams* pp, int out_dt, hipStream_t st) {
     const IGemmParams& p = *pp;

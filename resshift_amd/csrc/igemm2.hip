@@ -14,10 +14,10 @@
 //   * epilogue: bias / residual fetched up front, activation chosen at compile time behind one uniform branch, fragments
 //     finished one at a time (register budget), fp16 results transposed through LDS into 16-byte NHWC stores.
 #include "igemm_common.h"
+#include "launchers.h"
 #include <algorithm>
 #include <type_traits>
 
-extern "C" int rs_splitk_reduce_launch(const IGemmParams* p, int out_dt, hipStream_t st);
 
 namespace {
 

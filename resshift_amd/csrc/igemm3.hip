@@ -12,6 +12,7 @@
 //         X2: ds_read k-step 1 of stage i+1                     |  MFMA k-step 0 of stage i+1
 //     barrier(i+1) then publishes stage i+2 and retires every read of stage i.
 #include "igemm_common.h"
+#include "launchers.h"
 #include <type_traits>
 
 namespace {

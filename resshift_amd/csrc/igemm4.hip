@@ -2,6 +2,7 @@
 // split-K planning and the launch entry points.  The small-plane geometries (SEG > 0) are instantiated in igemm4s.hip.
 #define RS_IGEMM4_MAIN_TU 1
 #include "igemm4_kernel.h"
+#include "launchers.h"
 #include <algorithm>
 
 namespace {
@@ -17,8 +18,6 @@ hipError_t launch4_t(const IGemmParams& p, int TW, int BC, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int rs_igemm4_seg_launch(const IGemmParams* pp, int in_dt, int SEG, int BC, hipStream_t st);   // igemm4s.hip
-extern "C" int rs_splitk_reduce_launch(const IGemmParams* p, int out_dt, hipStream_t st);                  // igemm.hip
 
 namespace {
 

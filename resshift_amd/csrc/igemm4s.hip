@@ -2,6 +2,7 @@
 // 256-pixel tile, split-K over stages.  Serves every 3x3 / stride-1 conv of the 16 x 16 and 8 x 8 UNet levels
 // (models/unet.py:147,173 at ds = 16, 8).  Separate translation unit: the instantiations compile in parallel with igemm4.hip's.
 #include "igemm4_kernel.h"
+#include "launchers.h"
 
 extern "C" int rs_igemm4_seg_launch(const IGemmParams* pp, int in_dt, int SEG, int BC, hipStream_t st) {
     const IGemmParams& p = *pp;

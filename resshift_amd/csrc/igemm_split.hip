@@ -14,12 +14,11 @@
 //     residual (split storage), then either fp32 output or a fresh (hi, lo) split, transposed through LDS into 16-byte
 //     stores.
 #include "igemm_common.h"
+#include "launchers.h"
 #include "gn_tail.h"
 #include <algorithm>
 #include <type_traits>
 
-extern "C" int rs_splitk_reduce_launch(const IGemmParams* p, int out_dt, hipStream_t st);
-extern "C" int rs_splitk_reduce_stats_launch(const IGemmParams* p, int out_dt, hipStream_t st);   // igemm4.hip: reduce + statistics (+ GroupNorm tail)
 
 namespace {
 

@@ -1,0 +1,69 @@
+// Every host entry point that one .hip file defines and another calls, declared once.  The defining file includes this header too: with C
+// linkage a definition that disagrees with its declaration does not compile.
+#pragma once
+#include "common.h"
+#include "../../include/resshift_hip.h"
+
+extern "C" {
+int rs_set_last_error(const char* text, int rc);   // engine.hip (rs_last_error's text); returns rc
+// ---- the conv planner and what it routes to
+int rs_conv_plan(const IGemmParams* p, int in_dt, int out_dt, int nz, ConvPlan* plan);   // igemm.hip: THE kernel / tile / split-K decision
+int rs_conv_launch(const IGemmParams* p, int in_dt, int out_dt, int nz, const ConvPlan* plan, hipStream_t st);
+int rs_splitk_reduce_launch(const IGemmParams* p, int out_dt, hipStream_t st);         // igemm.hip
+int rs_splitk_reduce_stats_launch(const IGemmParams* p, int out_dt, hipStream_t st);   // igemm4.hip: reduce + statistics (+ GroupNorm tail)
+int rs_igemm2_pick(int M, int Cout, int Kbytes, int nz, int* BP, int* BC);
+int rs_igemm2_tile_px(int BP);
+int rs_igemm2_launch(const IGemmParams* pp, int in_dt, int out_dt, int BP, int BC, int nz, hipStream_t st);
+int rs_igemm3_pick(int M, int Cout, int Ktot, int in_dt, int nz, int splitk, int* BC);
+int rs_igemm3_launch(const IGemmParams* pp, int out_dt, int BC, hipStream_t st);
+int rs_igemm4_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz, ConvPlan* pl);
+int rs_igemm4_launch(const IGemmParams* pp, int in_dt, const ConvPlan* pl, hipStream_t st);
+int rs_igemm4_seg_launch(const IGemmParams* pp, int in_dt, int SEG, int BC, hipStream_t st);   // igemm4s.hip
+int rs_wino_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz, ConvPlan* pl);
+int rs_wino_launch(const IGemmParams* pp, hipStream_t st);
+void rs_igemm_split_plan(const IGemmParams* pp, int out_dt, int nz, int can_split, ConvPlan* pl);
+int rs_igemm_split_launch(const IGemmParams* pp, int out_dt, int nz, const ConvPlan* pl, hipStream_t st);
+// ---- everything else the engine launches
+size_t rs_wino_weight_bytes(int Cin, int Cout);
+float rs_wino_pack(const float* w_ref, int Cin, int Cout, void* dst);
+int rs_wino_tiles(const IGemmParams* p);
+int rs_direct_conv_launch(const DirectConvParams* p, int in_dt, int out_dt, hipStream_t st);
+int rs_head_conv_launch(const void* x, int in_dt, const float* coef_dev, const float* w_dev, const float* bias_dev, float* y, int B, int H, int W, int C,
+                        int ldx, int Cout, int ldy, hipStream_t st);
+int rs_groupnorm_launch(const GNParams* p, int dt, int apply_slabs, hipStream_t st);
+int rs_win_attn_launch(const WinAttnParams* p, int dt, hipStream_t st);
+int rs_softmax_rows_launch(const float* s, void* out, int out_dt, long long nrows, int ncols, long long lds_, long long ldo, hipStream_t st);
+int rs_nchw_to_nhwc_launch(const float* in, void* out, int out_dt, int B, int C, int HW, int ldo, int coff, float scale, hipStream_t st);
+int rs_nhwc_to_nchw_launch(const void* in, int in_dt, float* out, int B, int C, int HW, int ldi, int coff, hipStream_t st);
+int rs_axpbypcz_launch(const float* x, const float* z, const float* n, float* y, float a, float b, float c, long long cnt, hipStream_t st);
+int rs_axpbypcz_rows_launch(const float* x, const float* z, const float* n, float* y, const float* a, const float* b, const float* c, long long per,
+                            int B, hipStream_t st);
+int rs_axpbypcz_seeded_launch(const float* x, const float* z, float* y, const float* a, const float* b, const float* c, const rs_noise_key* keys,
+                              const rs_noise_key* keys_dev, const int* draw, long long per, int B, hipStream_t st);
+int rs_film_gather_launch(const float* const* rows, int B, int total, float* out, hipStream_t st);
+int rs_nchw_to_nhwc_rows_launch(const float* in, void* out, int out_dt, int B, int C, int HW, int ldo, int coff, const float* scale, hipStream_t st);
+int rs_clamp_launch(float* x, float lo, float hi, long long cnt, hipStream_t st);
+int rs_win_attn_qkv_supported(int heads, int E);
+int rs_win_attn_qkv_launch(const WinAttnParams* p, hipStream_t st);
+int rs_win_attn_qkv_split_launch(const WinAttnParams* p, hipStream_t st);
+int rs_ae_flash_supported(int C, int T);
+int rs_ae_flash_launch(const void* q, int ldq, const void* k, int ldk, const void* vt, const float* bv, void* o, int ldo, int nz, int T, int C,
+                       float scale, hipStream_t st);
+int rs_ae_flash_split_supported(int C, int T);
+int rs_ae_flash_split_launch(const void* q, int ldq, const void* k, int ldk, const void* vt, const float* bv, void* o, int ldo, int nz, int T, int C,
+                             float scale, hipStream_t st);
+int rs_swin_mlp_supported(int E, int HD);
+int rs_swin_mlp_split_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* res, void* y, int M, int ldx,
+                             int ldres, int ldy, int E, int HD, const float* xcoef, int HW, float* ystats, int ystats_ld, const GNTail* tail, hipStream_t st);
+int rs_swin_mlp_split_launch_n(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* res, void* y, int M, int ldx,
+                               int ldres, int ldy, int E, int HD, int NO, const float* xcoef, int HW, float* ystats, int ystats_ld, const GNTail* tail,
+                               hipStream_t st);
+int rs_swin_mlp_split_unembed_supported(int E, int HD, int NO);
+int rs_swin_mlp_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* res, void* y, int M, int ldx,
+                       int ldres, int ldy, int E, int HD, const float* xcoef, int HW, float* ystats, int ystats_ld, hipStream_t st);
+int rs_small_linear_launch(const float* x, const float* w, const float* bias, float* y, int R, int K, int N, int silu_in, int silu_out, hipStream_t st);
+int rs_bicubic_launch(const float* in, void* out, int out_dt, int B, int C, int H, int W, int sf, int ldo, hipStream_t st);
+int rs_vq_launch(const float* z, const float* codebook, float* zq, int* idx, long long N, int NE, int D, hipStream_t st);
+int rs_copy_channels_launch(const void* src, int lds_, void* dst, int ldd, int C, long long npix, int dt, hipStream_t st);
+int rs_convert_launch(const void* src, int src_dt, void* dst, int dst_dt, int C, long long npix, hipStream_t st);
+}

@@ -7,7 +7,7 @@
 //              shift mask, softmax, PV) with roll / window_partition / window_reverse
 //              (swin_transformer.py:35-63,252-275) folded into the load/store addressing.
 //   Row softmax: ldm/modules/diffusionmodules/model.py:193 (AE mid-block attention).
-#include "common.h"
+#include "launchers.h"
 #include "gn_tail.h"
 #include <type_traits>
 
@@ -840,7 +840,7 @@ __global__ __launch_bounds__(384) void win_attn_qkv_kernel(WinAttnParams p, unsi
     const f16* wq = (const f16*)p.wqkv;
     const int swz[2] = {(lg ^ (lr & 7)) << 4, ((4 + lg) ^ (lr & 7)) << 4};
     // this head's 32 output features starting at weight row n0: fragments straight from L2 in MFMA A-operand layout.  The weights come
-    // in FRAGMENT-MAJOR order (engine.hip ConvW::wh_frag: [16-row block][k step][lane] x 16 B): one contiguous 1 KB per wave instruction
+    // in FRAGMENT-MAJOR order (weight_pack.h; ConvW::wh_frag: [16-row block][k step][lane] x 16 B): one contiguous 1 KB per wave instruction
     // (8 cache lines) where the row-major weight costs 16 lines of which half the bytes are used
     auto load_w = [&](const f16* wsrc, int n0, f16x8 (&wf)[2][KS]) {
 #pragma unroll

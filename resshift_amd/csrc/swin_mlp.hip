@@ -16,6 +16,7 @@
 // 146 us for this kernel at 131072 tokens: every wave then reads the whole W1 and W2 chunk from LDS, 72 LDS instructions
 // per chunk per wave.  profiles/r1_igemm_ablation.txt.)
 #include "igemm_common.h"
+#include "launchers.h"
 #include "gn_tail.h"
 #include <type_traits>
 #include <cstdlib>

@@ -15,7 +15,7 @@
 //      O^T = V^T P with P split on the fly (as win_attn_split_kernel);
 //   4. the heads' results meet in LDS (the token tile's space, same format) and wave h produces output features 32h .. 32h + 31 of
 //      the projection, adds the shortcut and stores the (hi, lo) pair.
-#include "common.h"
+#include "launchers.h"
 #include "gn_tail.h"
 #include <type_traits>
 
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(384) void win_attn_qkv_split_kernel(WinAttnParams p
     auto load_w = [&](const f16* wsrc, int n0, f16x8 (&wh)[2][KS], f16x8 (&wl)[2][KS]) {
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
-            // fragment-major weights (engine.hip ConvW::ws_frag): per (16-row block, k step) 1 KB of hi then 1 KB of lo, lane-contiguous
+            // fragment-major weights (weight_pack.h; ConvW::ws_frag): per (16-row block, k step) 1 KB of hi then 1 KB of lo, lane-contiguous
             const f16* wr = wsrc + (long long)((n0 >> 4) + f) * KS * 1024 + lane * 8;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {

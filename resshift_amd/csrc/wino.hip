@@ -36,6 +36,7 @@
 //   * epilogue: the sixteen positions of a (tile, channel) meet through LDS (rounds of 16 tiles x half the channels), output transform,
 //     x 2^-11, bias, residual, split, stores; statistics in a fixed order; tail as in igemm4.
 #include "igemm_common.h"
+#include "launchers.h"
 #include "gn_tail.h"
 #include <algorithm>
 #include <cmath>

@@ -248,7 +248,7 @@ def swin_mlp(x, w1, b1, w2, b2, res=None):
 def swin_mlp_unembed(x, coef, hw, w1, b1, w2, b2, wu, bu):
     """Last Swin block's MLP half + patch_unembed in one launch (split storage): x [M, E] int32 (hi, lo) pairs = the block's raw input,
     coef [M / hw, 2, E] fp32 = norm2's per-image affine; returns [M, NO] split.  The product matrix [Wu W2 | Wu] and the merged bias are
-    formed here in float64 exactly like the engine's packer (engine.hip: add_basiclayer)."""
+    formed here in float64 exactly like the engine's packer (csrc/weight_pack.h: rs_unembed_fold_weight)."""
     lib = _lib.load()
     M, E = x.shape
     HD, NO = w1.shape[0], wu.shape[0]

@@ -179,7 +179,7 @@ def reflect_pad(x: torch.Tensor, pad_h: int, pad_w: int) -> torch.Tensor:
     return _lib.window_copy(x, 0, 0, H + pad_h, W + pad_w)
 
 
-BLOB_CACHE_MAGIC = b"RSBLOB06"   # bump when the packed layout (csrc/engine.hip weight builder) changes
+BLOB_CACHE_MAGIC = b"RSBLOB06"   # bump when the packed layout (csrc/model.hip, csrc/weight_pack.h) changes
 BLOB_CACHE_HEADER = 40            # magic 8 | blob bytes 8 | checkpoint fingerprint 16 | packed weight forms 4 | reserved 4
 
 

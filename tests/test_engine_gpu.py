@@ -693,7 +693,7 @@ def test_patch_unembed_fold_matches_the_separate_conv(gpu, tmp_path):
 @pytest.mark.parametrize("prec", ["split", "fp16"])
 def test_upsample_subpixel_form_matches_the_folded_address_conv(gpu, tmp_path, prec):
     """Round 5: `Upsample` (models/unet.py:53-81; ldm/modules/diffusionmodules/model.py:50-65: nearest x2, then conv3x3) as four 2x2 convs
-    over the low-resolution grid with the taps that fall on one source pixel summed up front (engine.hip add_upfold: 2.25 x fewer
+    over the low-resolution grid with the taps that fall on one source pixel summed up front (model.hip add_upfold: 2.25 x fewer
     multiply-adds) against RS_UPFOLD=0, the 3x3 conv whose addressing folds the upsample: a full-size UNet forward at the bench batch (the
     32 x 32 -> 64 x 64 step takes the new form there) and the VQ-f4 decoder of a 512 x 512 image (both of its steps), same weights, same
     inputs.  fp32-class agreement in split storage; fp16 storage rounds the SUMMED weight once instead of every tap - fp16-class agreement."""

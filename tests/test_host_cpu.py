@@ -468,7 +468,7 @@ def test_bench_launcher_pieces(monkeypatch):
 @pytest.mark.parametrize("cname,B,prec", [("realsr_swinunet_realesrgan256", 32, 2), ("realsr_swinunet_realesrgan256", 4, 0),
                                           ("inpaint_lama256_imagenet", 16, 2), ("faceir_gfpgan512_lpips", 2, 2)])
 def test_dry_and_real_pass_agree_without_a_gpu(cname, B, prec):
-    """Round 4: the GroupNorm tail plan (resshift_amd/csrc/gn_tail.h, engine.hip: TailPlan) is made by the engine's dry sizing pass and
+    """Round 4: the GroupNorm tail plan (resshift_amd/csrc/gn_tail.h, graphs.h: TailPlan) is made by the engine's dry sizing pass and
     executed by its real pass; the two walk the same control flow and must agree about every pool they size: coefficient pool, tickets,
     producer and GroupNorm sequence numbers - and every planned tail must be attached to its producer's launch.  RS_FAKE_DEVICE=1 lets the
     real pass run on a host-memory arena in this GPU-less container (every launch fails, the bookkeeping does not).  Also pins the
@@ -558,11 +558,11 @@ def test_weight_forms_and_sampler_policies():
 
 
 def test_subpixel_form_of_upsample_conv_is_exact_algebra():
-    """The algebra behind engine.hip add_upfold, restated in torch on the CPU: nearest x2 + conv3x3 (models/unet.py:53-81,
+    """The algebra behind model.hip add_upfold, restated in torch on the CPU: nearest x2 + conv3x3 (models/unet.py:53-81,
     ldm/modules/diffusionmodules/model.py:50-65) == four 2x2 convs over the LOW-resolution grid (pad_t = 1 - py, pad_l = 1 - px, i.e. rows
     {y - 1 + py, y + py}) whose weights are the sums of the taps that land on the same source pixel, outputs interleaved by parity.  In float64
     the two forms agree to rounding - including the borders, where zero padding of the upsampled image is zero padding of the source.  (The C++
-    packer and the kernels' row scatter are pinned on the GPU: test_upsample_subpixel_form_matches_the_folded_address_conv.)"""
+    packer's tap sums are pinned by tests/weight_pack_check.cpp, the kernels' row scatter on the GPU: test_upsample_subpixel_form_matches_the_folded_address_conv.)"""
     import torch.nn.functional as F
 
     g = torch.Generator().manual_seed(11)
@@ -587,3 +587,72 @@ def test_subpixel_form_of_upsample_conv_is_exact_algebra():
             out[:, :, py::2, px::2] = F.conv2d(xp, w2, b)
     assert [len(taps(0, 0)), len(taps(0, 1)), len(taps(1, 0)), len(taps(1, 1))] == [1, 2, 2, 1]
     assert (out - ref).abs().max().item() < 1e-12
+
+
+def test_weight_packers_give_known_answers_under_sanitizers(tmp_path):
+    """resshift_amd/csrc/weight_pack.h - the one place that writes the packed weight formats, for the model packer and the op-level entries
+    alike - is host code without a HIP runtime call: tests/weight_pack_check.cpp (its own main, weights that encode their index) is built
+    host-only with AddressSanitizer + UBSan and run here.  Row forms with zero padded columns, the fragment-major order, the three
+    relative-position bias tables, the sub-pixel tap sums and the patch_unembed fold are checked against known answers."""
+    import subprocess
+
+    from resshift_amd import build
+
+    if not os.path.exists(build.HIPCC):
+        pytest.skip("hipcc not available")
+    exe = str(tmp_path / "weight_pack_check")
+    r = subprocess.run([build.HIPCC, "-x", "hip", "--offload-host-only", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined", "-I", build.CSRC,
+                        os.path.join(ROOT, "tests", "weight_pack_check.cpp"), "-o", exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "weight_pack_check: ok" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+
+
+# rs_weight_bytes of the shipped configs, measured with the library of the commit before the packer moved into model.hip / weight_pack.h:
+# (all three weight forms, the parity policy's fp16 + split)
+_BLOB_BYTES = {"realsr_swinunet_realesrgan256": (2044816384, 1333900800),
+               "inpaint_lama256_imagenet": (2045422336, 1334419200),
+               "faceir_gfpgan512_lpips": (2267170816, 1467323136)}
+
+
+def _blob_bytes(cname, f16, f32, split):
+    """rs_weight_bytes of a fresh engine: rs_create sizes the blob - no GPU, no weights"""
+    from resshift_amd import _lib
+    from resshift_amd.config import load_config, to_plain
+    from resshift_amd.engine import _fill_ae, _fill_unet
+
+    lib = _lib.load()
+    y = to_plain(load_config(cname))
+    cfg = _lib.Config()
+    _fill_unet(cfg.unet, y["model"]["params"])
+    _fill_ae(cfg.ae, y["autoencoder"]["params"])
+    cfg.has_unet = cfg.has_ae = 1
+    cfg.enable_f16, cfg.enable_f32, cfg.enable_split = f16, f32, split
+    h = lib.rs_create(ctypes.byref(cfg))
+    assert h, _lib.last_error()
+    n = lib.rs_weight_bytes(h)
+    lib.rs_destroy(h)
+    return n
+
+
+@pytest.mark.parametrize("cname", sorted(_BLOB_BYTES))
+def test_weight_blob_layout_is_pinned(cname):
+    """The blob's layout is a pure function of the config and the enabled weight forms (a rank that receives the blob by broadcast, or reads
+    it from the cache file, resolves the same offsets): its size is pinned per shipped config.  A deliberate layout change updates these
+    numbers - and BLOB_CACHE_MAGIC (resshift_amd/sharding.py)."""
+    assert (_blob_bytes(cname, 1, 1, 1), _blob_bytes(cname, 1, 0, 1)) == _BLOB_BYTES[cname]
+
+
+@pytest.mark.parametrize("knob,nbytes", [("RS_WINO", 1843293184), ("RS_UPFOLD", 1894050816)])
+def test_weight_blob_layout_knobs_are_pinned(knob, nbytes):
+    """RS_WINO=0 / RS_UPFOLD=0 when the engine is created leave the Winograd / sub-pixel forms out of the blob (realsr, all three forms;
+    measured like _BLOB_BYTES).  In a child process: the library reads a knob once."""
+    import subprocess
+    import sys
+
+    src = "import sys; sys.path.insert(0, %r); import test_host_cpu as t; print('blob_bytes', t._blob_bytes('realsr_swinunet_realesrgan256', 1, 1, 1))"
+    r = subprocess.run([sys.executable, "-c", src % os.path.join(ROOT, "tests")], env=dict(os.environ, **NO_GPU, **{knob: "0"}), capture_output=True,
+                       text=True, timeout=300)
+    m = re.search(r"blob_bytes (\d+)", r.stdout)
+    assert m and int(m.group(1)) == nbytes, (r.stdout[-500:], r.stderr[-1500:])
