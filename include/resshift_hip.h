@@ -280,6 +280,33 @@ size_t rs_color_fix_work_bytes(int B, int C, int H, int W, int sf, int mode);
 int rs_color_fix(const float* sr, const float* lq, float* out, int B, int C, int H, int W, int sf, int mode, void* work, size_t work_bytes,
                  void* stream);
 
+/* ---- antialiased resize to any output size (opt-in) ---------------------------------------------------
+ * The network produces its own factor only (sf = 4, 2 or 1); another output scale ("x2 from the x4 model", "x3") is a resample of its
+ * result.  The function is MATLAB's imresize with antialiasing - the resampler of the SR literature and of the reference's data
+ * pipeline (utils/util_image.py:imresize_np), so it also makes bicubic LQ inputs the way the models were trained on.  Stateless.
+ *   in  [B,C,H,W]  fp32 NCHW, contiguous, only read        out  [B,C,Ho,Wo]  fp32 NCHW, contiguous
+ * One axis, input length n, output length m, scale s > 0:   a = min(s, 1),   kw = 4 / a,   P = ceil(kw) + 2.
+ * Output index i (0-based), taps k = 0 .. P-1:
+ *       u    = (i + 1) / s + 0.5 (1 - 1/s)
+ *       left = floor(u - kw / 2)
+ *       tap k has the 1-based index j = left + k and the raw weight  a * cubic(a * (u - j))
+ *   cubic = Keys' kernel with A = -0.5:   1.5|x|^3 - 2.5|x|^2 + 1  for |x| <= 1,   -0.5|x|^3 + 2.5|x|^2 - 4|x| + 2  for 1 < |x| <= 2,
+ *   0 otherwise.  The weights are divided by their sum.  The tap reads in[mirror(j - 1)]; mirror is the symmetric reflection of period 2n
+ *   that repeats the edge sample, applied as often as needed:   q = (j - 1) mod 2n,   q < n ? q : 2n - 1 - q.
+ * The image is resized along H first, then along W; both passes in fp32, taps accumulated in ascending order.  No clamp unless `clamp`.
+ * This is imresize_np(..., antialiasing=True): its removal of zero-weight columns changes no value, its single reflection is the case
+ * P <= n.  (rs_bicubic / F.interpolate differ: A = -0.75 and clamped borders; F.interpolate(antialias=True) clamps and renormalises at
+ * the borders where this definition mirrors.)
+ * Coordinates are part of the definition: u and left in fp64 from the integer output index, the distance u - j formed in fp64 and
+ * rounded to fp32 once; weights and sums are fp32.  A pixel's value is a function of its plane and its output index only - not of the
+ * tile, the batch, the grid or the pointer alignment; no floating-point atomics.  tests/_resize_ref.py restates this in float64.
+ * `clamp` = 1 clamps the result to [-1, 1] (the samplers), 0 leaves it as computed.  The caller chooses Ho, Wo and the scales:
+ * imresize's rules are Ho = ceil(H s) for a given scale, s_h = Ho / H and s_w = Wo / W for a given size.
+ * Argument errors are found before anything is launched, -2 with rs_last_error() starting "rs_resize: ": a null pointer, a
+ * non-positive size, a scale outside [1/8, 8] (1/8 bounds P at 34), an `out` that is or overlaps `in`, a clamp other than 0 or 1. */
+int rs_resize(const float* in, float* out, int B, int C, int H, int W, int Ho, int Wo, double scale_h, double scale_w, int clamp,
+              void* stream);
+
 /* uint8 pre / post processing on the device.
  * rs_u8_to_input:  interleaved uint8 [B,H,W,C] -> planar fp32 [B,C,H,W] in [-1,1]  ((v/255 - 0.5)/0.5; replaces
  *                  datapipe/datasets.py:59-63 ToTensor + Normalize on the host)

@@ -8,7 +8,9 @@ so torch device pointers and streams are valid inside the engine.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
+from fractions import Fraction
 
 import torch  # noqa: F401  (must precede the CDLL call, see module docstring)
 
@@ -139,6 +141,7 @@ SIGNATURES = {
     "rs_tile_scatter_weighted": (_I, [C.POINTER(TileDesc), _I, _I, _I, _P, _I, _I, _I, _I, _P]),
     "rs_color_fix_work_bytes": (_SZ, [_I] * 6),
     "rs_color_fix": (_I, [_P, _P, _P] + [_I] * 6 + [_P, _SZ, _P]),
+    "rs_resize": (_I, [_P, _P] + [_I] * 6 + [C.c_double, C.c_double, _I, _P]),
     "rs_u8_to_input": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rs_output_to_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rs_arena_bytes": (_SZ, [_P]),
@@ -324,4 +327,38 @@ def color_fix(sr, lq, mode):
     out = torch.empty_like(sr)
     check(lib.rs_color_fix(sr.data_ptr(), lq.data_ptr(), out.data_ptr(), B, Cc, H, W, sf, m, work.data_ptr() if need else None, need,
                            current_stream_ptr()), "rs_color_fix")
+    return out
+
+
+RESIZE_SCALES = (0.125, 8.0)   # rs_resize holds at most ceil(4 * 8) + 2 = 34 taps per axis
+
+
+def resize_len(n, scale) -> int:
+    """ceil(n * scale), exactly: the scale is taken as the nearest fraction of denominator <= 4096 (0.3 * 40 is 12)"""
+    return math.ceil(int(n) * Fraction(scale).limit_denominator(4096))
+
+
+def resize(x, scale=None, size=None, clamp=False):
+    """rs_resize: x [B,C,H,W] (a contiguous fp32 device tensor) resized with MATLAB's antialiased bicubic imresize (include/resshift_hip.h).
+    Exactly one of `scale` - a number for both axes; the output is ceil(H * scale) x ceil(W * scale), as imresize_np has it - and `size`
+    = (Ho, Wo), which gives the per-axis scales Ho / H and Wo / W.  `clamp`: clamp the result to [-1, 1].  Returns a new tensor."""
+    if (scale is None) == (size is None):
+        raise ValueError("resize: give exactly one of scale and size")
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4):
+        raise ValueError("resize: x [B,C,H,W] must be a contiguous float32 device tensor")
+    B, Cc, H, W = x.shape
+    if scale is not None:
+        if isinstance(scale, bool) or not isinstance(scale, (int, float, Fraction)) or not scale > 0:
+            raise ValueError(f"resize: scale must be a positive number, not {scale!r}")
+        Ho, Wo = resize_len(H, scale), resize_len(W, scale)
+        sh = sw = float(scale)
+    else:
+        if not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and not isinstance(v, bool) and v > 0 for v in size)):
+            raise ValueError(f"resize: size must be two positive integers (Ho, Wo), not {size!r}")
+        Ho, Wo = size
+        sh, sw = Ho / H, Wo / W
+    if not all(RESIZE_SCALES[0] <= s <= RESIZE_SCALES[1] for s in (sh, sw)):
+        raise ValueError(f"resize: the scales ({sh:.6g}, {sw:.6g}) of {H} x {W} -> {Ho} x {Wo} must lie in [1/8, 8]")
+    out = torch.empty((B, Cc, Ho, Wo), device=x.device, dtype=torch.float32)
+    check(load().rs_resize(x.data_ptr(), out.data_ptr(), B, Cc, H, W, Ho, Wo, sh, sw, 1 if clamp else 0, current_stream_ptr()), "rs_resize")
     return out

@@ -204,6 +204,13 @@ class Engine:
         with torch.cuda.device(self.device):
             return _lib.color_fix(self._f32c(sr), self._f32c(lq), mode)
 
+    def resize(self, x, scale=None, size=None, clamp=False):
+        """x [B,C,H,W] resized with MATLAB's antialiased bicubic imresize (rs_resize): `scale` for both axes (output
+        ceil(H * scale) x ceil(W * scale)) or `size` = (Ho, Wo); `clamp` clamps the result to [-1, 1].  Returns a new fp32 tensor; whole
+        images only - tiles are resized after they are blended."""
+        with torch.cuda.device(self.device):
+            return _lib.resize(self._f32c(x), scale=scale, size=size, clamp=clamp)
+
     def axpbypcz(self, x, z, n, a, b, c, out=None):
         """out = a*x + b*z + c*n elementwise on fp32 tensors of identical layout (z, n optional)."""
         x = self._f32c(x)

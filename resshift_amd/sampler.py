@@ -68,7 +68,7 @@ class BaseSampler:
 
     def __init__(self, configs, sf=4, use_amp=True, chop_size=128, chop_stride=128, chop_bs=1, padding_offset=16, seed=10000,
                  state_dicts: Optional[Mapping[str, Mapping[str, torch.Tensor]]] = None, blob_cache=None, precision=None, pack="policy",
-                 tile_blend="uniform", color_fix="none"):
+                 tile_blend="uniform", color_fix="none", out_scale=None):
         """`state_dicts` ({"model": sd, "autoencoder": sd}) replaces checkpoint files, e.g. for synthetic-weight runs.
         `blob_cache`: file that keeps the packed device weights between runs (sharding.build_engine_with_broadcast).
         `precision`: "parity" | "fp16" | "fp32" | "split" (POLICIES).  Default: "parity" when `use_amp` (the reduced-precision path of the
@@ -82,7 +82,12 @@ class BaseSampler:
         `color_fix`: "none" | "wavelet" | "adain" - colour correction of every whole image `sample_tiled` / `inference` (with and without
         `pool`) return against its LQ input, on the device (rs_color_fix): "wavelet" keeps the sample's detail and takes the
         low frequencies of the bicubic up-sampled input, "adain" takes the input's per-channel mean and deviation.  Tiles are corrected
-        after they are blended, never one by one; `sample_func` is not affected.  Undefined for masked (inpainting) inputs: ValueError."""
+        after they are blended, never one by one; `sample_func` is not affected.  Undefined for masked (inpainting) inputs: ValueError.
+        `out_scale`: None, or the factor between the LQ input and every whole image `sample_tiled` / `inference` (with and without `pool`)
+        return - "x2 from the x4 model", "x3": the image is (ceil(H_lq * out_scale), ceil(W_lq * out_scale)), the model's result resized
+        on the device by MATLAB's antialiased bicubic imresize and clamped to [-1, 1] (rs_resize), after the tiles are
+        blended and after the colour fix.  None, or a value equal to `sf`, issues exactly the launches issued without it; otherwise
+        out_scale / sf must lie in [1/8, 8].  `sample_func` is not affected.  Masked (inpainting) inputs: ValueError."""
         self.configs = configs if isinstance(configs, Mapping) else load_config(configs)
         self.sf = sf
         self.chop_size, self.chop_stride, self.chop_bs = chop_size, chop_stride, chop_bs
@@ -95,6 +100,8 @@ class BaseSampler:
         self.tile_blend = tile_blend
         tiling.check_color_fix(color_fix)
         self.color_fix = color_fix
+        tiling.check_out_scale(out_scale, sf)
+        self.out_scale = out_scale
         if pack not in ("policy", "all"):
             raise ValueError("pack must be 'policy' or 'all'")
         self.pack = pack
@@ -208,6 +215,9 @@ class ResShiftSampler(BaseSampler):
         tiling.check_color_fix(fix)
         if fix != "none" and mask is not None:
             raise ValueError(f"color_fix={fix!r} is undefined for a masked input (the LQ image has a hole): use color_fix='none'")
+        out_scale = self._out_scale()
+        if out_scale is not None and mask is not None:
+            raise ValueError(f"out_scale={out_scale!r} is undefined for a masked input (lq and mask stay at the model's size): use out_scale=None")
         B0 = im_lq.shape[0]
         if seed is not None:
             if tile_noises is not None or noise_repeat:
@@ -221,7 +231,7 @@ class ResShiftSampler(BaseSampler):
             else:
                 nz = tile_noises[0] if tile_noises else (None, None)
                 sr = self.sample_func(im_lq, noise_repeat=noise_repeat, mask=mask, noise=nz[0], step_noises=nz[1])
-            return sr if fix == "none" else self.engine.color_fix(sr, im_lq, fix)
+            return self._finish(sr, im_lq, fix, out_scale)
         x = torch.cat([im_lq, mask], dim=1) if mask is not None else im_lq
         blend = getattr(self, "tile_blend", "uniform")   # ("uniform" issues exactly the calls it always has)
         splitter = TileSplitter(x, self.chop_size, stride=self.chop_stride, sf=self.sf, extra_bs=self.chop_bs,
@@ -238,8 +248,24 @@ class ResShiftSampler(BaseSampler):
                 nz = tile_noises[k] if tile_noises else (None, None)
                 out = self.sample_func(pch, noise_repeat=noise_repeat, mask=mask_pch, noise=nz[0], step_noises=nz[1])
             splitter.update(out, index_infos)
-        sr = splitter.gather()
-        return sr if fix == "none" else self.engine.color_fix(sr, im_lq, fix)
+        return self._finish(splitter.gather(), im_lq, fix, out_scale)
+
+    def _out_scale(self):
+        """the sampler's `out_scale` where it asks for another size than the model's, else None: None and a value equal to sf issue
+        exactly the calls issued without it"""
+        out_scale = getattr(self, "out_scale", None)
+        if out_scale is None:
+            return None
+        tiling.check_out_scale(out_scale, self.sf)
+        return out_scale if tiling.resizes(out_scale, self.sf) else None
+
+    def _finish(self, sr, im_lq, fix, out_scale):
+        """what follows the blend of a whole image: the colour fix at the model's scale, then the resize to `out_scale`"""
+        if fix != "none":
+            sr = self.engine.color_fix(sr, im_lq, fix)
+        if out_scale is not None:
+            sr = self.engine.resize(sr, size=tiling.out_size(im_lq.shape[2], im_lq.shape[3], out_scale), clamp=True)
+        return sr
 
     # ------------------------------------------------------------------ file-level demo driver
     @staticmethod
@@ -263,12 +289,15 @@ class ResShiftSampler(BaseSampler):
         `seeded=True` (with and without `pool`): the image at position i of the sorted listing of the whole input gets the seed
         `image_seed(i)`, its tile j the stream j - the noise of a file does not depend on the number of ranks, on `bs` or
         on `pool`, so neither do the PNGs beyond the engine's own batch-size sensitivity.  Excludes `noise_repeat`.
-        The sampler's `color_fix` reaches every image through `sample_tiled` resp. the `TilePool`; it excludes `mask_path`."""
+        The sampler's `color_fix` and `out_scale` reach every image through `sample_tiled` resp. the `TilePool`; they exclude `mask_path`."""
         if seeded and noise_repeat:
             raise ValueError("seeded=True names every draw by (seed, stream): it excludes noise_repeat")
         fix = getattr(self, "color_fix", "none")
         if fix != "none" and mask_path is not None:
             raise ValueError(f"color_fix={fix!r} is undefined for masked (inpainting) inputs: use color_fix='none'")
+        out_scale = self._out_scale()
+        if out_scale is not None and mask_path is not None:
+            raise ValueError(f"out_scale={out_scale!r} is undefined for masked (inpainting) inputs: use out_scale=None")
         in_path, out_path = Path(in_path), Path(out_path)
         if self.rank == 0:
             out_path.mkdir(parents=True, exist_ok=True)

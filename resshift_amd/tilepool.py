@@ -28,7 +28,8 @@ tiles retire through ONE `rs_tile_scatter_weighted` launch - the bits of `rs_til
 `sample_tiled` issues under the same mode - and the count plane holds the weight sum that `rs_tile_finalize` divides by.
 
 The sampler's `color_fix` ("none" by default) is applied to each completed image after `rs_tile_finalize`, against the
-image's own LQ planes (`rs_color_fix`): tiles are never corrected one by one.
+image's own LQ planes (`rs_color_fix`): tiles are never corrected one by one.  The sampler's `out_scale` (None by default)
+follows it: each completed image is resized to (ceil(H * out_scale), ceil(W * out_scale)) and clamped (`rs_resize`).
 
 `seeded=True`: `submit(image, seed=...)` names the image; tile j (index in `tiling.extract_starts` order, the order of
 `tile_windows`) draws its noise from key (seed, stream = j) inside the engine's kernels.  No draws are made or stored, and an image's
@@ -44,7 +45,7 @@ import torch
 
 from . import _lib
 from .continuous import ContinuousSampler, check_sampler, request_seed
-from .tiling import check_blend, check_color_fix, extract_starts, feather_ramp
+from .tiling import check_blend, check_color_fix, check_out_scale, extract_starts, feather_ramp, out_size, resizes
 
 HEADLINE_PIXELS = 32 * 64 * 64   # LR pixels of the benchmark's batch (32 images of 64 x 64): what `max_batch=None` fills a class up to
 
@@ -107,6 +108,11 @@ class TilePool:
         check_color_fix(self.color_fix)
         if self.color_fix != "none" and self.cond_mask:
             raise ValueError(f"color_fix={self.color_fix!r} is undefined for a model conditioned on a mask (the LQ image has a hole)")
+        # and the output scale (BaseSampler(out_scale=)): each completed image is resized after the colour fix
+        self.out_scale = getattr(sampler, "out_scale", None)
+        check_out_scale(self.out_scale, self.sf)
+        if resizes(self.out_scale, self.sf) and self.cond_mask:
+            raise ValueError(f"out_scale={self.out_scale!r} is undefined for a model conditioned on a mask (lq and mask stay at the model's size)")
 
     # ------------------------------------------------------------------ requests
     def class_max_batch(self, key: Tuple[int, int]) -> int:
@@ -236,6 +242,8 @@ class TilePool:
             res = _lib.tile_finalize(im.acc, im.count)
             if self.color_fix != "none":   # the whole image against its own LQ planes
                 res = self.engine.color_fix(res.unsqueeze(0), im.src[:3].unsqueeze(0), self.color_fix)[0]
+            if resizes(self.out_scale, self.sf):   # after the fix, whole images only
+                res = self.engine.resize(res.unsqueeze(0), size=out_size(im.src.shape[1], im.src.shape[2], self.out_scale), clamp=True)[0]
             out[im.id] = res
             del self._images[im.id]
         return out

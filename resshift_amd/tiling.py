@@ -8,6 +8,8 @@ tensors.  Tiles are independent units, so `extra_bs` tiles travel through the sa
 """
 from __future__ import annotations
 
+import math
+from fractions import Fraction
 from typing import List, Tuple
 
 import torch
@@ -43,6 +45,27 @@ COLOR_FIXES = ("none", "wavelet", "adain")
 def check_color_fix(color_fix) -> None:
     if color_fix not in COLOR_FIXES:
         raise ValueError(f"unknown colour fix {color_fix!r} (one of {sorted(COLOR_FIXES)})")
+
+
+def check_out_scale(out_scale, sf) -> None:
+    """`out_scale` of BaseSampler: None, or a positive number with out_scale / sf in [1/8, 8] (rs_resize's range of scales)"""
+    if out_scale is None:
+        return
+    if isinstance(out_scale, bool) or not isinstance(out_scale, (int, float, Fraction)) or not out_scale > 0:
+        raise ValueError(f"out_scale must be None or a positive number, not {out_scale!r}")
+    if not 0.125 <= Fraction(out_scale).limit_denominator(4096) / int(sf) <= 8:
+        raise ValueError(f"out_scale={out_scale!r} is outside [sf / 8, 8 sf] = [{sf / 8:g}, {8 * sf:g}] (the resize holds scales in [1/8, 8])")
+
+
+def resizes(out_scale, sf) -> bool:
+    """does `out_scale` ask for another size than the model's?  None and a value equal to sf issue exactly the launches issued without it"""
+    return out_scale is not None and out_scale != sf
+
+
+def out_size(h_lq, w_lq, out_scale) -> Tuple[int, int]:
+    """(ceil(h_lq * out_scale), ceil(w_lq * out_scale)), exactly: out_scale as the nearest fraction of denominator <= 4096"""
+    f = Fraction(out_scale).limit_denominator(4096)
+    return math.ceil(int(h_lq) * f), math.ceil(int(w_lq) * f)
 
 
 def feather_ramp(pch_size: int, stride: int, sf: int) -> Tuple[int, int]:
