@@ -307,6 +307,36 @@ int rs_color_fix(const float* sr, const float* lq, float* out, int B, int C, int
 int rs_resize(const float* in, float* out, int B, int C, int H, int W, int Ho, int Wo, double scale_h, double scale_w, int clamp,
               void* stream);
 
+/* ---- image metrics: PSNR and SSIM against ground truth -------------------------------------------------
+ * The scores of the restoration literature, as the reference's utils/util_image.py calculate_psnr / calculate_ssim compute them on
+ * uint8 images, for a whole batch in two launches.  Stateless.
+ *   a, b  two batches of one shape; each is either uint8 [B,H,W,C] (x_is_float = 0) or fp32 [B,C,H,W] in [-1,1] (x_is_float = 1), which
+ *         is first quantised exactly as rs_output_to_u8 quantises it (x*0.5+0.5, clamp, *255, round half to even - one device function).
+ *   C is 1 or 3.  ycbcr = 1 (C == 3 only): both images are replaced by MATLAB's rounded luma
+ *         Y = 16 + round((65481 r + 128553 g + 24966 b) / 255000)     in exact integer arithmetic, ties to even.
+ *         (Deviation: the reference evaluates 16 + (65.481 r + 128.553 g + 24.966 b) / 255 in float64 and rounds; at the 194 RGB triples
+ *         whose exact value is a tie, float64 noise - the order of the dot product - decides, and numpy's own paths disagree with each
+ *         other there.  The integer form differs from every float64 form only at those triples.)
+ *   `border` pixels are cropped from every side; the cropped height and width must be >= 11.
+ *   PSNR: sse_out[i] = the sum over the cropped pixels and channels of (a - b)^2, an exact 64-bit integer; the caller forms
+ *         psnr = 20 log10(255 / sqrt(sse / n)), n = channels * cropped height * cropped width, inf at sse == 0.
+ *   SSIM: per channel, with the 11-tap window g[i] = exp(-(i - 5)^2 / 4.5) / sum (sigma = 1.5, fp64), applied along rows and columns
+ *         ("valid": no padding) to a, b, a^2, b^2, ab:   mu1, mu2, s1 = E[a^2] - mu1^2, s2 = E[b^2] - mu2^2, s12 = E[ab] - mu1 mu2,
+ *         map = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)),   C1 = 6.5025, C2 = 58.5225;
+ *         ssim_out[i] = the mean of the map over its (H' - 10)(W' - 10) positions, then the mean over the channels.  All of it in fp64.
+ * sse_out [B] int64 and ssim_out [B] fp64 are device memory.  No floating-point atomics: every sum has an order fixed by the image's
+ * shape, so image i's results are the same bits run to run and whatever else the batch holds.  Identical images give sse 0 and ssim 1.0
+ * exactly.  tests/_metrics_ref.py restates the definition in numpy.
+ * `work`: device scratch of rs_metrics_work_bytes(...) bytes (0 for a geometry rs_metrics refuses), 8-byte aligned.  Argument errors
+ * are found before anything is launched, -2 with rs_last_error() starting "rs_metrics: ": a null pointer, a flag other than 0 or 1, a
+ * non-positive size, C other than 1 or 3, ycbcr without C == 3, a negative border, a cropped image below 11 x 11 (both sizes are
+ * named), a workspace that is too small or misaligned.
+ * rs_rgb_to_y_u8: the same Y as an op of its own, interleaved uint8 [pixels,3] -> uint8 [pixels]. */
+size_t rs_metrics_work_bytes(int B, int C, int H, int W, int border, int ycbcr);
+int rs_metrics(const void* a, const void* b, int a_is_float, int b_is_float, int B, int C, int H, int W, int border, int ycbcr,
+               long long* sse_out, double* ssim_out, void* work, size_t work_bytes, void* stream);
+int rs_rgb_to_y_u8(const uint8_t* rgb_hwc, uint8_t* y, size_t pixels, void* stream);
+
 /* uint8 pre / post processing on the device.
  * rs_u8_to_input:  interleaved uint8 [B,H,W,C] -> planar fp32 [B,C,H,W] in [-1,1]  ((v/255 - 0.5)/0.5; replaces
  *                  datapipe/datasets.py:59-63 ToTensor + Normalize on the host)

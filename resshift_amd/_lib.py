@@ -142,6 +142,9 @@ SIGNATURES = {
     "rs_color_fix_work_bytes": (_SZ, [_I] * 6),
     "rs_color_fix": (_I, [_P, _P, _P] + [_I] * 6 + [_P, _SZ, _P]),
     "rs_resize": (_I, [_P, _P] + [_I] * 6 + [C.c_double, C.c_double, _I, _P]),
+    "rs_metrics_work_bytes": (_SZ, [_I] * 6),
+    "rs_metrics": (_I, [_P, _P] + [_I] * 8 + [_P, _P, _P, _SZ, _P]),
+    "rs_rgb_to_y_u8": (_I, [_P, _P, _SZ, _P]),
     "rs_u8_to_input": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rs_output_to_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rs_arena_bytes": (_SZ, [_P]),
@@ -361,4 +364,63 @@ def resize(x, scale=None, size=None, clamp=False):
         raise ValueError(f"resize: the scales ({sh:.6g}, {sw:.6g}) of {H} x {W} -> {Ho} x {Wo} must lie in [1/8, 8]")
     out = torch.empty((B, Cc, Ho, Wo), device=x.device, dtype=torch.float32)
     check(load().rs_resize(x.data_ptr(), out.data_ptr(), B, Cc, H, W, Ho, Wo, sh, sw, 1 if clamp else 0, current_stream_ptr()), "rs_resize")
+    return out
+
+
+METRICS_TAPS = 11   # the SSIM window: the cropped image must be at least 11 x 11
+
+
+def _metrics_input(t, who):
+    """(is_float, B, C, H, W) of one input of `metrics`: uint8 [B,H,W,C] or float32 [B,C,H,W]"""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4 and t.is_contiguous() and t.dtype in (torch.uint8, torch.float32)):
+        raise ValueError(f"metrics: {who} must be a contiguous device tensor, uint8 [B,H,W,C] or float32 [B,C,H,W] in [-1,1]")
+    if t.dtype == torch.uint8:
+        B, H, W, Cc = t.shape
+        return 0, B, Cc, H, W
+    B, Cc, H, W = t.shape
+    return 1, B, Cc, H, W
+
+
+def metrics(a, b, border=0, ycbcr=True):
+    """rs_metrics: PSNR / SSIM of the image batch `a` against `b` on uint8 pixels (include/resshift_hip.h "image metrics").  Each input is a
+    contiguous device tensor, uint8 [B,H,W,C] or float32 [B,C,H,W] in [-1,1] (quantised as rs_output_to_u8 does); C is 1 or 3; `ycbcr`
+    (C == 3) scores MATLAB's Y channel; `border` pixels are cropped from every side and at least 11 x 11 must remain.  Returns
+    {"psnr": float64 [B], "ssim": float64 [B], "sse": int64 [B]} on the device: sse and ssim come from the kernels, psnr =
+    20 log10(255 / sqrt(sse / n)) from float64 torch ops on sse (inf at sse == 0) - nothing waits for the stream."""
+    fa, B, Cc, H, W = _metrics_input(a, "a")
+    fb, *shape_b = _metrics_input(b, "b")
+    if tuple(shape_b) != (B, Cc, H, W):
+        raise ValueError(f"metrics: a is {B} images of {H} x {W} x {Cc}, b is {shape_b[0]} images of {shape_b[2]} x {shape_b[3]} x {shape_b[1]}")
+    if Cc not in (1, 3):
+        raise ValueError(f"metrics: C must be 1 or 3, not {Cc}")
+    if isinstance(border, bool) or not isinstance(border, int) or border < 0:
+        raise ValueError(f"metrics: border must be a non-negative integer, not {border!r}")
+    ycbcr = bool(ycbcr)
+    if ycbcr and Cc != 3:
+        raise ValueError(f"metrics: ycbcr=True needs C == 3, not {Cc}")
+    Hc, Wc = H - 2 * border, W - 2 * border
+    if Hc < METRICS_TAPS or Wc < METRICS_TAPS:
+        raise ValueError(f"metrics: the cropped image is {Hc} x {Wc} ({H} x {W}, border {border}): the 11 x 11 window needs at least 11 x 11")
+    if a.device != b.device:
+        raise ValueError(f"metrics: a is on {a.device}, b on {b.device}")
+    lib = load()
+    need = int(lib.rs_metrics_work_bytes(B, Cc, H, W, border, int(ycbcr)))
+    work = torch.empty(need // 8, device=a.device, dtype=torch.int64)
+    sse = torch.empty(B, device=a.device, dtype=torch.int64)
+    ssim = torch.empty(B, device=a.device, dtype=torch.float64)
+    check(lib.rs_metrics(a.data_ptr(), b.data_ptr(), fa, fb, B, Cc, H, W, border, int(ycbcr), sse.data_ptr(), ssim.data_ptr(), work.data_ptr(),
+                         need, current_stream_ptr()), "rs_metrics")
+    n = (1 if ycbcr else Cc) * Hc * Wc
+    psnr = 20.0 * torch.log10(255.0 / torch.sqrt(sse.to(torch.float64) / n))
+    return {"psnr": psnr, "ssim": ssim, "sse": sse}
+
+
+def rgb_to_y(rgb):
+    """rs_rgb_to_y_u8: uint8 [...,3] (a contiguous device tensor) -> uint8 [...]: MATLAB's rounded luma, 16 + round((65481 r + 128553 g +
+    24966 b) / 255000) in exact integer arithmetic, ties to even"""
+    if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.is_contiguous() and rgb.dim() >= 1
+            and rgb.shape[-1] == 3 and rgb.numel() > 0):
+        raise ValueError("rgb_to_y: rgb must be a non-empty contiguous uint8 device tensor [...,3]")
+    out = torch.empty(rgb.shape[:-1], device=rgb.device, dtype=torch.uint8)
+    check(load().rs_rgb_to_y_u8(rgb.data_ptr(), out.data_ptr(), rgb.numel() // 3, current_stream_ptr()), "rs_rgb_to_y_u8")
     return out

@@ -88,6 +88,23 @@ __device__ __forceinline__ float rs_sum16(float v) {
 }
 
 // ---- device helpers -------------------------------------------------------
+// THE quantiser of a [0,1] value to a uint8 pixel (utils/util_image.py:245-269 tensor2img): clamp, * 255, round half to even.  The
+// non-contracting intrinsic rounds like the reference's separate ops.  rs_output_to_u8 and the float inputs of rs_metrics share it.
+__device__ __forceinline__ unsigned char rs_unit_to_u8(float v) {
+    v = fminf(fmaxf(v, 0.0f), 1.0f);
+    return (unsigned char)rintf(__fmul_rn(v, 255.0f));
+}
+// a [-1,1] sample to its uint8 pixel: x * 0.5 + 0.5 (unfused), then rs_unit_to_u8 - rs_output_to_u8 without the inpainting blend
+__device__ __forceinline__ unsigned char rs_sample_to_u8(float x) { return rs_unit_to_u8(__fadd_rn(__fmul_rn(x, 0.5f), 0.5f)); }
+// MATLAB's rgb2ycbcr Y of a uint8 pixel: 16 + round((65481 r + 128553 g + 24966 b) / 255000) in exact integer arithmetic, ties to even
+// (include/resshift_hip.h "image metrics"); 16 .. 235
+__device__ __forceinline__ unsigned char rs_rgb_to_y(int r, int g, int b) {
+    const int n = 65481 * r + 128553 * g + 24966 * b;   // <= 55 845 000
+    int q = n / 255000;
+    const int twice = 2 * (n - q * 255000);
+    q += (twice > 255000 || (twice == 255000 && (q & 1))) ? 1 : 0;
+    return (unsigned char)(16 + q);
+}
 __device__ __forceinline__ float rs_silu(float x) { return x / (1.0f + __expf(-x)); }
 // exact-erf GELU (nn.GELU() default; reference models/swin_transformer.py:18)
 __device__ __forceinline__ float rs_gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }

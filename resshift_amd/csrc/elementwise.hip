@@ -499,9 +499,8 @@ __global__ void output_to_u8_kernel(const float* __restrict__ sr, const float* _
                 const float l = __fadd_rn(__fmul_rn(lq[(b * C + c) * HW + hw], 0.5f), 0.5f);
                 v = __fadd_rn(__fmul_rn(v, m), __fmul_rn(l, __fsub_rn(1.0f, m)));
             }
-            v = fminf(fmaxf(v, 0.0f), 1.0f);
             const int oc = (bgr && C == 3) ? 2 - c : c;
-            dst[i * C + oc] = (unsigned char)rintf(__fmul_rn(v, 255.0f));
+            dst[i * C + oc] = rs_unit_to_u8(v);
         }
     }
 }

@@ -211,6 +211,20 @@ class Engine:
         with torch.cuda.device(self.device):
             return _lib.resize(self._f32c(x), scale=scale, size=size, clamp=clamp)
 
+    def metrics(self, sr, gt, border=0, ycbcr=True):
+        """PSNR / SSIM of the batch `sr` against the ground truth `gt` on uint8 pixels, as the reference's calculate_psnr / calculate_ssim
+        score them (rs_metrics).  Each is uint8 [B,H,W,C] or a float tensor [B,C,H,W] in [-1,1], which is quantised exactly
+        as `output_to_u8` does; C is 1 or 3; `ycbcr` scores MATLAB's Y channel (C == 3); `border` pixels are cropped from every side.
+        Returns {"psnr": float64 [B], "ssim": float64 [B], "sse": int64 [B]} on the device."""
+        prep = lambda t: t.contiguous() if t.dtype == torch.uint8 else self._f32c(t)
+        with torch.cuda.device(self.device):
+            return _lib.metrics(prep(sr), prep(gt), border=border, ycbcr=ycbcr)
+
+    def rgb_to_y(self, u8):
+        """uint8 [...,3] device tensor -> uint8 [...]: MATLAB's rounded Y channel in exact integer arithmetic (rs_rgb_to_y_u8)"""
+        with torch.cuda.device(self.device):
+            return _lib.rgb_to_y(u8.contiguous())
+
     def axpbypcz(self, x, z, n, a, b, c, out=None):
         """out = a*x + b*z + c*n elementwise on fp32 tensors of identical layout (z, n optional)."""
         x = self._f32c(x)

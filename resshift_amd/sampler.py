@@ -278,7 +278,55 @@ class ResShiftSampler(BaseSampler):
 
     POOL_LOOKAHEAD = 128   # inference(pool=True) reads files ahead until this many tiles wait for a slot
 
-    def inference(self, in_path, out_path, mask_path=None, mask_back=True, bs=1, noise_repeat=False, pool=False, seeded=False):
+    # ------------------------------------------------------------------ scores against ground truth
+    @staticmethod
+    def _gt_file(gt_path, p, single) -> Path:
+        """the ground truth of the input file `p`: looked up by file name in the directory `gt_path`; for a single input file `gt_path` is
+        the file itself (the rule of `mask_path`)"""
+        g = Path(gt_path) if single else Path(gt_path) / Path(p).name
+        if not g.is_file():
+            raise FileNotFoundError(f"no ground truth for {Path(p).name}: {g} is not a file")
+        return g
+
+    def _score(self, out_u8, files, gt_path, single, border, ycbcr) -> dict:
+        """{stem: (psnr, ssim)} of the uint8 device batch out_u8 [n,H,W,C] - the very pixels that become the PNGs of `files` - against
+        their ground-truth files: read on the host, scored on the device (Engine.metrics).  A gray output is its own luma."""
+        gray = out_u8.shape[3] == 1
+        gts = []
+        for p, im in zip(files, out_u8):
+            g = self._read_image_u8(self._gt_file(gt_path, p, single), gray=gray)
+            if tuple(g.shape) != tuple(im.shape):
+                raise ValueError(f"the ground truth of {Path(p).name} is {g.shape[0]} x {g.shape[1]}, the output is {im.shape[0]} x {im.shape[1]}")
+            gts.append(g)
+        m = self.engine.metrics(out_u8, torch.stack(gts).to(self.device), border=border, ycbcr=bool(ycbcr) and not gray)
+        psnr, ssim = m["psnr"].cpu().tolist(), m["ssim"].cpu().tolist()
+        return {Path(p).stem: (float(a), float(b)) for p, a, b in zip(files, psnr, ssim)}
+
+    @staticmethod
+    def _write_metrics(out_path, rows) -> tuple:
+        """out_path/metrics.csv: name,psnr,ssim - one row per image sorted by name, then the row `mean`; returns the two means"""
+        names = sorted(rows)
+        mean = tuple(float(np.mean([rows[k][i] for k in names])) if names else float("nan") for i in (0, 1))
+        with open(Path(out_path) / "metrics.csv", "w") as fh:
+            fh.write("name,psnr,ssim\n")
+            for k in names:
+                fh.write(f"{k},{rows[k][0]!r},{rows[k][1]!r}\n")
+            fh.write(f"mean,{mean[0]!r},{mean[1]!r}\n")
+        return mean
+
+    def _finish_metrics(self, out_path, rows) -> dict:
+        """the rows of every rank combined (all_gather_object); rank 0 writes metrics.csv and logs the means; every rank returns all rows"""
+        if self.num_gpus > 1 and dist.is_available() and dist.is_initialized():
+            parts = [None] * dist.get_world_size()
+            dist.all_gather_object(parts, rows)
+            rows = {k: v for part in parts for k, v in part.items()}
+        if self.rank == 0:
+            mean = self._write_metrics(out_path, rows)
+            self.write_log(f"{len(rows)} images against ground truth: mean PSNR {mean[0]:.4f} dB, mean SSIM {mean[1]:.6f} ({Path(out_path) / 'metrics.csv'})")
+        return rows
+
+    def inference(self, in_path, out_path, mask_path=None, mask_back=True, bs=1, noise_repeat=False, pool=False, seeded=False, gt_path=None,
+                  metric_border=0, metric_ycbcr=True):
         """sampler.py:167-308: batches of `bs` images are sharded over the ranks exactly like sampler.py:273-277; every
         rank writes its own PNGs.  uint8 -> [-1,1] (datapipe/datasets.py:59-63), the inpainting blend (sampler.py:218-222)
         and the final clamp / round to uint8 (utils/util_image.py:245-269) run on the device (rs_u8_to_input /
@@ -289,7 +337,13 @@ class ResShiftSampler(BaseSampler):
         `seeded=True` (with and without `pool`): the image at position i of the sorted listing of the whole input gets the seed
         `image_seed(i)`, its tile j the stream j - the noise of a file does not depend on the number of ranks, on `bs` or
         on `pool`, so neither do the PNGs beyond the engine's own batch-size sensitivity.  Excludes `noise_repeat`.
-        The sampler's `color_fix` and `out_scale` reach every image through `sample_tiled` resp. the `TilePool`; they exclude `mask_path`."""
+        The sampler's `color_fix` and `out_scale` reach every image through `sample_tiled` resp. the `TilePool`; they exclude `mask_path`.
+        `gt_path` (None: nothing changes, None is returned): every image is scored against its ground truth - the file of the same name in
+        that directory, or `gt_path` itself for a single input file - on the device, from the very uint8 tensor that becomes its PNG (after
+        the inpainting blend, the colour fix and `out_scale`): PSNR and SSIM as the reference's calculate_psnr / calculate_ssim compute
+        them (Engine.metrics), `metric_border` pixels cropped, on MATLAB's Y channel when `metric_ycbcr`.  Returns
+        {stem: (psnr, ssim)} for the whole input on every rank; rank 0 writes out_path/metrics.csv.  A missing ground-truth file raises
+        FileNotFoundError before anything is sampled, one of another size than the output ValueError."""
         if seeded and noise_repeat:
             raise ValueError("seeded=True names every draw by (seed, stream): it excludes noise_repeat")
         fix = getattr(self, "color_fix", "none")
@@ -312,12 +366,22 @@ class ResShiftSampler(BaseSampler):
             files = [p for e in exts for p in sorted(in_path.glob(f"**/*.{e}"))]
         from PIL import Image
 
+        rows = None
+        if gt_path is not None:
+            if isinstance(metric_border, bool) or not isinstance(metric_border, int) or metric_border < 0:
+                raise ValueError(f"metric_border must be a non-negative integer, not {metric_border!r}")
+            for p in files:
+                self._gt_file(gt_path, p, single)
+            rows = {}
+        score = (lambda u8, fs: rows.update(self._score(u8, fs, gt_path, single, metric_border, metric_ycbcr))) if rows is not None else None
         micro = math.ceil(bs / self.num_gpus)   # sampler.py:274-277: the slice width comes from bs, also on the last, partial batch
         if pool:
-            self._inference_pool(files, out_path, mask_path, mask_back, bs, micro, single, noise_repeat, seeded)
+            self._inference_pool(files, out_path, mask_path, mask_back, bs, micro, single, noise_repeat, seeded, **({"score": score} if score else {}))
             sharding.barrier()
+            if rows is not None:
+                rows = self._finish_metrics(out_path, rows)
             self.write_log(f"Processing done, enjoy the results in {out_path}")
-            return
+            return rows
         for b0 in range(0, len(files), bs):
             batch = files[b0:b0 + bs]
             mine = batch[self.rank * micro:(self.rank + 1) * micro]
@@ -335,13 +399,19 @@ class ResShiftSampler(BaseSampler):
                 else:
                     sr = self.sample_tiled(lq, mask=mask, noise_repeat=noise_repeat)
                 blend = mask is not None and mask_back
-                out_u8 = self.engine.output_to_u8(sr, lq=lq if blend else None, mask=mask if blend else None).cpu().numpy()
+                out_u8 = self.engine.output_to_u8(sr, lq=lq if blend else None, mask=mask if blend else None)
+                if score is not None:
+                    score(out_u8, mine)
+                out_u8 = out_u8.cpu().numpy()
                 for p, im in zip(mine, out_u8):
                     Image.fromarray(im if im.shape[2] != 1 else im[:, :, 0]).save(out_path / f"{p.stem}.png")
         sharding.barrier()
+        if rows is not None:
+            rows = self._finish_metrics(out_path, rows)
         self.write_log(f"Processing done, enjoy the results in {out_path}")
+        return rows
 
-    def _inference_pool(self, files, out_path, mask_path, mask_back, bs, micro, single, noise_repeat, seeded=False):
+    def _inference_pool(self, files, out_path, mask_path, mask_back, bs, micro, single, noise_repeat, seeded=False, score=None):
         from PIL import Image
 
         from .tilepool import TilePool
@@ -355,7 +425,10 @@ class ResShiftSampler(BaseSampler):
             for rid, sr in done.items():
                 p, lq, mask = kept.pop(rid)
                 blend = mask is not None and mask_back
-                im = self.engine.output_to_u8(sr.unsqueeze(0), lq=lq if blend else None, mask=mask if blend else None)[0].cpu().numpy()
+                u8 = self.engine.output_to_u8(sr.unsqueeze(0), lq=lq if blend else None, mask=mask if blend else None)
+                if score is not None:
+                    score(u8, [p])
+                im = u8[0].cpu().numpy()
                 Image.fromarray(im if im.shape[2] != 1 else im[:, :, 0]).save(out_path / f"{p.stem}.png")
 
         for b0 in range(0, len(files), bs):
