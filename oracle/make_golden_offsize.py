@@ -9,9 +9,11 @@ sampler.py:186-208, inference_resshift.py:149-161).  What changes with the size,
   * the autoencoder's global attention over T = h*w tokens (ldm/modules/diffusionmodules/model.py:179-203).
 
 Produced by the UNMODIFIED reference modules (imported from /root/reference); the oracle restatement is asserted against every
-output in the same run.  Stored: tests/golden/reference_offsize.npz.
+output in the same run.  Stored: tests/golden/reference_offsize.npz, and - the headline network on the two smallest non-square planes
+its four levels and 8-pixel windows allow, 64 x 128 and 128 x 64, one UNet forward each - tests/golden/reference_nonsquare.npz.
 
-    python -m oracle.make_golden_offsize          (build container only: needs /root/reference)
+    python -m oracle.make_golden_offsize              (build container only: needs /root/reference; writes reference_offsize.npz)
+    python -m oracle.make_golden_offsize nonsquare    (writes reference_nonsquare.npz only, and leaves reference_offsize.npz alone)
 """
 from __future__ import annotations
 
@@ -56,6 +58,15 @@ def case_inputs(tag):
 
 def realsr_inputs(steps):
     return synth.synthetic_inputs(SEED_X, 1, REALSR_SIDE, REALSR_SIDE, 3, REALSR_SIDE, REALSR_SIDE, steps)
+
+NONSQUARE = ((64, 128), (128, 64))   # latent h x w of the realsr network's non-square forwards (B = 1, t = 7)
+
+
+def nonsquare_inputs(h, w, steps):
+    """(x, lq) of the realsr UNet forward at the latent size h x w, in the style of realsr_inputs (sf = 4 and the f4 autoencoder: the lq
+    has the latent's size); seeded per size"""
+    y, noises, _ = synth.synthetic_inputs(SEED_X + 1000 * h + w, 1, h, w, 3, h, w, steps)
+    return noises[1] * 1.3, y
 
 
 def tiled_inputs(steps):
@@ -163,5 +174,29 @@ def main():
     print(f"wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB, {len(out)} arrays)")
 
 
+def main_nonsquare():
+    """realsr UNetModelSwin (constructed for 64 x 64) on 64 x 128 and 128 x 64, B = 1, t = 7: the unmodified reference modules' outputs"""
+    torch.manual_seed(0)
+    torch.set_grad_enabled(False)
+    U, V, _ = ref_import.load()
+    cfg = to_plain(load_config("realsr_swinunet_realesrgan256"))
+    up, ap, dp = cfg["model"]["params"], cfg["autoencoder"]["params"], cfg["diffusion"]["params"]
+    usd, _, um, _ = build(U, V, up, ap)
+    out = {}
+    for h, w in NONSQUARE:
+        print(f"[realsr @ {h} x {w}]")
+        x, y = nonsquare_inputs(h, w, dp["steps"])
+        ref_u = um(x, torch.tensor([7]), lq=y)
+        got = oc.unet_forward(usd, up, x, torch.tensor([7]), lq=y)
+        check(f"realsr{h}x{w}/unet", got, ref_u, 2e-5)
+        rel = (got - ref_u).abs().max().item() / ref_u.abs().max().item()
+        assert rel < 2e-5, rel   # (what tests/test_oracle.py asserts: relative to the output's own scale)
+        assert tuple(ref_u.shape) == (1, 3, h, w) and ref_u.dtype == torch.float32
+        out[f"realsr{h}x{w}/unet"] = ref_u.numpy()
+    path = os.path.join(GOLD, "reference_nonsquare.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB, {len(out)} arrays)")
+
+
 if __name__ == "__main__":
-    main()
+    main_nonsquare() if sys.argv[1:] == ["nonsquare"] else main()

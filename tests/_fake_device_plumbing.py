@@ -1,7 +1,8 @@
 """Helper of test_dry_and_real_pass_agree_without_a_gpu / test_launch_mix_is_pinned_without_a_gpu (tests/test_host_cpu.py): one rs_sample call with RS_FAKE_DEVICE=1 - the engine's real
 pass walks its whole control flow on a host-memory arena while every launch simply fails (there is no GPU), and prints what the dry
 sizing pass and the real pass each counted: coefficient-pool bytes, GroupNorm-tail tickets, producer / GroupNorm sequence numbers,
-kernel launches; then the launch mix of the call (per kernel family, igemm path, GroupNorm).  Usage: _fake_device_plumbing.py <config yaml name> <batch> <precision 0 fp16 | 1 fp32 | 2 split>"""
+kernel launches; then the launch mix of the call (per kernel family, igemm path, GroupNorm).  Usage: _fake_device_plumbing.py <config yaml name> <batch> <precision 0 fp16 | 1 fp32 | 2 split> [<LR h> <LR w>]
+(the LR size defaults to the config's own square one)"""
 import os, sys, ctypes as C
 os.environ["RS_FAKE_DEVICE"]="1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,7 +27,8 @@ d=create_gaussian_diffusion(**dp); tables=d.step_tables(); steps=len(tables["coe
 a=_lib.SampleArgs()
 a.y=a.noise=a.out=4096; a.mask=4096 if up.get("cond_mask") else None
 lr={"realsr_swinunet_realesrgan256":64,"faceir_gfpgan512_lpips":512,"inpaint_lama256_imagenet":256}.get(cname,64)
-a.B,a.h,a.w,a.sf,a.steps=B,lr,lr,int(d.sf),steps
+lh,lw=(int(sys.argv[4]),int(sys.argv[5])) if len(sys.argv)>5 else (lr,lr)
+a.B,a.h,a.w,a.sf,a.steps=B,lh,lw,int(d.sf),steps
 for t in range(steps):
     a.inv_std[t]=float(tables["inv_std"][t]); a.coef1[t]=float(tables["coef1"][t]); a.coef2[t]=float(tables["coef2"][t]); a.sigma[t]=float(tables["sigma"][t]); a.tmap[t]=int(tables["tmap"][t]); a.prec_unet[t]=prec
 a.prior_scale=float(tables["prior_scale"]); a.scale_factor=float(d.scale_factor); a.prec_encode=prec; a.prec_decode=0

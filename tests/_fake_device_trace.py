@@ -2,7 +2,8 @@
 bookkeeping of the dry and the real pass does not - see _fake_device_plumbing.py), untraced and then traced, at mixed per-image timesteps.
 Prints the engine's "[fake device]" line of each call on stderr, one "CALL <untraced|traced> rc <rc> launches <n> records <n>" line per
 call and one "REC <name> <B> <C> <H> <W>" line per debug-trace record of the traced call.
-Usage: _fake_device_trace.py <config yaml name> <batch> <precision 0 fp16 | 1 fp32 | 2 split>"""
+Usage: _fake_device_trace.py <config yaml name> <batch> <precision 0 fp16 | 1 fp32 | 2 split> [<latent h> <latent w>]
+(the latent size defaults to the config's image_size; the lq / mask size follows from it by the config's lq_size / image_size ratio)"""
 import ctypes as C
 import os
 import sys
@@ -28,11 +29,13 @@ assert h
 lib.rs_bind_weight_blob(h, 256 * 1024, lib.rs_weight_bytes(h))   # fake, aligned address: never dereferenced on the host
 assert lib.rs_weights_ready(h) == 0
 hz, hl = int(up["image_size"]), int(up["lq_size"])
+zh, zw = (int(sys.argv[4]), int(sys.argv[5])) if len(sys.argv) > 5 else (hz, hz)
+lh, lw = zh * hl // hz, zw * hl // hz
 ts = (C.c_int * B)(*[(7 * b) % 15 for b in range(B)])
 mask = 4096 if up.get("cond_mask") else None
 for name in ("untraced", "traced"):
     lib.rs_debug_enable(h, int(name == "traced"))
-    rc = lib.rs_unet_forward(h, 4096, ts, 4096, mask, 4096, B, hz, hz, hl, hl, prec, None)
+    rc = lib.rs_unet_forward(h, 4096, ts, 4096, mask, 4096, B, zh, zw, lh, lw, prec, None)
     sys.stderr.flush()
     print(f"CALL {name} rc {rc} launches {lib.rs_last_launch_count(h)} records {lib.rs_debug_count(h)}", flush=True)
 buf = C.create_string_buffer(128)

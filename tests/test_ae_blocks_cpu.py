@@ -162,7 +162,8 @@ def test_plans_in_float64(tag):
     print(f"{tag}: float64 plans vs fp32 oracle, worst step {worst:.2e}")
 
 
-@pytest.mark.parametrize("key,B,h,w", [("realsr", 32, 64, 64), ("realsr", 3, 64, 64), ("realsr", 2, 40, 24), ("faceir", 16, 64, 64)])
+@pytest.mark.parametrize("key,B,h,w", [("realsr", 32, 64, 64), ("realsr", 3, 64, 64), ("realsr", 2, 40, 24), ("faceir", 16, 64, 64),
+                                       ("realsr", 1, 64, 128)])
 def test_fp32_oracle_argmin_meets_the_cap_against_float64(key, B, h, w):
     """The GPU test lets an index differ from the float64 argmin where the float64 distances are within a few fp32 roundings of each other,
     but caps the share of differing positions at 0.1 % per image.  On the very latents it uses, the fp32 CPU oracle - the reference's own
@@ -196,7 +197,10 @@ def _plan_dims(cname, call, B, Hh, Ww):
 FAKE = [("realsr", "encode", 32, 256, 256, 2), ("realsr", "encode", 32, 256, 256, 0), ("realsr", "decode", 32, 64, 64, 0),
         ("realsr", "decode", 32, 64, 64, 2), ("realsr", "decode", 32, 64, 64, 1), ("realsr", "encode", 3, 256, 256, 2),
         ("realsr", "decode", 3, 64, 64, 0), ("realsr", "decode", 2, 40, 24, 0), ("realsr", "decode_nq", 2, 64, 64, 0),
-        ("faceir", "encode", 16, 512, 512, 2), ("faceir", "decode", 16, 64, 64, 0)]
+        ("faceir", "encode", 16, 512, 512, 2), ("faceir", "decode", 16, 64, 64, 0),
+        # the tile pool's size classes and batch 1 (the rows tests/test_ae_blocks_gpu.py adds to the square bench shapes)
+        ("realsr", "encode", 1, 256, 512, 2), ("realsr", "decode", 1, 64, 128, 0), ("realsr", "decode", 6, 128, 64, 0),
+        ("realsr", "decode", 1, 128, 128, 0), ("realsr", "decode", 1, 64, 128, 2)]
 
 
 @pytest.mark.parametrize("key,call,B,Hh,Ww,prec", FAKE, ids=[f"{k}-{c}-B{b}-{h}x{w}-p{p}" for k, c, b, h, w, p in FAKE])

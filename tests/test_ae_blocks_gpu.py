@@ -7,7 +7,7 @@ materialised softmax, GroupNorm tails and epilogue statistics, the fused head, t
 padded to 8.  A traced Engine.vq_encode / vq_decode (Engine.debug_enable) runs that same graph - the test asserts it: same output bits, same
 launch count - and records every block boundary.  Each block of the plan (oracle/resshift_oracle.py: ae_encode_plan / ae_decode_plan) is
 then fed the engine's own recorded inputs in float64 and compared with the engine's output of that block, per image: max |engine - ref| /
-max |ref| over the image's block output, for up to 8 images spread over the batch.  Every case also asserts, from the families of the traced
+max |ref| over the image's block output, for up to 8 images spread over the batch (8 * 64 * 64 latent pixels in all).  Every case also asserts, from the families of the traced
 pass and the launch shapes of a profiled pass, that it ran the kernels it is there for.  Run with -s for the table of the worst error per
 block and precision.
 
@@ -54,7 +54,15 @@ CASES = [("realsr", "encode", 32, 256, 256, "split", "flash_split", (), ()),
          ("faceir", "decode", 16, 64, 64, "fp16", "flash16", (3, 2, 1), ()),
          ("realsr", "decode", 2, 40, 24, "fp16", "rows", (), (2, 1)),
          ("realsr", "decode", 2, 40, 24, "split", "flash_split", (), (2, 1)),
-         ("realsr", "decode_nq", 2, 64, 64, "fp16", "flash16", (1,), (2,))]
+         ("realsr", "decode_nq", 2, 64, 64, "fp16", "flash16", (1,), (2,)),
+         # what the tile pool and the default tiled path (chop_size 128, chop_bs 1) hand the autoencoder: non-square size classes, batch 1, a
+         # plane larger than the constructed one.  Decode at batch 1: 64 x 128 has 8192 low-resolution pixels at level 2 (folded form) and
+         # 32768 at level 1; 128 x 128 has exactly 16384 at level 2, the threshold of the sub-pixel form, and T = 16384 tokens of attention
+         ("realsr", "encode", 1, 256, 512, "split", "flash_split", (), ()),
+         ("realsr", "decode", 1, 64, 128, "fp16", "flash16", (1,), (2,)),
+         ("realsr", "decode", 6, 128, 64, "fp16", "flash16", (2, 1), ()),
+         ("realsr", "decode", 1, 128, 128, "fp16", "flash16", (2, 1), ()),
+         ("realsr", "decode", 1, 64, 128, "split", "flash_split", (1,), (2,))]
 # Per-image tolerance of every block, per precision: the per-block tolerances of tests/test_unet_blocks_gpu.py (the same kernel families;
 # the longest reduction here is 9 x 512 products against 9 x 640 there).  For scale, on the CPU (one realsr decoder pass, every block
 # teacher-forced): the fp32 oracle is within 3.4e-7 of float64 on every block, a model of fp16 storage (float64 arithmetic; weights, conv1
@@ -66,6 +74,9 @@ CASES = [("realsr", "encode", 32, 256, 256, "split", "flash_split", (), ()),
 # enc.down.1.ds: 3.2e-6 / 2.9e-6 / 2.9e-6, dec.mid.block_1 2.7e-6, every other block <= 2.0e-6).  VQ: at most 1 position of an image's
 # 4096 (2.4e-4) differs from the float64 argmin, within the fp32-rounding slack, in split and fp16 decodes alike - the worst image of the
 # fp32 CPU oracle differs in one position too.
+# The tile pool's shapes (the last five CASES: non-square, batch 1, a 128 x 128 latent) keep these bounds.  Measured over them: split 3.29e-6
+# (enc.out, encode 256 x 512; decode 64 x 128: 1.78e-6, dec.head), fp16 5.76e-4 (dec.up.0.block.0, B = 6 at 128 x 64; 5.4e-4 / 5.1e-4 at batch 1
+# on 64 x 128 / 128 x 128).  VQ: at most 1 position of an image's 8192 (1.2e-4) differs from the float64 argmin.
 TOL = {"split": 5e-6, "fp16": 2.5e-3, "fp32": 1e-5}
 F_AEFLASH, F_AEFLASH_S = 9, 10   # Engine.FAMILIES
 
@@ -102,9 +113,10 @@ def _model(key, gpu):
     return _models[key]
 
 
-def _pick(B):
-    """8 images spread over the batch, the first and the last included (all of a smaller batch)"""
-    return sorted(set(int(v) for v in np.linspace(0, B - 1, min(8, B)).round()))
+def _pick(B, h=64, w=64):
+    """images spread over the batch, the first and the last included, as many as the budget of 8 * 64 * 64 latent pixels allows: 8 at a 64 x 64
+    latent, 4 at 64 x 128, 2 at 128 x 128 (all of a smaller batch)"""
+    return sorted(set(int(v) for v in np.linspace(0, B - 1, min(B, max(2, 8 * 64 * 64 // (h * w)))).round()))
 
 
 def _launches(shapes, part, M, N, K):
@@ -210,7 +222,8 @@ def test_every_autoencoder_block_against_float64(gpu, key, call, B, h, w, prec, 
             run = lambda: eng.vq_decode(x.to(gpu), prec=p, return_indices=True)
         else:
             run = lambda: (eng.vq_decode(x.to(gpu), force_not_quantize=True, prec=p), None)
-    pick = _pick(B)
+    f = 2 ** (len(ap["ddconfig"]["ch_mult"]) - 1)
+    pick = _pick(B, *((h // f, w // f) if call == "encode" else (h, w)))
     want = [s.name for s in plan] + ["dec.zq.z"]
 
     # the same pass untraced and traced: same bits, same network launches
@@ -251,10 +264,15 @@ def test_every_autoencoder_block_against_float64(gpu, key, call, B, h, w, prec, 
 
     host = {hname: x[pick]}
     idx_p = idx.view(B, -1)[pick].cpu() if call == "decode" else None
-    failures, missing = check_blocks(plan, host, trace, out[pick].cpu(), idx_p, asd, sd64, pick, prec, TOL[prec], _worst)
+    own = {}
+    failures, missing = check_blocks(plan, host, trace, out[pick].cpu(), idx_p, asd, sd64, pick, prec, TOL[prec], own)
+    for k, v in own.items():
+        _worst[k] = max(_worst.get(k, 0.0), v) if np.isfinite(v) else v
+    own_e, own_n = max(((v, n) for (n, _), v in own.items() if not n.startswith("dec.idx")), default=(0.0, "-"))
     worst = max((v for (n, pp), v in _worst.items() if pp == prec and not n.startswith("dec.idx")), default=0.0)
     print(f"\n{key} {call} B={B} {h}x{w} {prec}: {len(plan)} blocks x {len(pick)} images, {n_traced} launches, {len(recs)} records, capture region "
-          f"{cap / 2 ** 30:.2f} GiB, worst {prec} error so far {worst:.3e}")
+          f"{cap / 2 ** 30:.2f} GiB, worst error of this case {own_e:.3e} ({own_n}), VQ positions differing {own.get(('dec.idx (differ)', prec), 0.0):.2e}, "
+          f"worst {prec} error so far {worst:.3e}")
     assert not missing, f"blocks of the plan missing from the trace: {missing}"
     assert not failures, "\n".join(failures[:40])
     if kernels is not None:

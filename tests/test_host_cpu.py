@@ -465,9 +465,20 @@ def test_bench_launcher_pieces(monkeypatch):
     assert r.returncode != 0 and "refused" in r.stderr
 
 
-@pytest.mark.parametrize("cname,B,prec", [("realsr_swinunet_realesrgan256", 32, 2), ("realsr_swinunet_realesrgan256", 4, 0),
-                                          ("inpaint_lama256_imagenet", 16, 2), ("faceir_gfpgan512_lpips", 2, 2)])
-def test_dry_and_real_pass_agree_without_a_gpu(cname, B, prec):
+# (config, batch, precision, LR size - None: the config's own square one); the last three rows: two size classes of the tile pool and its default tile
+DRY = [("realsr_swinunet_realesrgan256", 32, 2, None), ("realsr_swinunet_realesrgan256", 4, 0, None), ("inpaint_lama256_imagenet", 16, 2, None),
+       ("faceir_gfpgan512_lpips", 2, 2, None), ("realsr_swinunet_realesrgan256", 8, 2, (64, 128)), ("realsr_swinunet_realesrgan256", 1, 2, (128, 128)),
+       ("realsr_swinunet_realesrgan256", 6, 0, (128, 64))]
+
+
+def _row_id(c, b, p, lr, *rest):
+    """the id pytest itself gives (config, batch, precision, ...), with the LR size put behind the precision where a row has one"""
+    rest = [f"families{rest[1]}" if k == 1 else str(v) for k, v in enumerate(rest)]
+    return "-".join([c, str(b), str(p)] + ([f"{lr[0]}x{lr[1]}"] if lr else []) + rest)
+
+
+@pytest.mark.parametrize("cname,B,prec,lr", DRY, ids=[_row_id(*r) for r in DRY])
+def test_dry_and_real_pass_agree_without_a_gpu(cname, B, prec, lr):
     """Round 4: the GroupNorm tail plan (resshift_amd/csrc/gn_tail.h, graphs.h: TailPlan) is made by the engine's dry sizing pass and
     executed by its real pass; the two walk the same control flow and must agree about every pool they size: coefficient pool, tickets,
     producer and GroupNorm sequence numbers - and every planned tail must be attached to its producer's launch.  RS_FAKE_DEVICE=1 lets the
@@ -481,15 +492,15 @@ def test_dry_and_real_pass_agree_without_a_gpu(cname, B, prec):
     from resshift_amd import build as _b
 
     env = dict(os.environ, RS_FAKE_DEVICE="1", RESSHIFT_HIP_LIB=_b.build_testhooks(), **NO_GPU)
-    r = subprocess.run([sys.executable, os.path.join(H.ROOT, "tests", "_fake_device_plumbing.py"), cname, str(B), str(prec)], env=env,
-                       capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(H.ROOT, "tests", "_fake_device_plumbing.py"), cname, str(B), str(prec)] +
+                       [str(v) for v in lr or ()], env=env, capture_output=True, text=True, timeout=600)
     m = re.search(r"dry: tickets (\d+) pool (\d+) prod (\d+) gn (\d+) \| real: tickets (\d+) pool (\d+) prod (\d+) gn (\d+) launches (\d+)", r.stderr)
     assert m, (r.stdout[-500:], r.stderr[-1500:])
     v = [int(x) for x in m.groups()]
     assert v[:4] == v[4:8], v
     assert "never attached" not in r.stderr and "disagree" not in r.stdout, (r.stdout[-500:], r.stderr[-500:])
     assert v[0] > 0 and v[1] > 0          # tails were planned at all
-    if cname.startswith("realsr") and B == 32 and prec == 2:
+    if cname.startswith("realsr") and B == 32 and prec == 2 and lr is None:
         # (round 5: 2 592 with the three folds; + 210 split-K reduce launches of the 16 x 16 level's 128-pixel tiles, measured 2.1 ms FASTER)
         # (+ 66: the sub-pixel form of the three large upsampling convs is four launches each, and the UNet's costs its consumer a statistics pass)
         assert v[8] <= 2880, v[8]
@@ -500,12 +511,21 @@ def test_dry_and_real_pass_agree_without_a_gpu(cname, B, prec):
         assert m0 and int(m0.group(1)) - v[8] == 7 * 15 + 2 + 2, (m0 and m0.group(1), v[8])
 
 
-@pytest.mark.parametrize("cname,B,prec,launches,families,igemm,gn", [
-    ("realsr_swinunet_realesrgan256", 32, 2, 2853, [22, 331, 13, 952, 0, 0, 0, 270, 120, 1, 1, 195], 1905, 426),
-    ("realsr_swinunet_realesrgan256", 4, 0, 4147, [38, 0, 1685, 0, 0, 270, 60, 0, 0, 2, 0, 0], 2055, 1225),
-    ("inpaint_lama256_imagenet", 16, 2, 837, [22, 84, 13, 275, 0, 0, 0, 72, 32, 1, 1, 68], 568, 114),
-    ("faceir_gfpgan512_lpips", 2, 2, 1218, [14, 10, 33, 510, 0, 0, 0, 72, 0, 1, 1, 0], 641, 326)])
-def test_launch_mix_is_pinned_without_a_gpu(cname, B, prec, launches, families, igemm, gn):
+MIX = [
+    ("realsr_swinunet_realesrgan256", 32, 2, None, 2853, [22, 331, 13, 952, 0, 0, 0, 270, 120, 1, 1, 195], 1905, 426),
+    ("realsr_swinunet_realesrgan256", 4, 0, None, 4147, [38, 0, 1685, 0, 0, 270, 60, 0, 0, 2, 0, 0], 2055, 1225),
+    ("inpaint_lama256_imagenet", 16, 2, None, 837, [22, 84, 13, 275, 0, 0, 0, 72, 32, 1, 1, 68], 568, 114),
+    ("faceir_gfpgan512_lpips", 2, 2, None, 1218, [14, 10, 33, 510, 0, 0, 0, 72, 0, 1, 1, 0], 641, 326),
+    # the tile pool's shapes (LR h x w), as the routing rules of the rows above give them: a wide size class at the sub-pixel threshold, the
+    # default tile at batch 1, a tall size class in fp16 storage
+    ("realsr_swinunet_realesrgan256", 8, 2, (64, 128), 3108, [22, 61, 13, 1222, 0, 0, 0, 270, 120, 1, 1, 255], 1965, 591),
+    ("realsr_swinunet_realesrgan256", 1, 2, (128, 128), 3873, [22, 16, 13, 1642, 0, 0, 0, 270, 60, 1, 1, 0], 2025, 981),
+    ("realsr_swinunet_realesrgan256", 6, 0, (128, 64), 3862, [188, 0, 1490, 0, 0, 270, 60, 0, 0, 2, 0, 0], 2010, 1135)]
+
+
+@pytest.mark.parametrize("cname,B,prec,lr,launches,families,igemm,gn", MIX,
+                         ids=[_row_id(*r[:5], k, *r[6:]) for k, r in enumerate(MIX)])
+def test_launch_mix_is_pinned_without_a_gpu(cname, B, prec, lr, launches, families, igemm, gn):
     """Which kernel runs a conv is decided once per launch (rs_conv_plan, resshift_amd/csrc/igemm.hip) and every launch is booked under the
     family of the kernel its plan names.  The launch mix of one sampling call - kernel launches, launches per kernel family in the order of
     Exec::Fam (rs_profile_families), igemm-path and GroupNorm launch counts (rs_profile_get) - is pinned to what the routing rules gave
@@ -517,8 +537,8 @@ def test_launch_mix_is_pinned_without_a_gpu(cname, B, prec, launches, families, 
     from resshift_amd import build as _b
 
     env = dict(os.environ, RS_FAKE_DEVICE="1", RESSHIFT_HIP_LIB=_b.build_testhooks(), **NO_GPU)
-    r = subprocess.run([sys.executable, os.path.join(H.ROOT, "tests", "_fake_device_plumbing.py"), cname, str(B), str(prec)], env=env,
-                       capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(H.ROOT, "tests", "_fake_device_plumbing.py"), cname, str(B), str(prec)] +
+                       [str(v) for v in lr or ()], env=env, capture_output=True, text=True, timeout=600)
     m = re.search(r"real: tickets \d+ pool \d+ prod \d+ gn \d+ launches (\d+)", r.stderr)
     f = re.search(r"families ([\d,]+) igemm (\d+) gn (\d+)", r.stdout)
     assert m and f, (r.stdout[-500:], r.stderr[-1500:])

@@ -115,6 +115,23 @@ def test_oracle_offsize_full_network_and_tiles():
     assert (got - torch.from_numpy(g["tiled32/sample"])).abs().max().item() <= 2e-5
 
 
+@pytest.mark.parametrize("h,w", [(64, 128), (128, 64)])
+def test_oracle_nonsquare_full_network(h, w):
+    """The headline network on the smallest non-square planes its four levels and 8-pixel windows allow - the tile pool's size classes: one
+    UNet forward (B = 1, t = 7) against the unmodified reference modules' output (tests/golden/reference_nonsquare.npz,
+    oracle/make_golden_offsize.py).  The block-by-block GPU tests take the oracle as their reference at these shapes."""
+    from oracle import make_golden_offsize as mo
+
+    assert (h, w) in mo.NONSQUARE
+    g = np.load(mo.os.path.join(mo.GOLD, "reference_nonsquare.npz"))
+    up, ap, dp = H.realsr_params()
+    usd, _ = H.weights(up, ap)
+    x, y = mo.nonsquare_inputs(h, w, dp["steps"])
+    ref = torch.from_numpy(g[f"realsr{h}x{w}/unet"])
+    assert ref.shape == (1, 3, h, w) and ref.dtype == torch.float32
+    assert H.rel_err(oc.unet_forward(usd, up, x, torch.tensor([7]), lq=y), ref) < 2e-5
+
+
 def _checks():
     """tests/golden/reference_checks.npz: what the unmodified reference produced for the tests below (oracle/make_golden_checks.py, which
     also asserts the oracle bit-exact against every entry in the same run)"""

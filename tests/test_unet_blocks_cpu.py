@@ -23,11 +23,13 @@ NO_GPU = {"HIP_VISIBLE_DEVICES": "-1"}
 
 
 def _inputs(tag):
-    """(params, fp32 state_dict, host inputs) of a tiny case or of the realsr config at B=1"""
-    if tag == "realsr":
+    """(params, fp32 state_dict, host inputs) of a tiny case or of the realsr config at B=1 ("realsr": its own 64 x 64 latent,
+    "realsr@64x128": a non-square one)"""
+    if tag.startswith("realsr"):
         up, ap, dp = H.realsr_params()
         usd, _ = H.weights(up, ap)
-        y, noises, _ = H.synth.synthetic_inputs(H.SEED_X, 1, 64, 64, 3, 64, 64, dp["steps"])
+        h, w = (int(v) for v in tag.split("@")[1].split("x")) if "@" in tag else (64, 64)
+        y, noises, _ = H.synth.synthetic_inputs(H.SEED_X, 1, h, w, 3, h, w, dp["steps"])
         return up, usd, {"x": noises[1] * 1.3, "t": torch.tensor([7]), "lq": y, "mask": None}, "realsr/unet"
     up, ap, dp, with_mask = H.CASES[tag]
     usd, _ = H.weights(up, ap)
@@ -60,7 +62,7 @@ def test_plan_reproduces_unet_forward_bit_for_bit(tag):
     assert H.rel_err(ref, torch.from_numpy(H.golden()[golden])) < 2e-5
 
 
-@pytest.mark.parametrize("tag", ["tiny_fe", "realsr"])
+@pytest.mark.parametrize("tag", ["tiny_fe", "realsr", "realsr@64x128"])
 def test_plan_in_float64(tag):
     """float64 weights and inputs keep every step in float64 (GroupNorm and the timestep embedding included), and the result agrees
     with the fp32 oracle to fp32 round-off"""
@@ -84,32 +86,43 @@ def test_plan_in_float64(tag):
     print(f"{tag}: float64 plan vs fp32 oracle, worst step {worst:.2e}")
 
 
-def _plan_dims(cname, B):
-    """name -> (B, C, H, W) of every traced step of the plan (fp32 oracle at batch 1, synthetic weights)"""
+def _plan_dims(cname, B, h=None, w=None):
+    """name -> (B, C, H, W) of every traced step of the plan (fp32 oracle at batch 1, synthetic weights) at the latent size h x w (the
+    config's image_size by default; the lq / mask size follows by the config's lq_size / image_size ratio)"""
     up = to_plain(load_config(cname))["model"]["params"]
     uspec, _ = unet_param_spec(up)
     usd = H.synth.synthetic_state_dict(uspec, H.SEED_W, image_size=up["image_size"])
     hz, hl = int(up["image_size"]), int(up["lq_size"])
+    h, w = (hz, hz) if h is None else (h, w)
+    lh, lw = h * hl // hz, w * hl // hz
     g = torch.Generator().manual_seed(5)
-    env = {"x": torch.randn(1, int(up["in_channels"]), hz, hz, generator=g), "t": torch.tensor([3]),
-           "lq": torch.rand(1, 3, hl, hl, generator=g) * 2 - 1}
+    env = {"x": torch.randn(1, int(up["in_channels"]), h, w, generator=g), "t": torch.tensor([3]),
+           "lq": torch.rand(1, 3, lh, lw, generator=g) * 2 - 1}
     if up.get("cond_mask"):
-        env["mask"] = (torch.rand(1, 1, hl, hl, generator=g) > 0.5).float() * 2 - 1
+        env["mask"] = (torch.rand(1, 1, lh, lw, generator=g) > 0.5).float() * 2 - 1
     plan = oc.unet_plan(usd, up, with_lq=True, with_mask="mask" in env)
     env = oc.run_plan(plan, env)
     return {s.name: (B,) + tuple(env[s.name].shape[1:]) for s in plan if s.name not in ("emb", "head")}
 
 
-@pytest.mark.parametrize("cname,B,prec", [("realsr_swinunet_realesrgan256", 32, 2), ("realsr_swinunet_realesrgan256", 3, 0),
-                                          ("faceir_gfpgan512_lpips", 2, 2), ("inpaint_lama256_imagenet", 4, 1)])
-def test_trace_names_are_the_plan_blocks_without_a_gpu(cname, B, prec):
+_R, _F, _I = "realsr_swinunet_realesrgan256", "faceir_gfpgan512_lpips", "inpaint_lama256_imagenet"
+# (config, batch, precision 0 fp16 | 1 fp32 | 2 split, latent h, w - None: image_size); from the fifth row on: the tile pool's size classes and
+# batch 1, the cases tests/test_unet_blocks_gpu.py adds to the square bench shapes
+FAKE = [(_R, 32, 2, None, None), (_R, 3, 0, None, None), (_F, 2, 2, None, None), (_I, 4, 1, None, None),
+        (_R, 8, 2, 64, 128), (_R, 6, 2, 128, 64), (_R, 6, 0, 64, 128), (_R, 2, 1, 64, 128), (_R, 1, 2, 128, 128), (_R, 1, 2, 64, 64),
+        (_R, 1, 0, 64, 64), (_R, 4, 2, 64, 64), (_I, 2, 2, 64, 128), (_F, 1, 2, 64, 128)]
+
+
+@pytest.mark.parametrize("cname,B,prec,h,w", FAKE, ids=[f"{c}-{b}-{p}" + (f"-{h}x{w}" if h else "") for c, b, p, h, w in FAKE])
+def test_trace_names_are_the_plan_blocks_without_a_gpu(cname, B, prec, h, w):
     """RS_FAKE_DEVICE=1 (test-hooks library, see _fake_device_plumbing.py): a traced rs_unet_forward at mixed timesteps records every
     block of the plan exactly once, with the plan's dims, plus inner records under a block's prefix; and tracing leaves the pass alone -
     the same launch count, pool, tickets and sequence numbers as the untraced call."""
     from resshift_amd import build as _b
 
     env = dict(os.environ, RS_FAKE_DEVICE="1", RESSHIFT_HIP_LIB=_b.build_testhooks(), **NO_GPU)
-    r = subprocess.run([sys.executable, os.path.join(H.ROOT, "tests", "_fake_device_trace.py"), cname, str(B), str(prec)], env=env,
+    r = subprocess.run([sys.executable, os.path.join(H.ROOT, "tests", "_fake_device_trace.py"), cname, str(B), str(prec)] +
+                       ([str(h), str(w)] if h else []), env=env,
                        capture_output=True, text=True, timeout=600)
     fake = re.findall(r"\[fake device\] (dry: .*)", r.stderr)
     calls = re.findall(r"CALL (\w+) rc -?\d+ launches (\d+) records (\d+)", r.stdout)
@@ -120,7 +133,7 @@ def test_trace_names_are_the_plan_blocks_without_a_gpu(cname, B, prec):
     assert len(recs) == int(calls[1][2]) and recs, calls
     names = [n for n, *_ in recs]
     assert len(set(names)) == len(names), [n for n in names if names.count(n) > 1]
-    dims = _plan_dims(cname, B)
+    dims = _plan_dims(cname, B, h, w)
     blocks = {n: tuple(int(v) for v in d) for n, *d in recs if n in dims}
     assert set(blocks) == set(dims), (sorted(set(dims) - set(blocks)), sorted(set(blocks) - set(dims)))
     for n, d in dims.items():
