@@ -108,27 +108,23 @@ class ContinuousSampler:
         if self._pad != (0, 0):   # sample_func's reflect padding (sampler.py:130-138), the mask alike
             lq = sharding.reflect_pad(lq, *self._pad)
             mask = sharding.reflect_pad(mask, *self._pad) if mask is not None else None
-        if self.seeded:
+        if self.seeded:   # per-request payload: the (seed, stream) key
             seeds = [int(v) for v in seed] if isinstance(seed, (list, tuple)) else [seed] * n
             if len(seeds) != n:
                 raise ValueError(f"seed: {n} images but {len(seeds)} seeds")
-            ids = []
-            for i in range(n):
-                sd = seeds[i] if seeds[i] is not None else request_seed(getattr(self.sampler, "seed", 0), self._next_id)
-                self._waiting.append((self._next_id, lq[i], mask[i] if mask is not None else None, (int(sd) % 2 ** 64, int(stream))))
-                ids.append(self._next_id)
-                self._next_id += 1
-            return ids
-        zs = self.engine.latent_shape(n, lq.shape[2], lq.shape[3], self.sf)
-        if noise is None:
-            noise = torch.randn(zs, device=self.device, dtype=torch.float32)
-        if step_noises is None:
-            step_noises = [torch.randn(zs, device=self.device, dtype=torch.float32) for _ in range(self.steps)]
-        if len(step_noises) != self.steps:
-            raise ValueError(f"step_noises: {self.steps} draws expected, got {len(step_noises)}")
-        draws = torch.stack([noise.to(self.device, torch.float32)] + [s.to(self.device, torch.float32) for s in step_noises], 1)
-        if tuple(draws.shape) != (n, self.steps + 1) + tuple(zs[1:]):
-            raise ValueError(f"noise draws must be [{n},{zs[1]},{zs[2]},{zs[3]}] each, got {tuple(draws.shape)}")
+            base = getattr(self.sampler, "seed", 0)
+            draws = [(int(sd if sd is not None else request_seed(base, self._next_id + i)) % 2 ** 64, int(stream)) for i, sd in enumerate(seeds)]
+        else:             # ... or its row of the stacked draws
+            zs = self.engine.latent_shape(n, lq.shape[2], lq.shape[3], self.sf)
+            if noise is None:
+                noise = torch.randn(zs, device=self.device, dtype=torch.float32)
+            if step_noises is None:
+                step_noises = [torch.randn(zs, device=self.device, dtype=torch.float32) for _ in range(self.steps)]
+            if len(step_noises) != self.steps:
+                raise ValueError(f"step_noises: {self.steps} draws expected, got {len(step_noises)}")
+            draws = torch.stack([noise.to(self.device, torch.float32)] + [s.to(self.device, torch.float32) for s in step_noises], 1)
+            if tuple(draws.shape) != (n, self.steps + 1) + tuple(zs[1:]):
+                raise ValueError(f"noise draws must be [{n},{zs[1]},{zs[2]},{zs[3]}] each, got {tuple(draws.shape)}")
         ids = []
         for i in range(n):
             self._waiting.append((self._next_id, lq[i], mask[i] if mask is not None else None, draws[i]))
@@ -171,13 +167,12 @@ class ContinuousSampler:
 
     def _begin(self, a: int, b: int, ids: List[int], keys=None):
         """slots a .. b-1 hold new images (LR planes, mask, draws - or, seeded, their `keys`): ONE rs_sample_begin batch makes their x_T"""
-        if self.seeded:
-            self.engine.sample_begin(self._Y[a:b], None, self.tables, self.sf, self.scale_factor, prec_encode=self.prec_encode,
-                                     out=self._X[a:b], keys=list(keys))
+        if self.seeded:   # draw 0 of each key, generated by the kernel that adds it
+            noise, kw = None, {"keys": list(keys)}
             self._keys += list(keys)
         else:
-            self.engine.sample_begin(self._Y[a:b], self._N[a:b, 0].contiguous(), self.tables, self.sf, self.scale_factor,
-                                     prec_encode=self.prec_encode, out=self._X[a:b])
+            noise, kw = self._N[a:b, 0].contiguous(), {}
+        self.engine.sample_begin(self._Y[a:b], noise, self.tables, self.sf, self.scale_factor, prec_encode=self.prec_encode, out=self._X[a:b], **kw)
         self._ids += ids
         self._t += [self.steps - 1] * (b - a)
         self._n = b
@@ -230,14 +225,12 @@ class ContinuousSampler:
         if n == 0:
             return [], None
         if self.seeded:   # draw steps - t of each slot's key, generated by the kernel that adds it
-            self.engine.sample_step(self._X[:n], self._Y[:n], list(self._t), None, self.tables, self.sf,
-                                    mask=self._M[:n] if self._M is not None else None, prec=self.prec_unet, keys=list(self._keys))
-        else:
-            # this step's draw of each slot: draw k = steps - t (draw 0 is the prior noise)
+            noise, kw = None, {"keys": list(self._keys)}
+        else:             # this step's draw of each slot: draw k = steps - t (draw 0 is the prior noise)
             k = torch.tensor([self.steps - t for t in self._t], device=self.device, dtype=torch.long)
-            noise = self._N[torch.arange(n, device=self.device), k]
-            self.engine.sample_step(self._X[:n], self._Y[:n], list(self._t), noise, self.tables, self.sf,
-                                    mask=self._M[:n] if self._M is not None else None, prec=self.prec_unet)
+            noise, kw = self._N[torch.arange(n, device=self.device), k], {}
+        self.engine.sample_step(self._X[:n], self._Y[:n], list(self._t), noise, self.tables, self.sf,
+                                mask=self._M[:n] if self._M is not None else None, prec=self.prec_unet, **kw)
         done = [i for i in range(n) if self._t[i] == 0]
         self._t = [t - 1 for t in self._t]
         ids, img = [], None

@@ -406,32 +406,22 @@ class Engine:
         image, see noise_fill): draws 0 .. steps of each key, generated in the kernels that consume them (rs_sample_seeded)."""
         y = self._f32c(y)
         B, _, h, w = y.shape
-        steps = int(len(tables["coef1"]))
-        f = 2 ** (int(self.cfg.ae.n_levels) - 1)
-        hz, wz, cz = h * sf // f, w * sf // f, int(self.cfg.ae.embed_dim)
+        zs = self.latent_shape(B, h, w, sf)
         karr = self._keys(keys, noise, B, "sample") if keys is not None else None
         if karr is None:
             noise = self._f32c(noise)
-            assert tuple(noise.shape) == (steps + 1, B, cz, hz, wz), (tuple(noise.shape), (steps + 1, B, cz, hz, wz))
+            assert tuple(noise.shape) == (len(tables["coef1"]) + 1,) + zs, (tuple(noise.shape), (len(tables["coef1"]) + 1,) + zs)
         out = torch.empty(B, int(self.cfg.ae.out_ch), h * sf, w * sf, device=y.device, dtype=torch.float32)
         a = _lib.SampleArgs()
         mk = self._f32c(mask) if mask is not None else None
-        z_out = torch.empty(B, cz, hz, wz, device=y.device, dtype=torch.float32) if return_aux else None
-        idx = torch.empty(B * hz * wz, device=y.device, dtype=torch.int32) if return_aux else None
+        z_out = torch.empty(zs, device=y.device, dtype=torch.float32) if return_aux else None
+        idx = torch.empty(B * zs[2] * zs[3], device=y.device, dtype=torch.int32) if return_aux else None
         a.y, a.noise, a.out = y.data_ptr(), (noise.data_ptr() if karr is None else None), out.data_ptr()
         a.mask = mk.data_ptr() if mk is not None else None
         a.z_out = z_out.data_ptr() if z_out is not None else None
         a.idx_out = idx.data_ptr() if idx is not None else None
-        a.B, a.h, a.w, a.sf, a.steps = B, h, w, int(sf), steps
-        pu = [prec_unet] * steps if isinstance(prec_unet, (int, str)) else list(prec_unet)
-        for t in range(steps):
-            a.inv_std[t] = float(tables["inv_std"][t])
-            a.coef1[t] = float(tables["coef1"][t])
-            a.coef2[t] = float(tables["coef2"][t])
-            a.sigma[t] = float(tables["sigma"][t])
-            a.tmap[t] = int(tables["tmap"][t])
-            a.prec_unet[t] = parse_precision(pu[t])
-        a.prior_scale = float(tables["prior_scale"])
+        a.B, a.h, a.w, a.sf = B, h, w, int(sf)
+        self._schedule(a, tables, prec_unet)
         a.scale_factor = float(scale_factor)
         a.prec_encode, a.prec_decode = parse_precision(prec_encode), parse_precision(prec_decode)
         a.stream = self._stream()

@@ -336,40 +336,31 @@ class ResShiftDiffusion:
             return self.decode_first_stage(final, first_stage_model=first_stage_model, consistencydecoder=consistencydecoder)
         eng = self._fused_engine(model, first_stage_model)
         B, _, h, w = y.shape
-        if seeds is not None:
-            mask = (model_kwargs or {}).get("mask", None)
-            lq = (model_kwargs or {}).get("lq", None)
-            if lq is not None and lq.data_ptr() != y.data_ptr() and not torch.equal(lq, y):
-                raise NotImplementedError("fused loop conditions the UNet on y itself (sampler.py:140-148)")
-            return eng.sample(y, None, self.step_tables(), sf=self.sf, scale_factor=self.scale_factor, mask=mask,
-                              prec_unet=self._unet_precisions(), prec_encode=self._prec(self.precision_encode),
-                              prec_decode=self._prec(self.precision_decode), return_aux=return_aux,
-                              keys=self._seed_keys(seeds, B, noise, step_noises, noise_repeat))
-        f = 2 ** (int(eng.cfg.ae.n_levels) - 1)
-        zshape = (B, int(eng.cfg.ae.embed_dim), h * self.sf // f, w * self.sf // f)
-        T = self.num_timesteps
-        # RNG draws in the reference's order: prior noise (:446), then one randn_like per step (:358)
-        draws = []
-        for k in range(T + 1):
-            if k == 0 and noise is not None:
-                n = noise
-            elif k > 0 and step_noises is not None:
-                n = step_noises[k - 1]
-            else:
-                n = torch.randn(zshape, device=y.device, dtype=torch.float32)
-            n = n.to(y.device, torch.float32)
-            if noise_repeat:
-                n = n[0,].repeat(B, 1, 1, 1)
-            draws.append(n)
-        noise_all = torch.stack(draws, 0)
+        if seeds is not None:   # nothing is drawn: the kernels make the normals of each key
+            noise_all, keys = None, self._seed_keys(seeds, B, noise, step_noises, noise_repeat)
+        else:
+            zshape = eng.latent_shape(B, h, w, self.sf)
+            # RNG draws in the reference's order: prior noise (:446), then one randn_like per step (:358)
+            draws = []
+            for k in range(self.num_timesteps + 1):
+                if k == 0 and noise is not None:
+                    n = noise
+                elif k > 0 and step_noises is not None:
+                    n = step_noises[k - 1]
+                else:
+                    n = torch.randn(zshape, device=y.device, dtype=torch.float32)
+                n = n.to(y.device, torch.float32)
+                if noise_repeat:
+                    n = n[0,].repeat(B, 1, 1, 1)
+                draws.append(n)
+            noise_all, keys = torch.stack(draws, 0), None
         mask = (model_kwargs or {}).get("mask", None)
         lq = (model_kwargs or {}).get("lq", None)
         if lq is not None and lq.data_ptr() != y.data_ptr() and not torch.equal(lq, y):
             raise NotImplementedError("fused loop conditions the UNet on y itself (sampler.py:140-148)")
-        res = eng.sample(y, noise_all, self.step_tables(), sf=self.sf, scale_factor=self.scale_factor, mask=mask,
-                         prec_unet=self._unet_precisions(), prec_encode=self._prec(self.precision_encode),
-                         prec_decode=self._prec(self.precision_decode), return_aux=return_aux)
-        return res
+        return eng.sample(y, noise_all, self.step_tables(), sf=self.sf, scale_factor=self.scale_factor, mask=mask,
+                          prec_unet=self._unet_precisions(), prec_encode=self._prec(self.precision_encode),
+                          prec_decode=self._prec(self.precision_decode), return_aux=return_aux, keys=keys)
 
 
 def create_gaussian_diffusion(*, normalize_input, schedule_name, sf=4, min_noise_level=0.01, steps=1000, kappa=1, etas_end=0.99,

@@ -5,6 +5,9 @@ change results: models come from the engine-backed classes (the YAML `target:` s
 reference are mapped onto them), every rank can receive the packed weights through ONE RCCL
 broadcast instead of re-reading the checkpoint (sharding.py), and image file I/O uses PIL (the
 reference uses cv2, which is a host-side detail outside the hot path).
+
+What follows the blend of a whole image - the colour fix, the resize to `out_scale`, their option checks - is `finish.Finish`:
+`sample_tiled` calls it on the image it returns, `inference` gets it through `sample_tiled` resp. the `TilePool`.
 """
 from __future__ import annotations
 
@@ -22,6 +25,7 @@ import torch.distributed as dist
 from . import sharding, tiling
 from .autoencoder import VQModelTorch
 from .config import ConfigNode, load_config
+from .finish import Finish
 from .gaussian_diffusion import create_gaussian_diffusion
 from .unet import UNetModelSwin
 
@@ -211,13 +215,10 @@ class ResShiftSampler(BaseSampler):
         key (seed, stream = j) - what tilepool.TilePool(seeded=True) gives the same image; an untiled image is its tile 0."""
         from .tiling import TileSplitter
 
-        fix = getattr(self, "color_fix", "none")   # ("none" issues exactly the calls it always has)
-        tiling.check_color_fix(fix)
-        if fix != "none" and mask is not None:
-            raise ValueError(f"color_fix={fix!r} is undefined for a masked input (the LQ image has a hole): use color_fix='none'")
-        out_scale = self._out_scale()
-        if out_scale is not None and mask is not None:
-            raise ValueError(f"out_scale={out_scale!r} is undefined for a masked input (lq and mask stay at the model's size): use out_scale=None")
+        finish = Finish.of(self)   # (per call: the options may change between calls)
+        if mask is not None:
+            finish.reject_mask("sample_tiled")
+        engine = getattr(self, "engine", None)   # (only a fix or a resize reaches it)
         B0 = im_lq.shape[0]
         if seed is not None:
             if tile_noises is not None or noise_repeat:
@@ -231,11 +232,10 @@ class ResShiftSampler(BaseSampler):
             else:
                 nz = tile_noises[0] if tile_noises else (None, None)
                 sr = self.sample_func(im_lq, noise_repeat=noise_repeat, mask=mask, noise=nz[0], step_noises=nz[1])
-            return self._finish(sr, im_lq, fix, out_scale)
+            return finish(engine, sr, im_lq)
         x = torch.cat([im_lq, mask], dim=1) if mask is not None else im_lq
-        blend = getattr(self, "tile_blend", "uniform")   # ("uniform" issues exactly the calls it always has)
         splitter = TileSplitter(x, self.chop_size, stride=self.chop_stride, sf=self.sf, extra_bs=self.chop_bs,
-                                **({"blend": blend} if blend != "uniform" else {}))
+                                **({"blend": finish.blend} if finish.blend != "uniform" else {}))   # ("uniform": the call as it always was)
         for k, (pch, index_infos) in enumerate(splitter):
             if mask is not None:
                 pch, mask_pch = pch[:, :-1].contiguous(), pch[:, -1:].contiguous()
@@ -248,24 +248,7 @@ class ResShiftSampler(BaseSampler):
                 nz = tile_noises[k] if tile_noises else (None, None)
                 out = self.sample_func(pch, noise_repeat=noise_repeat, mask=mask_pch, noise=nz[0], step_noises=nz[1])
             splitter.update(out, index_infos)
-        return self._finish(splitter.gather(), im_lq, fix, out_scale)
-
-    def _out_scale(self):
-        """the sampler's `out_scale` where it asks for another size than the model's, else None: None and a value equal to sf issue
-        exactly the calls issued without it"""
-        out_scale = getattr(self, "out_scale", None)
-        if out_scale is None:
-            return None
-        tiling.check_out_scale(out_scale, self.sf)
-        return out_scale if tiling.resizes(out_scale, self.sf) else None
-
-    def _finish(self, sr, im_lq, fix, out_scale):
-        """what follows the blend of a whole image: the colour fix at the model's scale, then the resize to `out_scale`"""
-        if fix != "none":
-            sr = self.engine.color_fix(sr, im_lq, fix)
-        if out_scale is not None:
-            sr = self.engine.resize(sr, size=tiling.out_size(im_lq.shape[2], im_lq.shape[3], out_scale), clamp=True)
-        return sr
+        return finish(engine, splitter.gather(), im_lq)
 
     # ------------------------------------------------------------------ file-level demo driver
     @staticmethod
@@ -346,12 +329,9 @@ class ResShiftSampler(BaseSampler):
         FileNotFoundError before anything is sampled, one of another size than the output ValueError."""
         if seeded and noise_repeat:
             raise ValueError("seeded=True names every draw by (seed, stream): it excludes noise_repeat")
-        fix = getattr(self, "color_fix", "none")
-        if fix != "none" and mask_path is not None:
-            raise ValueError(f"color_fix={fix!r} is undefined for masked (inpainting) inputs: use color_fix='none'")
-        out_scale = self._out_scale()
-        if out_scale is not None and mask_path is not None:
-            raise ValueError(f"out_scale={out_scale!r} is undefined for masked (inpainting) inputs: use out_scale=None")
+        finish = Finish.of(self)   # (the options are checked before anything is touched; sample_tiled and the TilePool build their own)
+        if mask_path is not None:
+            finish.reject_mask("inference")
         in_path, out_path = Path(in_path), Path(out_path)
         if self.rank == 0:
             out_path.mkdir(parents=True, exist_ok=True)
@@ -364,8 +344,6 @@ class ResShiftSampler(BaseSampler):
             # reference's extension order, each sorted; the inpainting loader adds 'PNG' (sampler.py:259)
             exts = ["png", "jpg", "jpeg", "JPEG", "bmp"] + (["PNG"] if mask_path is not None else [])
             files = [p for e in exts for p in sorted(in_path.glob(f"**/*.{e}"))]
-        from PIL import Image
-
         rows = None
         if gt_path is not None:
             if isinstance(metric_border, bool) or not isinstance(metric_border, int) or metric_border < 0:
@@ -374,46 +352,56 @@ class ResShiftSampler(BaseSampler):
                 self._gt_file(gt_path, p, single)
             rows = {}
         score = (lambda u8, fs: rows.update(self._score(u8, fs, gt_path, single, metric_border, metric_ycbcr))) if rows is not None else None
-        micro = math.ceil(bs / self.num_gpus)   # sampler.py:274-277: the slice width comes from bs, also on the last, partial batch
+        load = lambda fs: self._load(fs, mask_path, single)
+        write = lambda sr, lq, mask, fs: self._write_pngs(sr, lq, mask, mask_back, fs, out_path, score)
         if pool:
-            self._inference_pool(files, out_path, mask_path, mask_back, bs, micro, single, noise_repeat, seeded, **({"score": score} if score else {}))
-            sharding.barrier()
-            if rows is not None:
-                rows = self._finish_metrics(out_path, rows)
-            self.write_log(f"Processing done, enjoy the results in {out_path}")
-            return rows
-        for b0 in range(0, len(files), bs):
-            batch = files[b0:b0 + bs]
-            mine = batch[self.rank * micro:(self.rank + 1) * micro]
-            first = b0 + self.rank * micro   # position of mine[0] in the whole listing
-            if mine:
-                lq = self.engine.u8_to_input(torch.stack([self._read_image_u8(p) for p in mine]).to(self.device))
-                mask = None
-                if mask_path is not None:
-                    # a directory input looks the mask up by file name (datapipe/datasets.py:470); a single input file takes
-                    # mask_path as the mask file itself (sampler.py:296-297)
-                    mpaths = [Path(mask_path)] if single else [Path(mask_path) / p.name for p in mine]
-                    mask = self.engine.u8_to_input(torch.stack([self._read_image_u8(m, gray=True) for m in mpaths]).to(self.device))
+            self._inference_pool(self._shares(files, bs), load, write, noise_repeat, seeded)
+        else:
+            for first, mine in self._shares(files, bs):
+                lq, mask = load(mine)
                 if seeded:
                     sr = self.sample_tiled(lq, mask=mask, seed=[self.image_seed(first + j) for j in range(len(mine))])
                 else:
                     sr = self.sample_tiled(lq, mask=mask, noise_repeat=noise_repeat)
-                blend = mask is not None and mask_back
-                out_u8 = self.engine.output_to_u8(sr, lq=lq if blend else None, mask=mask if blend else None)
-                if score is not None:
-                    score(out_u8, mine)
-                out_u8 = out_u8.cpu().numpy()
-                for p, im in zip(mine, out_u8):
-                    Image.fromarray(im if im.shape[2] != 1 else im[:, :, 0]).save(out_path / f"{p.stem}.png")
+                write(sr, lq, mask, mine)
         sharding.barrier()
         if rows is not None:
             rows = self._finish_metrics(out_path, rows)
         self.write_log(f"Processing done, enjoy the results in {out_path}")
         return rows
 
-    def _inference_pool(self, files, out_path, mask_path, mask_back, bs, micro, single, noise_repeat, seeded=False, score=None):
+    def _shares(self, files, bs):
+        """(position of mine[0] in the whole listing, mine) for every batch of `bs` files that gives this rank a share `mine`"""
+        micro = math.ceil(bs / self.num_gpus)   # sampler.py:274-277: the slice width comes from bs, also on the last, partial batch
+        for b0 in range(0, len(files), bs):
+            mine = files[b0:b0 + bs][self.rank * micro:(self.rank + 1) * micro]
+            if mine:
+                yield b0 + self.rank * micro, mine
+
+    def _load(self, files, mask_path, single):
+        """(lq [n,3,H,W], mask [n,1,H,W] | None) of `files` in [-1,1] on the device.  A directory input looks the mask up by file name
+        (datapipe/datasets.py:470); a single input file takes mask_path as the mask file itself (sampler.py:296-297)."""
+        lq = self.engine.u8_to_input(torch.stack([self._read_image_u8(p) for p in files]).to(self.device))
+        if mask_path is None:
+            return lq, None
+        mpaths = [Path(mask_path)] if single else [Path(mask_path) / p.name for p in files]
+        return lq, self.engine.u8_to_input(torch.stack([self._read_image_u8(m, gray=True) for m in mpaths]).to(self.device))
+
+    def _write_pngs(self, sr, lq, mask, mask_back, files, out_path, score=None):
+        """the finished batch sr [n,C,H,W] of `files` -> their PNGs: the inpainting blend and the rounding on the device, `score(u8, files)`
+        on the very uint8 device tensor that is then written"""
         from PIL import Image
 
+        blend = mask is not None and mask_back
+        out_u8 = self.engine.output_to_u8(sr, lq=lq if blend else None, mask=mask if blend else None)
+        if score is not None:
+            score(out_u8, files)
+        for p, im in zip(files, out_u8.cpu().numpy()):
+            Image.fromarray(im if im.shape[2] != 1 else im[:, :, 0]).save(out_path / f"{p.stem}.png")
+
+    def _inference_pool(self, shares, load, write, noise_repeat, seeded):
+        """the files of `shares`, one by one, through ONE TilePool: submitted ahead while fewer than POOL_LOOKAHEAD tiles wait; an image
+        is written when it completes"""
         from .tilepool import TilePool
 
         if noise_repeat:
@@ -421,27 +409,16 @@ class ResShiftSampler(BaseSampler):
         tp = TilePool(self, seeded=seeded)
         kept = {}   # image id -> (file, lq, mask) until its PNG is written
 
-        def write(done):
-            for rid, sr in done.items():
+        def step():
+            for rid, sr in tp.step().items():
                 p, lq, mask = kept.pop(rid)
-                blend = mask is not None and mask_back
-                u8 = self.engine.output_to_u8(sr.unsqueeze(0), lq=lq if blend else None, mask=mask if blend else None)
-                if score is not None:
-                    score(u8, [p])
-                im = u8[0].cpu().numpy()
-                Image.fromarray(im if im.shape[2] != 1 else im[:, :, 0]).save(out_path / f"{p.stem}.png")
+                write(sr.unsqueeze(0), lq, mask, [p])
 
-        for b0 in range(0, len(files), bs):
-            for j, p in enumerate(files[b0:b0 + bs][self.rank * micro:(self.rank + 1) * micro]):
-                lq = self.engine.u8_to_input(self._read_image_u8(p).unsqueeze(0).to(self.device))
-                mask = None
-                if mask_path is not None:
-                    mp = Path(mask_path) if single else Path(mask_path) / p.name
-                    mask = self.engine.u8_to_input(self._read_image_u8(mp, gray=True).unsqueeze(0).to(self.device))
-                # (position of this file in the whole listing: b0 + rank * micro + j)
-                rid = tp.submit(lq, mask=mask, seed=self.image_seed(b0 + self.rank * micro + j)) if seeded else tp.submit(lq, mask=mask)
-                kept[rid] = (p, lq, mask)
+        for first, mine in shares:
+            for j, p in enumerate(mine):
+                lq, mask = load([p])
+                kept[tp.submit(lq, mask=mask, seed=self.image_seed(first + j) if seeded else None)] = (p, lq, mask)
                 while tp.waiting_tiles() >= self.POOL_LOOKAHEAD:
-                    write(tp.step())
+                    step()
         while tp.pending():
-            write(tp.step())
+            step()

@@ -29,7 +29,8 @@ tiles retire through ONE `rs_tile_scatter_weighted` launch - the bits of `rs_til
 
 The sampler's `color_fix` ("none" by default) is applied to each completed image after `rs_tile_finalize`, against the
 image's own LQ planes (`rs_color_fix`): tiles are never corrected one by one.  The sampler's `out_scale` (None by default)
-follows it: each completed image is resized to (ceil(H * out_scale), ceil(W * out_scale)) and clamped (`rs_resize`).
+follows it: each completed image is resized to (ceil(H * out_scale), ceil(W * out_scale)) and clamped (`rs_resize`).  Both are
+`finish.Finish`, the one stage `sample_tiled` runs too; `step()` calls it where an image completes.
 
 `seeded=True`: `submit(image, seed=...)` names the image; tile j (index in `tiling.extract_starts` order, the order of
 `tile_windows`) draws its noise from key (seed, stream = j) inside the engine's kernels.  No draws are made or stored, and an image's
@@ -45,7 +46,8 @@ import torch
 
 from . import _lib
 from .continuous import ContinuousSampler, check_sampler, request_seed
-from .tiling import check_blend, check_color_fix, check_out_scale, extract_starts, feather_ramp, out_size, resizes
+from .finish import Finish
+from .tiling import extract_starts, feather_ramp
 
 HEADLINE_PIXELS = 32 * 64 * 64   # LR pixels of the benchmark's batch (32 images of 64 x 64): what `max_batch=None` fills a class up to
 
@@ -98,21 +100,14 @@ class TilePool:
         self._next_image = self._next_tile = 0
         self.keep_log, self.batches = bool(keep_log), []
         self.seeded = bool(seeded)
-        # the blend is the sampler's (BaseSampler(tile_blend=)): "feather" retires tiles through rs_tile_scatter_weighted
-        self.blend = getattr(sampler, "tile_blend", "uniform")
-        check_blend(self.blend)
+        # the blend ("feather" retires tiles through rs_tile_scatter_weighted), and what follows it on each completed image - the colour
+        # fix, then the output scale - are the sampler's (finish.py)
+        self.finish = Finish.of(sampler, sf=self.sf)
+        if self.cond_mask:
+            self.finish.reject_mask("TilePool")
+        self.blend, self.color_fix, self.out_scale = self.finish.blend, self.finish.color_fix, self.finish.out_scale
         self.ramp = feather_ramp(self.chop_size, self.chop_stride, self.sf) if self.blend == "feather" else None
         self._tile_index: Dict[int, int] = {}
-        # so is the colour correction (BaseSampler(color_fix=)): applied to each completed image, never to a tile
-        self.color_fix = getattr(sampler, "color_fix", "none")
-        check_color_fix(self.color_fix)
-        if self.color_fix != "none" and self.cond_mask:
-            raise ValueError(f"color_fix={self.color_fix!r} is undefined for a model conditioned on a mask (the LQ image has a hole)")
-        # and the output scale (BaseSampler(out_scale=)): each completed image is resized after the colour fix
-        self.out_scale = getattr(sampler, "out_scale", None)
-        check_out_scale(self.out_scale, self.sf)
-        if resizes(self.out_scale, self.sf) and self.cond_mask:
-            raise ValueError(f"out_scale={self.out_scale!r} is undefined for a model conditioned on a mask (lq and mask stay at the model's size)")
 
     # ------------------------------------------------------------------ requests
     def class_max_batch(self, key: Tuple[int, int]) -> int:
@@ -240,10 +235,8 @@ class TilePool:
             _lib.tile_scatter(rows, batch, self.sf, ramp=self.ramp)
         for im in done:
             res = _lib.tile_finalize(im.acc, im.count)
-            if self.color_fix != "none":   # the whole image against its own LQ planes
-                res = self.engine.color_fix(res.unsqueeze(0), im.src[:3].unsqueeze(0), self.color_fix)[0]
-            if resizes(self.out_scale, self.sf):   # after the fix, whole images only
-                res = self.engine.resize(res.unsqueeze(0), size=out_size(im.src.shape[1], im.src.shape[2], self.out_scale), clamp=True)[0]
+            # the whole image against its own LQ planes (no mask plane), never a tile
+            res = self.finish(self.engine, res.unsqueeze(0), im.src[:3].unsqueeze(0))[0]
             out[im.id] = res
             del self._images[im.id]
         return out

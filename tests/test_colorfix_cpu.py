@@ -10,16 +10,9 @@ import torch.nn.functional as F
 
 import helpers as H  # noqa: F401  (puts the repository root on sys.path)
 import _colorfix_ref as R
-from oracle import cases
-from resshift_amd import _lib, build, tiling
-from resshift_amd.gaussian_diffusion import create_gaussian_diffusion
+from _fakes import FakeEngine, _OnDevice, fake_launches, fake_sampler, lib  # noqa: F401  (fixtures)
+from resshift_amd import _lib, tiling
 from resshift_amd.tilepool import TilePool, tile_windows
-
-
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
 
 
 # ---------------------------------------------------------------------------------------------------------------- the restatement
@@ -180,58 +173,6 @@ def test_unknown_color_fix_is_rejected_by_the_constructor():
         tiling.check_color_fix(ok)
 
 
-class FakeEngine:
-    """the recording engine of tests/test_feather_cpu.py plus color_fix: the decoded tile is its code everywhere; the fix adds one"""
-
-    def __init__(self):
-        self.fixes = []
-
-    def latent_shape(self, B, h, w, sf):
-        return (B, 3, h * sf // 4, w * sf // 4)
-
-    def film_prewarm(self, timesteps):
-        pass
-
-    def sample_begin(self, y, noise, tables, sf, scale_factor, prec_encode=None, out=None, keys=None):
-        out.zero_()
-        out[:, 0, 0, 0] = y[:, 0, 0, 0]
-        return out
-
-    def sample_step(self, x, y, t, noise, tables, sf, mask=None, prec=None, pred_xstart=None, keys=None):
-        return x
-
-    def sample_end(self, x0, h, w, sf, scale_factor, prec_decode=None, return_aux=False):
-        return x0[:, 0, 0, 0].view(-1, 1, 1, 1).expand(-1, 3, h * sf, w * sf).contiguous() * 1.0
-
-    def color_fix(self, sr, lq, mode="wavelet"):
-        self.fixes.append((tuple(sr.shape), lq.clone(), mode))
-        return sr + 1.0
-
-
-def fake_sampler(cond_mask=False, **extra):
-    d = create_gaussian_diffusion(**cases.TINY_DIFFUSION)
-    d.set_precision("split", "split", "fp16")
-    return SimpleNamespace(base_diffusion=d, engine=FakeEngine(), autoencoder=object(), padding_offset=16, chop_size=16, chop_stride=12,
-                           seed=77, configs={"model": {"params": {"cond_mask": cond_mask}}}, device=torch.device("cpu"), **extra)
-
-
-@pytest.fixture
-def fake_launches(monkeypatch):
-    def gather(tiles, out_lq, out_mask=None):
-        Hp, Wp = out_lq.shape[-2:]
-        for k, (src, h0, w0, th, tw) in enumerate(tiles):
-            out_lq[k] = F.pad(src[None, :3, h0:h0 + th, w0:w0 + tw], (0, Wp - tw, 0, Hp - th), mode="reflect")[0]
-
-    def scatter(tiles, batch, sf, ramp=None):
-        for k, (acc, cnt, Hh, W, h0, w0, th, tw) in enumerate(tiles):
-            acc[:, h0 * sf:(h0 + th) * sf, w0 * sf:(w0 + tw) * sf] += batch[k, :, :th * sf, :tw * sf]
-            cnt[h0 * sf:(h0 + th) * sf, w0 * sf:(w0 + tw) * sf] += 1
-
-    monkeypatch.setattr(_lib, "tile_gather", gather)
-    monkeypatch.setattr(_lib, "tile_scatter", scatter)
-    monkeypatch.setattr(_lib, "tile_finalize", lambda acc, count: acc.div_(count))
-
-
 @pytest.mark.parametrize("fix", ["none", "wavelet", "adain", None])
 def test_tile_pool_fixes_each_completed_image_once(fake_launches, fix):
     """the fix is the sampler's; it sees whole blended images with their own LQ planes, never a tile; "none" - named, or a sampler
@@ -257,11 +198,6 @@ def test_tile_pool_fixes_each_completed_image_once(fake_launches, fix):
         Hh, W = sizes[i]
         assert shape == (1, 3, Hh * 4, W * 4) and mode == fix and torch.equal(lq_seen, lqs[i][None])
     assert all(o.min().item() >= 1.0 for o in out.values())     # the pool returns what the fix returned
-
-
-class _OnDevice(torch.Tensor):
-    """a CPU tensor that says it is a device tensor (tests/test_feather_cpu.py)"""
-    is_cuda = True
 
 
 @pytest.mark.parametrize("size", [(40, 28), (16, 12)], ids=["tiled", "untiled"])

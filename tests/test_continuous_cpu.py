@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import helpers as H
+import _fakes
 from oracle import cases
 from resshift_amd import _lib
 from resshift_amd.continuous import ContinuousSampler
@@ -54,11 +55,8 @@ class FakeEngine:
         return torch.zeros(x0.shape[0], 3, h * sf, w * sf)
 
 
-def fake_sampler(cond_mask=False, precision=("split", "split", "fp16"), autoencoder=True):
-    d = create_gaussian_diffusion(**cases.TINY_DIFFUSION)
-    d.set_precision(*precision)
-    return SimpleNamespace(base_diffusion=d, engine=FakeEngine(), autoencoder=object() if autoencoder else None, padding_offset=16,
-                           configs={"model": {"params": {"cond_mask": cond_mask}}}, device=torch.device("cpu"))
+def fake_sampler(**kw):
+    return _fakes.fake_sampler(engine=FakeEngine(), **kw)
 
 
 def lq_of(i, n=1, h=16):

@@ -10,16 +10,9 @@ import torch.nn.functional as F
 
 import helpers as H  # noqa: F401  (puts the repository root on sys.path)
 import _feather_ref as R
-from oracle import cases
-from resshift_amd import _lib, build, tiling
-from resshift_amd.gaussian_diffusion import create_gaussian_diffusion
+from _fakes import _OnDevice, fake_sampler, lib  # noqa: F401  (fixtures)
+from resshift_amd import _lib, tiling
 from resshift_amd.tilepool import TilePool, tile_windows
-
-
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
 
 
 # ---------------------------------------------------------------------------------------------------------------- the restatement
@@ -137,34 +130,6 @@ def test_the_new_symbols_are_declared_and_the_descriptor_keeps_its_layout(lib):
 CODE = 1e-3   # a tile's code travels as code * CODE, so that it survives the clamp to [-1, 1]
 
 
-class FakeEngine:
-    """the recording engine of tests/test_tilepool_cpu.py, with and without keys: the decoded tile is its code everywhere"""
-
-    def latent_shape(self, B, h, w, sf):
-        return (B, 3, h * sf // 4, w * sf // 4)
-
-    def film_prewarm(self, timesteps):
-        pass
-
-    def sample_begin(self, y, noise, tables, sf, scale_factor, prec_encode=None, out=None, keys=None):
-        out.zero_()
-        out[:, 0, 0, 0] = y[:, 0, 0, 0]
-        return out
-
-    def sample_step(self, x, y, t, noise, tables, sf, mask=None, prec=None, pred_xstart=None, keys=None):
-        return x
-
-    def sample_end(self, x0, h, w, sf, scale_factor, prec_decode=None, return_aux=False):
-        return x0[:, 0, 0, 0].view(-1, 1, 1, 1).expand(-1, 3, h * sf, w * sf).contiguous() * 1.0
-
-
-def fake_sampler(**extra):
-    d = create_gaussian_diffusion(**cases.TINY_DIFFUSION)
-    d.set_precision("split", "split", "fp16")
-    return SimpleNamespace(base_diffusion=d, engine=FakeEngine(), autoencoder=object(), padding_offset=16, chop_size=16, chop_stride=12,
-                           seed=77, configs={"model": {"params": {"cond_mask": False}}}, device=torch.device("cpu"), **extra)
-
-
 @pytest.fixture
 def fake_launches(monkeypatch):
     """torch restatements of the pool's launches (the weights are the restatement's); every scatter call is recorded as it was made"""
@@ -244,11 +209,6 @@ def test_unknown_blend_is_rejected():
     with pytest.raises(ValueError, match="unknown tile blend"):
         tiling.check_blend(None)
     assert tiling.BLENDS == ("uniform", "feather") and tiling.feather_ramp(16, 12, 4) == (16, 16) and tiling.feather_ramp(8, 8, 2) == (0, 0)
-
-
-class _OnDevice(torch.Tensor):
-    """a CPU tensor that says it is a device tensor: TileSplitter refuses host tensors, and its kernels are faked below"""
-    is_cuda = True
 
 
 @pytest.mark.parametrize("seed", [None, 5])

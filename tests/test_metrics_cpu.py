@@ -12,14 +12,9 @@ import torch
 
 import helpers as H  # noqa: F401  (puts the repository root on sys.path)
 import _metrics_ref as M
+from _fakes import InstantPool, _OnDevice, lib  # noqa: F401  (fixtures)
 from resshift_amd import _lib, build
 from resshift_amd.sampler import ResShiftSampler
-
-
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
 
 
 @pytest.fixture(scope="module")
@@ -210,11 +205,6 @@ def test_the_symbols_are_declared_and_the_source_is_built(lib):
     assert "rs_sample_to_u8(" in src and "rs_rgb_to_y(" in src and "atomic" not in src.replace("floating-point atomics", "")
 
 
-class _OnDevice(torch.Tensor):
-    """a CPU tensor that says it is a device tensor (tests/test_feather_cpu.py)"""
-    is_cuda = True
-
-
 def test_lib_metrics_rejects_bad_arguments_before_the_library_is_called(monkeypatch):
     monkeypatch.setattr(_lib, "load", lambda: pytest.fail("the library was reached"))
     u8 = torch.zeros(2, 24, 32, 3, dtype=torch.uint8)
@@ -297,26 +287,7 @@ def _read_csv(path):
 def test_inference_scores_every_image_against_the_file_of_its_name(tmp_path, golden, monkeypatch, pool):
     from resshift_amd import tilepool
 
-    class Pool:   # completes every image at the next step: the "sample" is the input
-        def __init__(self, sampler, seeded=False):
-            self.done, self.n = {}, 0
-
-        def submit(self, lq, mask=None, seed=None):
-            self.done[self.n] = lq[0]
-            self.n += 1
-            return self.n - 1
-
-        def waiting_tiles(self):
-            return 0
-
-        def pending(self):
-            return len(self.done)
-
-        def step(self):
-            d, self.done = self.done, {}
-            return d
-
-    monkeypatch.setattr(tilepool, "TilePool", Pool)
+    monkeypatch.setattr(tilepool, "TilePool", InstantPool)   # completes every image at the next step: the "sample" is the input
     src, gtd = _folder(tmp_path, golden)
     s = _stub_sampler()
     rows = s.inference(src, tmp_path / "out", bs=2, pool=pool, gt_path=gtd, metric_border=4, metric_ycbcr=False)

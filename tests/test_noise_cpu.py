@@ -15,6 +15,8 @@ import torch
 
 import helpers as H
 import _philox_ref as P
+import _fakes
+from _fakes import fake_launches, lib  # noqa: F401  (fixtures)
 from oracle import cases
 from resshift_amd import _lib, build
 from resshift_amd.continuous import ContinuousSampler, request_seed
@@ -64,12 +66,6 @@ def test_restatement_moments_and_independence_of_streams_seeds_and_draws():
 
 
 # ---------------------------------------------------------------------------------------------------------------- C ABI
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
-
-
 def test_noise_key_layout_and_exports(lib):
     assert ctypes.sizeof(_lib.NoiseKey) == 16
     assert [f[0] for f in _lib.NoiseKey._fields_] == ["seed", "stream", "reserved"]
@@ -143,12 +139,8 @@ class FakeEngine:
         return x0[:, 0, 0, 0].view(-1, 1, 1, 1).expand(-1, 3, h * sf, w * sf).contiguous() * 1.0
 
 
-def fake_sampler(chop_size=16, chop_stride=12, seed=77):
-    d = create_gaussian_diffusion(**cases.TINY_DIFFUSION)
-    d.set_precision("split", "split", "fp16")
-    return SimpleNamespace(base_diffusion=d, engine=FakeEngine(), autoencoder=object(), padding_offset=16, chop_size=chop_size,
-                           chop_stride=chop_stride, seed=seed, configs={"model": {"params": {"cond_mask": False}}},
-                           device=torch.device("cpu"))
+def fake_sampler(**kw):
+    return _fakes.fake_sampler(engine=FakeEngine(), **kw)
 
 
 def lq_of(code, h=16, w=16):
@@ -216,23 +208,8 @@ class _TensorEngine(FakeEngine):
     """the engine of a default-mode pool is never reached by the rejected calls above"""
 
 
-def test_tile_j_of_an_image_gets_stream_j(monkeypatch):
+def test_tile_j_of_an_image_gets_stream_j(fake_launches):
     """two images (six tiles and three) in a seeded pool of 4: every row of every engine call carries (its image's seed, its tile index)"""
-    from resshift_amd import _lib as L
-
-    def gather(tiles, out_lq, out_mask=None):
-        for k, (src, h0, w0, th, tw) in enumerate(tiles):
-            out_lq[k] = 0
-            out_lq[k, :, :th, :tw] = src[:3, h0:h0 + th, w0:w0 + tw]
-
-    def scatter(tiles, batch, sf):
-        for k, (acc, cnt, Hh, W, h0, w0, th, tw) in enumerate(tiles):
-            acc[:, h0 * sf:(h0 + th) * sf, w0 * sf:(w0 + tw) * sf] += batch[k, :, :th * sf, :tw * sf]
-            cnt[h0 * sf:(h0 + th) * sf, w0 * sf:(w0 + tw) * sf] += 1
-
-    monkeypatch.setattr(L, "tile_gather", gather)
-    monkeypatch.setattr(L, "tile_scatter", scatter)
-    monkeypatch.setattr(L, "tile_finalize", lambda acc, count: acc.div_(count))
     s = fake_sampler()
     tp = TilePool(s, max_batch=4, seeded=True)
     sizes, seeds = [(40, 28), (12, 40)], [901, None]
@@ -323,26 +300,11 @@ def test_inference_seeded_gives_a_file_the_same_seed_for_any_world_size(tmp_path
     def record(code, seed):
         seen.setdefault(code, set()).add(int(seed))
 
-    class Pool:
-        def __init__(self, sampler, seeded=False):
-            assert seeded
-            self.n, self.done = 0, {}
-
-        def submit(self, lq, mask=None, seed=None):
+    class Pool(_fakes.InstantPool):
+        def finished(self, lq, seed):
+            assert self.seeded
             record(int(lq[0, 0, 0, 0]), seed)
-            self.done[self.n] = torch.zeros(3, 32, 32)
-            self.n += 1
-            return self.n - 1
-
-        def waiting_tiles(self):
-            return 0
-
-        def pending(self):
-            return len(self.done)
-
-        def step(self):
-            d, self.done = self.done, {}
-            return d
+            return torch.zeros(3, 32, 32)
 
     monkeypatch.setattr(tilepool, "TilePool", Pool)
     eng = SimpleNamespace(u8_to_input=lambda t: t.permute(0, 3, 1, 2).float(),

@@ -9,24 +9,15 @@ import torch
 import torch.nn.functional as F
 
 import helpers as H  # noqa: F401  (puts the repository root on sys.path)
+import _fakes
+from _fakes import _OnDevice, lib  # noqa: F401  (fixtures)
 from oracle import cases
-from resshift_amd import _lib, build, tiling
+from resshift_amd import _lib, tiling
 from resshift_amd.gaussian_diffusion import create_gaussian_diffusion
 from resshift_amd.tilepool import TilePool, class_key, tile_windows
 
 
-@pytest.fixture(scope="module")
-def lib():
-    build.build(verbose=False)
-    return _lib.load()
-
-
 # ---------------------------------------------------------------------------------------------------------------- geometry
-class _OnDevice(torch.Tensor):
-    """a CPU tensor that says it is a device tensor: TileSplitter refuses host tensors, and its crops are faked below"""
-    is_cuda = True
-
-
 GEOMETRY = [  # H, W, chop_size, chop_stride, sf, padding_offset
     (40, 28, 16, 12, 4, 16),     # the golden tiled fixture: 3 x 2 tiles, the last ones pulled back to the border
     (12, 40, 16, 12, 4, 16),     # one side below the tile: 12 x 16 tiles, padded class 16 x 16
@@ -102,12 +93,8 @@ class FakeEngine:
         return x0[:, 0, 0, 0].view(-1, 1, 1, 1).expand(-1, 3, h * sf, w * sf).contiguous() * 1.0
 
 
-def fake_sampler(cond_mask=False, precision=("split", "split", "fp16"), autoencoder=True, chop_size=16, chop_stride=12, offset=16):
-    d = create_gaussian_diffusion(**cases.TINY_DIFFUSION)
-    d.set_precision(*precision)
-    return SimpleNamespace(base_diffusion=d, engine=FakeEngine(), autoencoder=object() if autoencoder else None, padding_offset=offset,
-                           chop_size=chop_size, chop_stride=chop_stride, configs={"model": {"params": {"cond_mask": cond_mask}}},
-                           device=torch.device("cpu"))
+def fake_sampler(**kw):
+    return _fakes.fake_sampler(engine=FakeEngine(), **kw)
 
 
 @pytest.fixture
