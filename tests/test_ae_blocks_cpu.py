@@ -15,6 +15,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _regimes as R
 import helpers as H
 from oracle import resshift_oracle as oc
 from resshift_amd.config import load_config, to_plain
@@ -179,6 +180,48 @@ def test_fp32_oracle_argmin_meets_the_cap_against_float64(key, B, h, w):
         worst = max(worst, differ)
         assert bad == 0 and differ <= H.VQ_CAP, (b, differ, bad)
     print(f"{key} B={B} {h}x{w}: fp32 oracle vs float64 argmin, worst share of differing positions per image {worst:.2e}")
+
+
+@pytest.mark.parametrize("regime", R.REGIMES)
+def test_regime_is_what_it_claims_and_its_yardstick_is_small(regime):
+    """The regime cases of tests/test_ae_blocks_gpu.py (realsr, B = 1: encode 256 x 256, decode a 40 x 24 latent), oracle only.  quiet: the
+    median GroupNorm variance within 100 eps (the minimum far below eps); loud: both attention softmaxes peaked, conv outputs well inside
+    fp16; every regime finite and centred enough that GroupNorm's E[x^2] - mean^2 in fp32 costs ~1e-6 at most (|mean| / std <= 4 over
+    every group).  The tolerance's yardstick, the float32 oracle's own error on each teacher-forced block, stays <= 1e-4.  (The
+    autoencoder has no zero_module tensors: zero_init is the synthetic draw again, at this batch and these shapes.)"""
+    up, ap, dp = H.realsr_params()
+    _, asd = H.weights(up, ap)
+    sd = R.regime_sd(asd, regime)
+    if regime == "zero_init":
+        assert H.synth.zero_module_names(asd.keys()) == [] and all(torch.equal(sd[k], asd[k]) for k in asd)
+    assert torch.equal(sd["quantize.embedding.weight"], asd["quantize.embedding.weight"])
+    if regime == "quiet":
+        assert all(torch.equal(sd[k], asd[k]) for k in asd if k.startswith(("quant_conv.", "post_quant_conv.")))
+        assert torch.equal(sd["decoder.conv_in.weight"], asd["decoder.conv_in.weight"] * 0.01)
+    sd64 = {k: v.double() for k, v in sd.items()}
+    x, z = R.ae_case_inputs(ap, "encode", 1, 256, 256), R.ae_case_inputs(ap, "decode", 1, 40, 24)
+    var_eps = []
+    for call, plan64, plan32, inp in (("encode", oc.ae_encode_plan(sd64, ap), oc.ae_encode_plan(sd, ap), {"x": x.double()}),
+                                      ("decode", oc.ae_decode_plan(sd64, ap), oc.ae_decode_plan(sd, ap), {"z": z.double()})):
+        with R.probe() as p:
+            env = oc.run_plan(plan64, inp)
+        var_eps += p.var_eps
+        print(f"\n{regime} {call}: GroupNorm var / eps median {p.median_var_eps():.3g} minimum {p.min_var_eps():.3g}, max |mean| / std "
+              f"{p.max_offcentre():.2f}, median largest probability {p.median_pmax():.3f}, largest |conv output| {p.conv:.3g}")
+        assert p.finite and all(bool(torch.isfinite(env[s.name]).all()) for s in plan64 if s.name != "dec.idx")
+        assert p.max_offcentre() <= 4.0
+        if regime == "loud":
+            assert p.median_pmax() >= 0.5 and p.conv <= 1000.0
+        worst = (0.0, "-")
+        for s64, s32 in zip(plan64, plan32):
+            if s64.name in ("dec.idx", "dec.zq"):
+                continue
+            e = max(R.err32(s32, [env[i] for i in s64.inputs], env[s64.name]))
+            worst = max(worst, (e, s64.name))
+            assert e <= R.ERR32_CAP, (s64.name, e)
+        print(f"{regime} {call}: float32 oracle against float64, teacher-forced, worst block {worst[0]:.3e} ({worst[1]})")
+    if regime == "quiet":
+        assert torch.cat(var_eps).median().item() <= 100.0
 
 
 def _plan_dims(cname, call, B, Hh, Ww):

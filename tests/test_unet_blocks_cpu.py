@@ -12,6 +12,7 @@ import sys
 import pytest
 import torch
 
+import _regimes as R
 import helpers as H
 from oracle import resshift_oracle as oc
 from resshift_amd.config import load_config, to_plain
@@ -143,3 +144,65 @@ def test_trace_names_are_the_plan_blocks_without_a_gpu(cname, B, prec, h, w):
         if n not in dims:
             parts = n.split(".")
             assert any(".".join(parts[:k]) in dims for k in range(1, len(parts))), n
+
+
+# ---------------------------------------------------------------- the weight regimes of tests/test_unet_blocks_gpu.py (oracle/synth.py: regime_state_dict)
+def test_regime_state_dict_is_a_pure_function_of_the_synthetic_weights():
+    up, ap, dp = H.realsr_params()
+    usd, _ = H.weights(up, ap)
+    before = {k: v.clone() for k, v in usd.items()}
+    zero = set(H.synth.zero_module_names(usd.keys()))
+    nres = sum(k.endswith(".in_layers.0.weight") for k in usd)
+    assert len(zero) == 2 * nres + 2 and "out.2.weight" in zero and "middle_block.0.out_layers.3.bias" in zero
+    for regime in R.REGIMES:
+        sd = H.synth.regime_state_dict(usd, regime)
+        assert list(sd) == list(usd) and all(torch.equal(usd[k], before[k]) for k in usd)
+        again = H.synth.regime_state_dict(usd, regime)
+        for k, v in sd.items():
+            assert v.shape == usd[k].shape and v.dtype == usd[k].dtype and torch.equal(v, again[k]), k
+            if not torch.is_floating_point(v) or k.endswith("attn_mask"):
+                assert torch.equal(v, usd[k]), k    # index and mask buffers
+            elif regime == "zero_init":
+                assert torch.equal(v, torch.zeros_like(v) if k in zero else usd[k]), k
+    with pytest.raises(ValueError):
+        H.synth.regime_state_dict(usd, "base")
+
+
+@pytest.mark.parametrize("regime", R.REGIMES)
+def test_regime_is_what_it_claims_and_its_yardstick_is_small(regime):
+    """The new cases of tests/test_unet_blocks_gpu.py (realsr, B = 3, 64 x 64, mixed timesteps), oracle only.  A regime must stay what it is
+    there for - quiet: GroupNorm variances of the order of eps and below; loud: peaked softmaxes, GELU arguments far past the fast form's
+    clamp, conv outputs still well inside fp16 - finite, and centred enough that GroupNorm's E[x^2] - mean^2 in fp32 costs ~1e-6 at most
+    (|mean| / std <= 4 over every group: (1 + R^2) 2^-24).  And the tolerance's yardstick, the float32 oracle's own error on each
+    teacher-forced block, stays <= 1e-4.  zero_init: a ResBlock without a skip conv is the identity and the output is zero, bit for bit."""
+    up, ap, dp = H.realsr_params()
+    usd, _ = H.weights(up, ap)
+    sd = R.regime_sd(usd, regime)
+    sd64 = {k: (v.double() if torch.is_floating_point(v) else v) for k, v in sd.items()}
+    x, lq, _, t = R.unet_case_inputs(up, 3, 64, 64, int(dp["steps"]))
+    plan64, plan32 = oc.unet_plan(sd64, up), oc.unet_plan(sd, up)
+    with R.probe() as p:
+        env = oc.run_plan(plan64, {"x": x.double(), "t": torch.tensor(t), "lq": lq.double()})
+    print(f"\n{regime}: GroupNorm var / eps median {p.median_var_eps():.3g} minimum {p.min_var_eps():.3g}, max |mean| / std {p.max_offcentre():.2f}, "
+          f"median largest probability {p.median_pmax():.3f}, largest GELU argument {p.gelu:.3g}, largest |conv output| {p.conv:.3g}")
+    assert p.finite and all(bool(torch.isfinite(env[s.name]).all()) for s in plan64)
+    assert p.max_offcentre() <= 4.0
+    if regime == "quiet":
+        assert p.median_var_eps() <= 0.5
+    if regime == "loud":
+        assert p.median_pmax() >= 0.5 and p.gelu >= 10.0 and p.conv <= 1000.0
+    worst = (0.0, "-")
+    for s64, s32 in zip(plan64, plan32):
+        if s64.name == "emb":
+            continue
+        e = max(R.err32(s32, [env[i] for i in s64.inputs], env[s64.name])) if env[s64.name].abs().max() > 0 else 0.0
+        worst = max(worst, (e, s64.name))
+        assert e <= R.ERR32_CAP, (s64.name, e)
+    print(f"{regime}: float32 oracle against float64, teacher-forced, worst block {worst[0]:.3e} ({worst[1]})")
+    if regime == "zero_init":
+        assert torch.equal(env["head"], torch.zeros_like(env["head"]))
+        same = [s.name for s in plan64 if R.unet_identity_step(s, sd)]
+        assert len(same) >= 4, same
+        for s in plan64:
+            if s.name in same:
+                assert torch.equal(env[s.name], env[s.inputs[0]]), s.name
