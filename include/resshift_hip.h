@@ -337,6 +337,57 @@ int rs_metrics(const void* a, const void* b, int a_is_float, int b_is_float, int
                long long* sse_out, double* ssim_out, void* work, size_t work_bytes, void* stream);
 int rs_rgb_to_y_u8(const uint8_t* rgb_hwc, uint8_t* y, size_t pixels, void* stream);
 
+/* ---- degradation: LQ test sets from ground truth ----------------------------------------------------------
+ * The operators of the reference's Real-ESRGAN degradation (basicsr/data/realesrgan_dataset.py:240-363 degrade_fun), with which the LQ
+ * inputs of the `realsr` configurations are made from ground-truth images; resshift_amd/degrade.py draws a plan and runs them in the
+ * recipe's order.  Stateless.  Tensors are fp32 NCHW, contiguous, with values nominally in [0, 1]; inputs are only read.  Every output
+ * value is a function of its image and its own index alone, every sum has a fixed order, nothing is atomic: a batch is bit for bit its
+ * B = 1 calls.  tests/_degrade_ref.py restates all of it in float64.  Argument errors are found before anything is launched, -2 with
+ * rs_last_error() starting "rs_<name>: ".
+ *
+ * rs_filter2d: basicsr/utils/img_process_util.py filter2D.  A CROSS-CORRELATION - the kernel is not flipped:
+ *       out[b,c,i,j] = sum_{u,v} kernels[kb,u,v] * in[b,c,refl(i + u - k/2, H),refl(j + v - k/2, W)],   taps in row-major ascending order,
+ *   refl = torch's `reflect`, which does not repeat the edge sample:  refl(q, n) = |q| for q < n, 2 (n - 1) - q otherwise.
+ *   kernels [Bk,k,k] fp32 device; Bk = 1 (one kernel for the batch, kb = 0) or B (one per image, for all its channels, kb = b).  k odd,
+ *   k <= 21, k / 2 < min(H, W).  clamp = 1 clamps the result to [0, 1].  One launch, no padded copy; not in place.
+ * rs_interp: F.interpolate(x, mode = "area" (RS_INTERP_AREA) | "bilinear" | "bicubic", align_corners=False), NO antialiasing - the resize the
+ *   degradation uses.  (rs_resize is another function: MATLAB's antialiased kernel, A = -0.5, mirrored borders.)
+ *   scale_h = scale_w = 0: a size (Ho, Wo) was given and source coordinates step by H / Ho;  scale_h, scale_w > 0: a scale factor was given,
+ *   Ho = floor(H * scale_h) (likewise Wo) is required and source coordinates step by 1 / scale, as torch has it.  Either way the scales
+ *   (Ho / H resp. scale_h) must lie in [1/8, 8].   src(i) = step * (i + 0.5) - 0.5  in fp64; the fraction src - floor(src) is rounded to
+ *   fp32 once; weights and sums are fp32.
+ *     bicubic:  taps floor(src) - 1 .. floor(src) + 2, indices clamped to the image, Keys' cubic with A = -0.75, rows of four then the column.
+ *     bilinear: src below 0 is 0; taps floor(src) and floor(src) + 1 (clamped), weights 1 - t and t.
+ *     area:     adaptive average pooling, the mean over the integer window [floor(i H / Ho), ceil((i + 1) H / Ho)) x (likewise for W).
+ *   clamp = 1 clamps the result to [0, 1].  Not in place.
+ * rs_jpeg: basicsr/utils/diffjpeg.py DiffJPEG(differentiable=False); C = 3; quality [B] is a HOST array (by value to the kernel, B <=
+ *   RS_MAX_ROWS), each in (0, 100) exclusive: factor = (q < 50 ? 5000 / q : 200 - 2 q) / 100 in fp32, 0 at q = 100, where the reference
+ *   divides by it.  Per 16 x 16 MCU - H and W are padded on the right / bottom with zeros in RGB, inside the kernel, and cropped on the
+ *   store - forward: x 255; Y = .299 R + .587 G + .114 B, Cb = -.168736 R - .331264 G + .5 B + 128, Cr = .5 R - .418688 G - .081312 B +
+ *   128; chroma 2 x 2 mean; - 128; the 8 x 8 DCT  F[u,v] = s[u,v] sum_{x,y} f[x,y] cos((2x+1) u pi/16) cos((2y+1) v pi/16),  s = 1/4
+ *   a[u] a[v], a[0] = 1/sqrt 2, as a row pass and a column pass, of the four Y blocks and the two chroma blocks; q = rint(F / (table *
+ *   factor)) - an fp32 product, a true division, ties to even - with the luminance resp. chrominance table of the JPEG standard's Annex
+ *   K.  Inverse: q * (table * factor); f = 1/4 sum a[u] a[v] F[u,v] cos.. + 128; chroma by pixel repetition; R = Y + 1.402 Cr', G = Y -
+ *   .344136 Cb' - .714136 Cr', B = Y + 1.772 Cb' (Cb' = Cb - 128, Cr' = Cr - 128); clamp to [0, 255]; / 255.  The INPUT is not clamped:
+ *   that is the caller's, as in the reference.  All constants are the float32 roundings of the reference's double values.  One launch,
+ *   coefficients never leave LDS / registers; `out` may be `in`.
+ * rs_add_noise: out = x + (sigma[b] / 255) n, clamped to [0, 1] when clamp = 1 (basicsr/data/degradations.py add_gaussian_noise_pt).  n =
+ *   the normals rs_noise_fill writes for (keys[b], draw[b]) and per_image_count C*H*W, element by element - or, where gray[b] = 1, those for
+ *   H*W, shared by the image's channels.  keys, draw, sigma, gray are HOST arrays [B], B <= RS_MAX_ROWS.  In fp32: x + c * n with c =
+ *   (float)(sigma / 255), the product and the sum rounded separately, as the reference's tensor operations round them.  `out` may be `x`.
+ * rs_unit_to_u8: planar fp32 [B,C,H,W] in [0,1] -> interleaved uint8 [B,H,W,C] = clamp(rint(x * 255), 0, 255), ties to even: the recipe's last
+ *   line, and what becomes the PNG. */
+#define RS_INTERP_AREA 0
+#define RS_INTERP_BILINEAR 1
+#define RS_INTERP_BICUBIC 2
+int rs_filter2d(const float* in, const float* kernels, float* out, int B, int C, int H, int W, int k, int Bk, int clamp, void* stream);
+int rs_interp(const float* in, float* out, int B, int C, int H, int W, int Ho, int Wo, double scale_h, double scale_w, int mode, int clamp,
+              void* stream);
+int rs_jpeg(const float* in, float* out, const float* quality, int B, int C, int H, int W, void* stream);
+int rs_add_noise(const float* x, float* out, const rs_noise_key* keys, const int* draw, const float* sigma, const int* gray, int B, int C, int H,
+                 int W, int clamp, void* stream);
+int rs_unit_to_u8(const float* src_f32_nchw, void* dst_u8_nhwc, int B, int C, int H, int W, void* stream);
+
 /* uint8 pre / post processing on the device.
  * rs_u8_to_input:  interleaved uint8 [B,H,W,C] -> planar fp32 [B,C,H,W] in [-1,1]  ((v/255 - 0.5)/0.5; replaces
  *                  datapipe/datasets.py:59-63 ToTensor + Normalize on the host)

@@ -145,6 +145,11 @@ SIGNATURES = {
     "rs_metrics_work_bytes": (_SZ, [_I] * 6),
     "rs_metrics": (_I, [_P, _P] + [_I] * 8 + [_P, _P, _P, _SZ, _P]),
     "rs_rgb_to_y_u8": (_I, [_P, _P, _SZ, _P]),
+    "rs_filter2d": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
+    "rs_interp": (_I, [_P, _P] + [_I] * 6 + [C.c_double, C.c_double, _I, _I, _P]),
+    "rs_jpeg": (_I, [_P, _P, C.POINTER(C.c_float)] + [_I] * 4 + [_P]),
+    "rs_add_noise": (_I, [_P, _P, C.POINTER(NoiseKey), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)] + [_I] * 5 + [_P]),
+    "rs_unit_to_u8": (_I, [_P, _P] + [_I] * 4 + [_P]),
     "rs_u8_to_input": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rs_output_to_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rs_arena_bytes": (_SZ, [_P]),
@@ -364,6 +369,129 @@ def resize(x, scale=None, size=None, clamp=False):
         raise ValueError(f"resize: the scales ({sh:.6g}, {sw:.6g}) of {H} x {W} -> {Ho} x {Wo} must lie in [1/8, 8]")
     out = torch.empty((B, Cc, Ho, Wo), device=x.device, dtype=torch.float32)
     check(load().rs_resize(x.data_ptr(), out.data_ptr(), B, Cc, H, W, Ho, Wo, sh, sw, 1 if clamp else 0, current_stream_ptr()), "rs_resize")
+    return out
+
+
+# ---- degradation operators (include/resshift_hip.h "degradation") -------------------------------------------------------
+FILTER_KMAX = 21
+INTERP_MODES = {"area": 0, "bilinear": 1, "bicubic": 2}
+
+
+def _image_batch(x, who):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4):
+        raise ValueError(f"{who}: x [B,C,H,W] must be a contiguous float32 device tensor")
+    return tuple(int(v) for v in x.shape)
+
+
+def filter2d(x, kernels, clamp=False):
+    """rs_filter2d: x [B,C,H,W] cross-correlated (the kernel is not flipped) with `kernels` [Bk,k,k] behind torch's `reflect` padding - the
+    reference's filter2D.  Bk is 1 (one kernel for the batch) or B (one per image, for all its channels); k is odd, at most 21, and k // 2
+    is below min(H, W).  `clamp` clamps the result to [0, 1].  Contiguous fp32 device tensors; returns a new tensor."""
+    B, Cc, H, W = _image_batch(x, "filter2d")
+    if not (isinstance(kernels, torch.Tensor) and kernels.is_cuda and kernels.dtype == torch.float32 and kernels.is_contiguous() and kernels.dim() == 3
+            and kernels.shape[1] == kernels.shape[2] and kernels.device == x.device):
+        raise ValueError("filter2d: kernels [Bk,k,k] must be a contiguous float32 tensor on x's device")
+    Bk, k = int(kernels.shape[0]), int(kernels.shape[1])
+    if k % 2 == 0 or k > FILTER_KMAX:
+        raise ValueError(f"filter2d: k must be odd and at most {FILTER_KMAX}, not {k}")
+    if k // 2 >= min(H, W):
+        raise ValueError(f"filter2d: k // 2 = {k // 2} must be below min(H, W) = {min(H, W)} (one reflection per border)")
+    if Bk not in (1, B):
+        raise ValueError(f"filter2d: {Bk} kernels for {B} images (1 or B)")
+    out = torch.empty_like(x)
+    check(load().rs_filter2d(x.data_ptr(), kernels.data_ptr(), out.data_ptr(), B, Cc, H, W, k, Bk, 1 if clamp else 0, current_stream_ptr()), "rs_filter2d")
+    return out
+
+
+def interp_size(n, scale_factor) -> int:
+    """floor(n * scale_factor) in float64: F.interpolate's output length for a scale factor"""
+    return int(math.floor(float(n) * float(scale_factor)))
+
+
+def interpolate(x, scale_factor=None, size=None, mode="bilinear", clamp=False):
+    """rs_interp: F.interpolate(x, scale_factor= | size=, mode="area" | "bilinear" | "bicubic", align_corners=False) without antialiasing on
+    a contiguous fp32 device tensor [B,C,H,W] - the resize of the degradation recipe (`resize` is MATLAB's antialiased one).  Exactly one
+    of `scale_factor` (a number for both axes: output floor(H * s), coordinates step by 1 / s) and `size` = (Ho, Wo) (coordinates step by H
+    / Ho).  The scales must lie in [1/8, 8].  `clamp` clamps the result to [0, 1].  Returns a new tensor."""
+    B, Cc, H, W = _image_batch(x, "interpolate")
+    if mode not in INTERP_MODES:
+        raise ValueError(f"interpolate: unknown mode {mode!r} (one of {sorted(INTERP_MODES)})")
+    if (scale_factor is None) == (size is None):
+        raise ValueError("interpolate: give exactly one of scale_factor and size")
+    if scale_factor is not None:
+        if isinstance(scale_factor, bool) or not isinstance(scale_factor, (int, float)) or not scale_factor > 0:
+            raise ValueError(f"interpolate: scale_factor must be a positive number, not {scale_factor!r}")
+        s = float(scale_factor)
+        Ho, Wo, sh, sw = interp_size(H, s), interp_size(W, s), s, s
+        inside = RESIZE_SCALES[0] <= s <= RESIZE_SCALES[1] and Ho >= 1 and Wo >= 1
+    else:
+        if not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and not isinstance(v, bool) and v > 0 for v in size)):
+            raise ValueError(f"interpolate: size must be two positive integers (Ho, Wo), not {size!r}")
+        Ho, Wo = size
+        sh = sw = 0.0
+        inside = all(RESIZE_SCALES[0] <= v <= RESIZE_SCALES[1] for v in (Ho / H, Wo / W))
+    if not inside:
+        raise ValueError(f"interpolate: the scales of {H} x {W} -> {Ho} x {Wo} must lie in [1/8, 8]")
+    out = torch.empty((B, Cc, Ho, Wo), device=x.device, dtype=torch.float32)
+    check(load().rs_interp(x.data_ptr(), out.data_ptr(), B, Cc, H, W, Ho, Wo, sh, sw, INTERP_MODES[mode], 1 if clamp else 0, current_stream_ptr()),
+          "rs_interp")
+    return out
+
+
+def _per_image(values, B, who, what):
+    vals = [values] * B if isinstance(values, (int, float)) and not isinstance(values, bool) else list(values)
+    if len(vals) != B:
+        raise ValueError(f"{who}: {B} images but {len(vals)} {what}")
+    return vals
+
+
+def jpeg(x, quality):
+    """rs_jpeg: the reference's DiffJPEG(differentiable=False) on x [B,3,H,W] (a contiguous fp32 device tensor in [0,1] - the caller clamps),
+    `quality` one number per image (or one for all) in (0, 100) exclusive.  Batches above RS_MAX_ROWS go in chunks (the qualities travel by
+    value).  Returns a new tensor."""
+    B, Cc, H, W = _image_batch(x, "jpeg")
+    if Cc != 3:
+        raise ValueError(f"jpeg: C must be 3 (RGB), not {Cc}")
+    q = [float(v) for v in _per_image(quality, B, "jpeg", "qualities")]
+    if not all(0.0 < v < 100.0 for v in q):
+        raise ValueError(f"jpeg: every quality must lie in (0, 100), not {q}")
+    out = torch.empty_like(x)
+    lib = load()
+    for b0 in range(0, B, RS_MAX_ROWS):
+        n = min(RS_MAX_ROWS, B - b0)
+        check(lib.rs_jpeg(x[b0:].data_ptr(), out[b0:].data_ptr(), (C.c_float * n)(*q[b0:b0 + n]), n, 3, H, W, current_stream_ptr()), "rs_jpeg")
+    return out
+
+
+def add_noise(x, keys, sigma, gray=False, draw=0, clamp=True):
+    """rs_add_noise: x [B,C,H,W] + (sigma[b] / 255) n, clamped to [0, 1] unless clamp=False.  n = the normals `noise_fill` gives for
+    (keys[b], draw[b]) and the shape (C, H, W); an image whose `gray` flag is set takes those for (1, H, W) in every channel.  `sigma`, `gray`
+    and `draw` are one value per image or one for all.  Returns a new tensor."""
+    B, Cc, H, W = _image_batch(x, "add_noise")
+    if len(keys) != B:
+        raise ValueError(f"add_noise: {B} images but {len(keys)} keys")
+    sg = [float(v) for v in _per_image(sigma, B, "add_noise", "sigmas")]
+    gr = [int(bool(v)) for v in ([gray] * B if isinstance(gray, (bool, int)) else _per_image(gray, B, "add_noise", "gray flags"))]
+    dr = [int(v) for v in _per_image(draw, B, "add_noise", "draw indices")]
+    if not all(math.isfinite(v) and v >= 0 for v in sg):
+        raise ValueError(f"add_noise: every sigma must be finite and not negative, not {sg}")
+    if any(v < 0 for v in dr):
+        raise ValueError(f"add_noise: negative draw index in {dr}")
+    out = torch.empty_like(x)
+    lib = load()
+    for b0 in range(0, B, RS_MAX_ROWS):
+        n = min(RS_MAX_ROWS, B - b0)
+        s = slice(b0, b0 + n)
+        check(lib.rs_add_noise(x[b0:].data_ptr(), out[b0:].data_ptr(), noise_keys(list(keys[s])), (C.c_int * n)(*dr[s]), (C.c_float * n)(*sg[s]),
+                               (C.c_int * n)(*gr[s]), n, Cc, H, W, 1 if clamp else 0, current_stream_ptr()), "rs_add_noise")
+    return out
+
+
+def unit_to_u8(x):
+    """rs_unit_to_u8: fp32 [B,C,H,W] in [0,1] (a contiguous device tensor) -> uint8 [B,H,W,C] = clamp(rint(x * 255), 0, 255), ties to even"""
+    B, Cc, H, W = _image_batch(x, "unit_to_u8")
+    out = torch.empty((B, H, W, Cc), device=x.device, dtype=torch.uint8)
+    check(load().rs_unit_to_u8(x.data_ptr(), out.data_ptr(), B, Cc, H, W, current_stream_ptr()), "rs_unit_to_u8")
     return out
 
 

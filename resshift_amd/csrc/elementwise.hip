@@ -10,6 +10,7 @@
 #include "launchers.h"
 #include "philox.h"
 #include <algorithm>
+#include <cmath>
 #include <string>
 
 namespace {
@@ -165,6 +166,45 @@ __global__ __launch_bounds__(256) void axpbypcz_seeded_kernel(const float* x, co
             for (int e = 0; e < 4; ++e)
                 if (4 * q + e < per) y[g + e] = axpbypcz_combine(ca, x[g + e], has_z, cb, has_z ? z[g + e] : 0.f, has_n, cc, n[e]);
         }
+    }
+}
+
+// out = x + c[b] n per image b of an fp32 NCHW batch, optionally clamped to [0, 1]: the Gaussian noise of the degradation recipe (DESIGN.md
+// 7h; basicsr/data/degradations.py add_gaussian_noise_pt with c = sigma / 255).  n = the normals noise_fill_kernel writes for the draw
+// nk.draw[b] of key nk.k[b] and the shape (C, H, W) - or, for an image with gray[b] set, for the shape (1, H, W), shared by its channels.
+// Thread = one Philox call = four noise elements.  The product and the sum are rounded separately (non-contracting intrinsics), as the
+// reference's tensor operations round them.
+struct NoiseRows { float c[RS_MAX_ROWS]; unsigned char gray[RS_MAX_ROWS]; };
+__global__ __launch_bounds__(256) void add_noise_kernel(const float* __restrict__ x, float* __restrict__ out, NoiseRows k, RowKeys nk, int C, long long HW,
+                                                        int clamp) {
+    const int b = blockIdx.y;
+    const rs_noise_key key = nk.k[b];
+    const uint32_t draw = (uint32_t)nk.draw[b];
+    const float c = k.c[b];
+    const bool gray = k.gray[b] != 0;
+    const long long base = (long long)b * C * HW, per = gray ? HW : C * HW, nq = (per + 3) / 4;
+    const int reps = gray ? C : 1;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
+        float n[4];
+        rs_noise4(key.seed, key.stream, draw, (uint32_t)q, n);
+        for (int ch = 0; ch < reps; ++ch)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const long long i = 4 * q + e;
+                if (i < per) {
+                    float v = __fadd_rn(x[base + ch * HW + i], __fmul_rn(c, n[e]));
+                    if (clamp) v = fminf(fmaxf(v, 0.0f), 1.0f);
+                    out[base + ch * HW + i] = v;
+                }
+            }
+    }
+}
+
+// planar fp32 [B,C,H,W] in [0,1] -> interleaved uint8 [B,H,W,C]: clamp, * 255, round half to even (rs_unit_to_u8 of common.h)
+__global__ void unit_to_u8_kernel(const float* __restrict__ src, unsigned char* __restrict__ dst, long long npix, long long HW, int C) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long long)gridDim.x * blockDim.x) {
+        const long long b = i / HW, hw = i - b * HW;
+        for (int c = 0; c < C; ++c) dst[i * C + c] = rs_unit_to_u8(src[(b * C + c) * HW + hw]);
     }
 }
 
@@ -616,6 +656,42 @@ int rs_noise_fill(const rs_noise_key* keys, const int* draw, float* out, long lo
     const dim3 grid = seeded_grid(per_image_count, B);
     if ((per_image_count % 4) == 0 && al16f(out)) hipLaunchKernelGGL(noise_fill_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, out, nk, per_image_count);
     else hipLaunchKernelGGL(noise_fill_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, out, nk, per_image_count);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int rs_add_noise(const float* x, float* out, const rs_noise_key* keys, const int* draw, const float* sigma, const int* gray, int B, int C, int H,
+                 int W, int clamp, void* stream) {
+    const std::string who = "rs_add_noise: ";
+    if (B < 1 || B > RS_MAX_ROWS) return rs_set_last_error((who + "B must be 1 .. RS_MAX_ROWS").c_str(), -2);
+    if (const char* e = noise_keys_error(keys, B)) return rs_set_last_error((who + e).c_str(), -2);
+    if (!x || !out || !draw || !sigma || !gray) return rs_set_last_error((who + "null pointer (x / out / draw / sigma / gray)").c_str(), -2);
+    if (C < 1 || H < 1 || W < 1) return rs_set_last_error((who + "C, H and W must be positive").c_str(), -2);
+    if ((long long)C * H * W > 0x3ffffffffLL) return rs_set_last_error((who + "an image has more than 2^34 - 1 elements").c_str(), -2);
+    if (clamp != 0 && clamp != 1) return rs_set_last_error((who + "clamp must be 0 or 1").c_str(), -2);
+    const long long HW = (long long)H * W, n = (long long)B * C * HW;
+    const uintptr_t x0 = (uintptr_t)x, o0 = (uintptr_t)out, bytes = (uintptr_t)n * sizeof(float);
+    if (x0 != o0 && o0 < x0 + bytes && x0 < o0 + bytes) return rs_set_last_error((who + "`out` partly overlaps `x` (in place or apart)").c_str(), -2);
+    NoiseRows k{};
+    RowKeys nk{};
+    bool any_color = false;
+    for (int b = 0; b < B; ++b) {
+        if (draw[b] < 0) return rs_set_last_error((who + "negative draw index").c_str(), -2);
+        if (!(sigma[b] >= 0.0f) || !std::isfinite(sigma[b])) return rs_set_last_error((who + "every sigma must be finite and not negative").c_str(), -2);
+        if (gray[b] != 0 && gray[b] != 1) return rs_set_last_error((who + "every gray flag must be 0 or 1").c_str(), -2);
+        k.c[b] = (float)((double)sigma[b] / 255.0);
+        k.gray[b] = (unsigned char)gray[b];
+        any_color |= gray[b] == 0;
+        nk.k[b] = keys[b]; nk.draw[b] = draw[b];
+    }
+    hipLaunchKernelGGL(add_noise_kernel, seeded_grid(any_color ? C * HW : HW, B), dim3(256), 0, (hipStream_t)stream, x, out, k, nk, C, HW, clamp);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int rs_unit_to_u8(const float* src_f32_nchw, void* dst_u8_nhwc, int B, int C, int H, int W, void* stream) {
+    if (!src_f32_nchw || !dst_u8_nhwc) return rs_set_last_error("rs_unit_to_u8: null tensor (src / dst)", -2);
+    if (B < 1 || C < 1 || H < 1 || W < 1) return rs_set_last_error("rs_unit_to_u8: B, C, H and W must be positive", -2);
+    const long long HW = (long long)H * W, npix = (long long)B * HW;
+    hipLaunchKernelGGL(unit_to_u8_kernel, dim3(nblk(npix)), dim3(256), 0, (hipStream_t)stream, src_f32_nchw, (unsigned char*)dst_u8_nhwc, npix, HW, C);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -211,6 +211,33 @@ class Engine:
         with torch.cuda.device(self.device):
             return _lib.resize(self._f32c(x), scale=scale, size=size, clamp=clamp)
 
+    # the degradation operators (resshift_amd/degrade.py runs them in the recipe's order): images in [0, 1], new tensors
+    def filter2d(self, x, kernels, clamp=False):
+        """The reference's filter2D: x [B,C,H,W] cross-correlated with `kernels` [1 | B,k,k] behind `reflect` padding (rs_filter2d)."""
+        with torch.cuda.device(self.device):
+            return _lib.filter2d(self._f32c(x), self._f32c(kernels), clamp=clamp)
+
+    def interpolate(self, x, scale_factor=None, size=None, mode="bilinear", clamp=False):
+        """F.interpolate(x, scale_factor= | size=, mode="area" | "bilinear" | "bicubic") without antialiasing (rs_interp); `resize` is
+        MATLAB's antialiased resize."""
+        with torch.cuda.device(self.device):
+            return _lib.interpolate(self._f32c(x), scale_factor=scale_factor, size=size, mode=mode, clamp=clamp)
+
+    def jpeg(self, x, quality):
+        """The reference's DiffJPEG(differentiable=False) on x [B,3,H,W] in [0,1], one quality in (0, 100) per image (rs_jpeg)."""
+        with torch.cuda.device(self.device):
+            return _lib.jpeg(self._f32c(x), quality)
+
+    def add_noise(self, x, keys, sigma, gray=False, draw=0, clamp=True):
+        """x + (sigma / 255) n with n = noise_fill(keys, draw, (C | 1, H, W)) generated in registers, clamped to [0, 1] (rs_add_noise)."""
+        with torch.cuda.device(self.device):
+            return _lib.add_noise(self._f32c(x), keys, sigma, gray=gray, draw=draw, clamp=clamp)
+
+    def unit_to_u8(self, x):
+        """fp32 [B,C,H,W] in [0,1] -> uint8 [B,H,W,C], clamp(rint(x * 255), 0, 255) (rs_unit_to_u8)."""
+        with torch.cuda.device(self.device):
+            return _lib.unit_to_u8(self._f32c(x))
+
     def metrics(self, sr, gt, border=0, ycbcr=True):
         """PSNR / SSIM of the batch `sr` against the ground truth `gt` on uint8 pixels, as the reference's calculate_psnr / calculate_ssim
         score them (rs_metrics).  Each is uint8 [B,H,W,C] or a float tensor [B,C,H,W] in [-1,1], which is quantised exactly

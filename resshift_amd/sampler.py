@@ -370,6 +370,26 @@ class ResShiftSampler(BaseSampler):
         self.write_log(f"Processing done, enjoy the results in {out_path}")
         return rows
 
+    def make_lq(self, gt_path, lq_path, opts=None, seed=None) -> dict:
+        """A folder of ground-truth images -> a folder of LQ PNGs plus plans.json, by the reference's Real-ESRGAN degradation on the device
+        (degrade.make_testset) with this sampler's `sf`, seed and device; the listing is sharded over the ranks like
+        `inference`'s, rank 0 writes plans.json.  Then `inference(lq_path, out, gt_path=gt_path)` closes the loop.  Returns {stem: plan}
+        for the whole input on every rank."""
+        from . import degrade
+
+        files = degrade.list_images(gt_path)
+        mine = [first + j for first, part in self._shares(files, self.num_gpus) for j in range(len(part))]
+        plans = degrade.make_testset(gt_path, lq_path, sf=self.sf, opts=degrade.REALESRGAN_TESTING if opts is None else opts,
+                                     seed=self.seed if seed is None else seed, device=getattr(self, "engine", None) or self.device, positions=mine)
+        if self.num_gpus > 1 and dist.is_available() and dist.is_initialized():
+            parts = [None] * dist.get_world_size()
+            dist.all_gather_object(parts, plans)
+            plans = {k: v for part in parts for k, v in part.items()}
+        if self.rank == 0:
+            degrade.write_plans(lq_path, plans)
+        sharding.barrier()
+        return plans
+
     def _shares(self, files, bs):
         """(position of mine[0] in the whole listing, mine) for every batch of `bs` files that gives this rank a share `mine`"""
         micro = math.ceil(bs / self.num_gpus)   # sampler.py:274-277: the slice width comes from bs, also on the last, partial batch
