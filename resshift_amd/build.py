@@ -93,5 +93,30 @@ def build_testhooks(verbose: bool = False) -> str:
     return out
 
 
+def gfx950_code_objects(lib_path: str):
+    """Yield the gfx950 code objects (ELF images, as bytes) of a built library: the clang offload bundles inside the .so are walked by
+    hand (magic, entry table).  The register-budget tests and scripts/kernel_digest.py read them with llvm-readelf."""
+    import struct
+
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    with open(lib_path, "rb") as fh:
+        data = fh.read()
+    pos = 0
+    while True:
+        i = data.find(magic, pos)
+        if i < 0:
+            return
+        n = struct.unpack_from("<Q", data, i + 24)[0]
+        q = i + 32
+        for _ in range(n):
+            off, size, tl = struct.unpack_from("<QQQ", data, q)
+            q += 24
+            triple = data[q:q + tl].decode()
+            q += tl
+            if "gfx950" in triple and size:
+                yield data[i + off:i + off + size]
+        pos = i + 24
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)

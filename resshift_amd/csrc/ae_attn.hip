@@ -22,11 +22,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr3_t;
-__device__ __forceinline__ void lds_dma16_fa(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr3_t)lds, 16, voff, 0, 0, 0);
-}
-
 struct FlashParams {
     const f16* q;      // [z][T][ldq]   (C channels used)
     const f16* k;      // [z][T][ldk]
@@ -68,7 +63,7 @@ __global__ __launch_bounds__(512, 2) void ae_flash_attn_kernel(FlashParams p) {
             const int rho = grp * 8 + rsub;
             const int kappa = 32 * (rho >> 5) + 8 * ((rho & 15) >> 2) + 4 * ((rho >> 4) & 1) + (rho & 3);
             const unsigned off = (unsigned)(((long long)(kb * BK + kappa) * p.ldk + st * 64 + kcp * 8) * 2);
-            lds_dma16_fa(rk, ks_ + st * (BK * 128) + (grp * 8) * 128, off);
+            lds_dma16(rk, ks_ + st * (BK * 128) + (grp * 8) * 128, off);
         }
     };
     // V^T tile: LDS row d holds keys kb * 64 .. + 63 of channel d (natural order); C / 8 pieces of 8 rows, wave w owns pieces w, w + 8, ...
@@ -78,7 +73,7 @@ __global__ __launch_bounds__(512, 2) void ae_flash_attn_kernel(FlashParams p) {
             const int piece = wave + 8 * i;
             const int d = piece * 8 + rsub;
             const unsigned off = (unsigned)(((long long)d * T + kb * BK + kcp * 8) * 2);
-            lds_dma16_fa(rv, vs_ + (piece * 8) * 128, off);
+            lds_dma16(rv, vs_ + (piece * 8) * 128, off);
         }
     };
     const int nkb = T / BK;

@@ -22,11 +22,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr4_t;
-__device__ __forceinline__ void lds_dma16_fs(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr4_t)lds, 16, voff, 0, 0, 0);
-}
-
 struct FlashSplitParams {
     const f16* q;      // [z][T] pixel records [ldq halfs hi | ldq halfs lo] (C channels used)
     const f16* k;      // [z][T] records [ldk hi | ldk lo]
@@ -72,7 +67,7 @@ __global__ __launch_bounds__(512, 2) void ae_flash_attn_split_kernel(FlashSplitP
             const int rho = grp * 8 + rsub;
             const int kappa = 8 * ((rho & 15) >> 2) + 4 * ((rho >> 4) & 1) + (rho & 3);
             const unsigned off = (unsigned)(((long long)(kb * BK + kappa) * p.ldk * 2 + (kcp >> 2) * p.ldk + st * 32 + (kcp & 3) * 8) * 2);
-            lds_dma16_fs(rk, ks_ + st * (BK * 128) + (grp * 8) * 128, off);
+            lds_dma16(rk, ks_ + st * (BK * 128) + (grp * 8) * 128, off);
         }
     };
     // V^T tile: LDS row d holds keys kb * 32 .. + 31 of channel d (natural order), hi half then lo half; C / 8 pieces of 8 rows
@@ -82,7 +77,7 @@ __global__ __launch_bounds__(512, 2) void ae_flash_attn_split_kernel(FlashSplitP
             const int piece = wave + 8 * i;
             const int d = piece * 8 + rsub;
             const unsigned off = (unsigned)(((long long)d * T * 2 + (kcp >> 2) * (long long)T + kb * BK + (kcp & 3) * 8) * 2);
-            lds_dma16_fs(rv, vs_ + (piece * 8) * 128, off);
+            lds_dma16(rv, vs_ + (piece * 8) * 128, off);
         }
     };
     const int nkb = T / BK;

@@ -16,6 +16,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 
 typedef _Float16 f16;
@@ -62,6 +64,13 @@ struct RsAttrFlags {   // "hipFuncSetAttribute done on this device?" of one kern
     bool need() { const int s = rs_device_slot(); if (s >= RS_MAX_DEVICES) return true; if (done[s]) return false; done[s] = true; return true; }
 };
 
+// THE reader of the RS_* environment knobs (DESIGN.md has the table).  A call reads the environment; a knob that is read once keeps the
+// result in a function-local static at its site.
+static inline bool rs_env_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }   // on unless the value starts with 0
+static inline long long rs_env_int(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
+static inline bool rs_env_set(const char* name) { return getenv(name) != nullptr; }   // present, whatever the value
+static inline bool rs_env_is(const char* name, const char* value) { const char* e = getenv(name); return e && !strcmp(e, value); }   // the one word-valued knob (RS_RESIZE_LDS)
+
 // Between a wave's writes to ITS OWN epilogue staging tile and its reads of that tile (and before the tile is overwritten) the wave's own
 // LDS instruction order is all that is needed: a workgroup barrier there makes every wave wait for the slowest one four times per
 // split-storage epilogue.  -DRS_EPI_FULL_BARRIER restores the barriers (A/B builds).
@@ -88,6 +97,15 @@ __device__ __forceinline__ float rs_sum16(float v) {
 }
 
 // ---- device helpers -------------------------------------------------------
+// LDS-DMA (`buffer_load_dwordx4 ... lds`): 16 bytes per lane from buffer `r` at byte offset voff (per lane) + soff (wave-uniform) to the
+// wave-uniform LDS address `lds` + lane * 16.  NB: keep the builtin inside a plain __device__ function: called directly from a kernel
+// template hipcc 7.2 silently drops the template's HOST stubs (undefined __device_stub__ symbols at load time).
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff, unsigned soff = 0) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds, 16, voff, soff, 0, 0);
+}
+template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
 // THE quantiser of a [0,1] value to a uint8 pixel (utils/util_image.py:245-269 tensor2img): clamp, * 255, round half to even.  The
 // non-contracting intrinsic rounds like the reference's separate ops.  rs_output_to_u8 and the float inputs of rs_metrics share it.
 __device__ __forceinline__ unsigned char rs_unit_to_u8(float v) {
@@ -292,7 +310,7 @@ struct IGemmParams {
 enum ConvKernel { CK_NONE = 0, CK_WINO, CK_HALO, CK_HALO_SEG, CK_SPLIT, CK_IGEMM3, CK_IGEMM2, CK_IGEMM };   // CK_NONE: no kernel takes the launch
 struct ConvPlan {
     int kernel;      // ConvKernel (halo: CK_HALO = 256-pixel tiles on big planes, CK_HALO_SEG = the small-plane geometries)
-    int BP, BC;      // pixel tile (halo: tile width TW; igemm2: its variant code) and channel tile
+    int BP, BC;      // pixel tile (halo: tile width TW) and channel tile
     int SEG;         // CK_HALO_SEG: 16 = one 16 x 16 image per tile, 8 = four 8 x 8 images per tile
     int splitk;      // K slices (1: none); > 1 needs IGemmParams::partial = [splitk][M][Cout] floats
     int stats_px;    // pixels per IGemmParams::ystats slab if the launch is asked for output statistics (0: it cannot produce them)

@@ -22,7 +22,7 @@ int fail(const std::string& m) { g_err = m; return -1; }
 #ifdef RS_TEST_HOOKS
 static bool rs_fake_device() {
     static const bool fake = []() {
-        if (!getenv("RS_FAKE_DEVICE")) return false;
+        if (!rs_env_set("RS_FAKE_DEVICE")) return false;
         int n = 0;
         const hipError_t e = hipGetDeviceCount(&n);
         // (only the definite answer "this host has no HIP device" enables the hook - a driver hiccup on a GPU box must not)
@@ -206,7 +206,7 @@ struct rs_engine : Model {
                     last_shapes += c;
                 }
                 std::sort(rows.begin(), rows.end());
-                static const bool shapes = getenv("RS_PROF_SHAPES") != nullptr;
+                static const bool shapes = rs_env_set("RS_PROF_SHAPES");
                 if (shapes) for (auto& rw : rows) fprintf(stderr, "[shapes] %s\n", rw.second.c_str());
             }
             // wall time of the parts (events at every change of part, the call's end closes the last one)

@@ -404,25 +404,24 @@ extern "C" int rs_conv_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz
     }
     if (!(in_dt == RS_F16 && (out_dt == RS_F16 || out_dt == RS_F32)) && !(in_dt == RS_F32 && out_dt == RS_F32)) return -2;
     // second-generation kernel (LDS-DMA ring) for everything that fills the chip; RS_IGEMM_V2=0 forces the first one
-    static const bool use_v2 = []() { const char* e = getenv("RS_IGEMM_V2"); return !(e && e[0] == '0'); }();
+    static const bool use_v2 = rs_env_on("RS_IGEMM_V2");
     const bool v2 = use_v2 && p.C1 == 0;
-    const int kbytes = p.Ktot * (in_dt == RS_F16 ? 2 : 4);
     int BP, BC, bp2 = 0, bc2 = 0, bc3 = 0, sk = 1;
     pick_tile(p.M, p.Cout, BP, BC);
     if (can_split) {   // the tile a single launch will run on: igemm2's wherever it takes the launch (every one with more than 64 channels)
-        const bool on2 = v2 && rs_igemm2_pick(p.M, p.Cout, kbytes, 1, &bp2, &bc2);
-        const int px = on2 ? rs_igemm2_tile_px(bp2) : BP, bc = on2 ? bc2 : BC;
+        const bool on2 = v2 && rs_igemm2_pick(p.M, p.Cout, 1, &bp2, &bc2);
+        const int px = on2 ? bp2 : BP, bc = on2 ? bc2 : BC;
         const int tiles = ((p.M + px - 1) / px) * ((p.Cout + bc - 1) / bc);
         const int bk = in_dt == RS_F16 ? 64 : 32;
         const int nk = (p.Ktot + bk - 1) / bk;
         // aim at ~3 workgroups per CU, keep >= 6 K stages per slice (RS_SPLITK_TARGET / RS_SPLITK_MINSTAGES override for tuning)
-        static const int target = []() { const char* e = getenv("RS_SPLITK_TARGET"); return e ? atoi(e) : 512; }();
-        static const int minst = []() { const char* e = getenv("RS_SPLITK_MINSTAGES"); return e ? atoi(e) : 8; }();
+        static const int target = (int)rs_env_int("RS_SPLITK_TARGET", 512);
+        static const int minst = (int)rs_env_int("RS_SPLITK_MINSTAGES", 8);
         if (tiles < (px == 64 ? 400 : 200) && nk >= 16 && !(p.Cout & 3)) sk = std::max(1, std::min(std::min((target + tiles - 1) / tiles, 16), nk / minst));
     }
     // third generation (256-pixel tiles, one workgroup per CU, register-pipelined fragments) for the long-K fp16 layers that fill the chip
     if (v2 && rs_igemm3_pick(p.M, p.Cout, p.Ktot, in_dt, nz, sk, &bc3)) *pl = ConvPlan{CK_IGEMM3, 256, bc3, 0, sk, 0};
-    else if (v2 && rs_igemm2_pick(p.M, p.Cout, kbytes, nz * sk, &bp2, &bc2)) *pl = ConvPlan{CK_IGEMM2, bp2, bc2, 0, sk, 0};
+    else if (v2 && rs_igemm2_pick(p.M, p.Cout, nz * sk, &bp2, &bc2)) *pl = ConvPlan{CK_IGEMM2, bp2, bc2, 0, sk, 0};
     else *pl = ConvPlan{CK_IGEMM, BP, BC, 0, sk, 0};
     return 0;
 }

@@ -4,13 +4,12 @@
 //     the ds_read_b128 fragment reads conflict-free is applied on the SOURCE side: lane (row r, slot c) fetches the
 //     K-chunk c ^ (r & 7) - free here because every lane computes its own gather address anyway.  Out-of-image taps,
 //     ragged rows and the K tail use a byte offset beyond the descriptor's num_records: the hardware returns zeros;
-//   * template <TI, TO, BP, BC, NS, NWV>: BP x BC output tile, NS-slot ring, NWV waves (NWV/2 pixel-waves x 2
-//     channel-waves).  Default instantiation: 128 x {128,160,192}, 2 slots, 8 waves, <= 80 KB of LDS and <= 128 VGPRs so
-//     that TWO workgroups share a CU and overlap each other's prologue / barrier / epilogue phases; 64 x BC on 4 waves for
-//     the 16x16 / 8x8 levels (split-K); the deeper rings / 256-pixel / 16-wave instantiations are kept behind environment
-//     knobs for A/B runs (profiles/r1_igemm_ablation.txt);
+//   * template <TI, TO, BP, BC>: BP x BC output tile, BC in {128, 160, 192}, on a two-slot LDS ring.  Two variants: 128
+//     pixels on 8 waves (4 pixel-waves x 2 channel-waves), <= 80 KB of LDS and <= 128 VGPRs so that TWO workgroups share a
+//     CU and overlap each other's prologue / barrier / epilogue phases; 64 pixels on 4 waves for the small-M launches of
+//     the 16x16 / 8x8 levels (split-K).  rs_igemm2_pick chooses between them;
 //   * raw `s_barrier` + counted `s_waitcnt vmcnt` (never __syncthreads() in the K loop: its fence would drain the DMA
-//     prefetch), one barrier per K stage; stages 0 and 1 are issued together in the prologue;
+//     prefetch), one barrier per K stage; stages 0 and 1 are issued together in the prologue (both slots are empty then);
 //   * epilogue: bias / residual fetched up front, activation chosen at compile time behind one uniform branch, fragments
 //     finished one at a time (register budget), fp16 results transposed through LDS into 16-byte NHWC stores.
 #include "igemm_common.h"
@@ -23,13 +22,6 @@ namespace {
 
 using namespace igemm_detail;
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-// s_setprio(1) around the MFMA clusters measured neutral here (4 waves/SIMD already interleave); kept as a build-time knob
-#ifndef RS_SETPRIO
-#define RS_SETPRIO 0
-#endif
 // One K stage of MFMAs with precomputed per-lane LDS base pointers: fragment i sits at base + i*2048 (16 rows x 128 B),
 // so every ds_read_b128 uses an immediate offset and the stage costs no address arithmetic beyond the 4 bases.
 template <typename T, int FC, int FP> struct Stage2;
@@ -48,12 +40,10 @@ template <int FC, int FP> struct Stage2<f16, FC, FP> {
             for (int i = 0; i < FC; ++i) a[i] = *(const f16x8*)(pa + i * 2048);
 #pragma unroll
             for (int j = 0; j < FP; ++j) b[j] = *(const f16x8*)(pb + j * 2048);
-            if (RS_SETPRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int i = 0; i < FC; ++i)
 #pragma unroll
                 for (int j = 0; j < FP; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i], b[j], acc[i][j], 0, 0, 0);
-            if (RS_SETPRIO) __builtin_amdgcn_s_setprio(0);
         }
     }
 };
@@ -78,42 +68,33 @@ template <int FC, int FP> struct Stage2<float, FC, FP> {
     }
 };
 
-// NB: keep the LDS-DMA builtin inside a plain __device__ function: called directly from the kernel template hipcc 7.2
-// silently drops the template's HOST stubs (undefined __device_stub__ symbols at load time).
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds, 16, voff, 0, 0, 0);
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 #ifdef RS_SPLIT_ABLATE
 __device__ long long g_ig2_clk[4 * 8192];   // per workgroup: cycle counter at kernel start / K loop start / K loop end / kernel end (ablate builds)
 #define RS_IG2_STAMP(k) if (threadIdx.x == 0 && blockIdx.x < 8192 && blockIdx.z == 0) g_ig2_clk[4 * blockIdx.x + (k)] = clock64()
 #else
 #define RS_IG2_STAMP(k)
 #endif
-template <typename TI, typename TO, int BP, int BC, int NS, int NWV>
-// second launch bound = waves per SIMD the register allocation must allow: the 2-stage 128-pixel variant lives on TWO
-// co-resident workgroups per CU (4 waves per SIMD, <= 128 VGPRs); one spilled-over register halves its occupancy
-__global__ __launch_bounds__(64 * NWV, ((NS == 2 && BP == 128 && NWV == 8) || NWV == 16) ? 4 : 2) void igemm2_kernel(IGemmParams p) {
+template <typename TI, typename TO, int BP, int BC>
+// 4 * BP threads: one wave per 16 pixels of the tile.  Second launch bound = waves per SIMD the register allocation must allow: the
+// 128-pixel variant lives on TWO co-resident workgroups per CU (4 waves per SIMD, <= 128 VGPRs); one spilled-over register halves its
+// occupancy
+__global__ __launch_bounds__(4 * BP, BP == 128 ? 4 : 2) void igemm2_kernel(IGemmParams p) {
     RS_IG2_STAMP(0);
+    constexpr int NWV = BP / 16;               // waves: 128 pixels on 8, 64 pixels on 4
     constexpr int WPN = NWV / 2;               // pixel-waves (x 2 channel-waves)
     constexpr int RND = 8 * NWV;               // rows covered by one LDS-DMA instruction of every wave
     constexpr int CH = MfmaOps<TI>::CH;
     constexpr int BK = 8 * CH;                 // elements of K per stage (128 bytes per row)
-    // Weight rows per stage: the 2-stage ring only ever waits with vmcnt(0), so its last load round may be partial (only the
-    // waves that own rows < BC issue it: no zero rows DMA'd for BC = 160); the deeper rings count loads per wave and keep
-    // whole rounds (rows beyond BC are fetched as hardware zeros).
-    constexpr bool EXACT = (NS == 2);
-    constexpr int BCP = EXACT ? BC : (BC + RND - 1) / RND * RND;
+    // Weight rows per stage: the last load round may be partial (only the waves that own rows < BC issue it: no zero rows
+    // DMA'd for BC = 160)
     constexpr int RWP = BC % RND;                     // rows of the partial round (a multiple of 8: one wave = 8 rows)
     static_assert(RWP % 8 == 0, "partial round must be whole waves");
     constexpr int RX = BP / RND, RW = (BC + RND - 1) / RND;   // load rounds (one LDS-DMA instruction per thread per round)
     constexpr int L = RX + RW;                 // LDS-DMA instructions per thread per stage
     constexpr int FP = BP / WPN / 16;          // wave tile = (BP/WPN) pixels x (BC/2) channels
     constexpr int FC = BC / 32;
-    constexpr int STAGE = (BP + BCP) * 128;
-    static_assert(BP % RND == 0 && (BP / WPN) % 16 == 0 && BC % 32 == 0 && (NS >= 2 && NS <= 4) && (NWV == 4 || NWV == 8 || NWV == 16), "tile");
+    constexpr int STAGE = (BP + BC) * 128;
+    static_assert(BP % RND == 0 && (BP / WPN) % 16 == 0 && BC % 32 == 0 && (BP == 64 || BP == 128), "tile");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -211,7 +192,7 @@ __global__ __launch_bounds__(64 * NWV, ((NS == 2 && BP == 128 && NWV == 8) || NW
         const unsigned kb = (unsigned)kk * SZ;
 #pragma unroll
         for (int i = 0; i < RW; ++i) {
-            if (EXACT && RWP && i == RW - 1 && wave >= RWP / 8) continue;   // wave-uniform: this wave's rows of the last round are >= BC
+            if (RWP && i == RW - 1 && wave >= RWP / 8) continue;   // wave-uniform: this wave's rows of the last round are >= BC
             lds_dma16(rw, sbase + (BP + RND * i) * 128, wk ? woff[i] + kb : INV);
         }
         kk += BK;
@@ -235,29 +216,23 @@ __global__ __launch_bounds__(64 * NWV, ((NS == 2 && BP == 128 && NWV == 8) || NW
 #pragma unroll
         for (int j = 0; j < FP; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // prologue: fill NS-1 ring slots - and, with only two slots, the second one as well: both are empty at this point, so
-    // stages 0 and 1 travel together and every workgroup saves one full load round trip (short-K launches have only 3)
+    // prologue: fill both ring slots - they are empty at this point, so stages 0 and 1 travel together and every workgroup
+    // saves one full load round trip (short-K launches have only 3)
     RS_IG2_STAMP(1);
     if (nk > 0) issue(0);
-    const bool pro2 = NS >= 3 || !(p.dbg & 64);   // (dbg 64: the 2-slot ring starts with one stage, for A/B timing)
+    const bool pro2 = !(p.dbg & 64);   // (dbg 64: the ring starts with one stage, for A/B timing)
     if (nk > 1 && pro2) issue(1);
-    if (NS >= 4 && nk > 2) issue(2);
     for (int kt = 0; kt < nk; ++kt) {
-        // stage kt has landed once at most the loads of the later stages already issued are still outstanding
-        if (NS == 2) {
-            if (kt == 0 && nk > 1 && pro2) {   // stage 1 was issued with stage 0; its loads (one fewer on the waves that skip the partial round) may fly on
-                if (EXACT && RWP && wave >= RWP / 8) wait_vmcnt<L - 1>(); else wait_vmcnt<L>();
-            } else {
-                wait_vmcnt<0>();
-            }
+        // stage kt has landed once at most the loads of the later stage already issued are still outstanding
+        if (kt == 0 && nk > 1 && pro2) {   // stage 1 was issued with stage 0; its loads (one fewer on the waves that skip the partial round) may fly on
+            if (RWP && wave >= RWP / 8) wait_vmcnt<L - 1>(); else wait_vmcnt<L>();
         } else {
-            const int later = min(NS - 2, nk - 1 - kt);   // stages issued after kt that may still be in flight
-            if (later >= 2) wait_vmcnt<2 * L>(); else if (later == 1) wait_vmcnt<L>(); else wait_vmcnt<0>();
+            wait_vmcnt<0>();
         }
         if (!(p.dbg & 4)) __builtin_amdgcn_s_barrier();
         // refill the slot every wave finished reading before this barrier
-        if (kt + NS - 1 < nk && !(NS == 2 && kt == 0 && pro2) && !(p.dbg & 1)) issue((kt + NS - 1) % NS);
-        const char* sb = smem + (kt % NS) * STAGE;
+        if (kt + 1 < nk && !(kt == 0 && pro2) && !(p.dbg & 1)) issue((kt + 1) & 1);
+        const char* sb = smem + (kt & 1) * STAGE;
         if (!(p.dbg & 2)) Stage2<TI, FC, FP>::run(sb + la + swz0, sb + la + swz1, sb + lb + swz0, sb + lb + swz1, acc);
     }
     RS_IG2_STAMP(2);
@@ -404,96 +379,51 @@ __global__ __launch_bounds__(64 * NWV, ((NS == 2 && BP == 128 && NWV == 8) || NW
     RS_IG2_STAMP(3);
 }
 
-template <typename TI, typename TO, int BP, int BC, int NS, int NWV = 8>
+template <typename TI, typename TO, int BP, int BC>
 hipError_t launch2_cfg(IGemmParams p, int nz, hipStream_t st) {
-    constexpr int RND = 8 * NWV;
-    constexpr int BCP = NS == 2 ? BC : (BC + RND - 1) / RND * RND;
     const int tiles = ((p.M + BP - 1) / BP) * ((p.Cout + BC - 1) / BC);
-    const size_t lds = (size_t)NS * (BP + BCP) * 128;
-    static_assert(NS * (BP + BCP) * 128 <= 160 * 1024, "LDS");
+    const size_t lds = (size_t)2 * (BP + BC) * 128;
+    static_assert(2 * (BP + BC) * 128 <= 160 * 1024, "LDS");
     static RsAttrFlags attr_flags;
     if (attr_flags.need()) {
-        (void)hipFuncSetAttribute((const void*)igemm2_kernel<TI, TO, BP, BC, NS, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)igemm2_kernel<TI, TO, BP, BC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     const size_t esz = sizeof(TI);
     const size_t xb = (size_t)p.B * p.Hs * p.Ws * p.ld0 * esz, wb = (size_t)p.Cout * p.Ktot * esz;
     if (xb >= 0xF0000000ull || wb >= 0xF0000000ull) return hipErrorInvalidValue;  // 32-bit buffer offsets
     p.x_bytes = (unsigned)xb;
     p.w_bytes = (unsigned)wb;
-    { static const int dbg = []() { const char* e = getenv("RS_IGEMM_DBG"); return e ? atoi(e) : 0; }(); p.dbg = dbg; }
+    { static const int dbg = (int)rs_env_int("RS_IGEMM_DBG", 0); p.dbg = dbg; }
     {
         const int howo = p.Ho * p.Wo;
         const bool pow2 = howo > 0 && (howo & (howo - 1)) == 0 && (p.Wo & (p.Wo - 1)) == 0;
         p.sh_howo = pow2 ? __builtin_ctz(howo) : -1;
         p.sh_wo = pow2 ? __builtin_ctz(p.Wo) : -1;
     }
-    hipLaunchKernelGGL((igemm2_kernel<TI, TO, BP, BC, NS, NWV>), dim3(tiles, 1, p.splitk > 1 ? p.splitk : nz), dim3(64 * NWV), lds, st, p);
+    hipLaunchKernelGGL((igemm2_kernel<TI, TO, BP, BC>), dim3(tiles, 1, p.splitk > 1 ? p.splitk : nz), dim3(4 * BP), lds, st, p);
     if (p.splitk > 1 && rs_splitk_reduce_launch(&p, sizeof(TO) == 2 ? RS_F16 : RS_F32, st) != 0) return hipErrorLaunchFailure;
     return hipGetLastError();
 }
 
+template <typename TI, typename TO, int BP>
+hipError_t launch2_bc(const IGemmParams& p, int BC, int nz, hipStream_t st) {
+    switch (BC) {
+        case 160: return launch2_cfg<TI, TO, BP, 160>(p, nz, st);
+        case 192: return launch2_cfg<TI, TO, BP, 192>(p, nz, st);
+        default: return launch2_cfg<TI, TO, BP, 128>(p, nz, st);
+    }
+}
+
+// 128-pixel tiles on 8 waves: two workgroups share a CU and overlap each other's prologue / barrier / epilogue.  64-pixel tiles on 4
+// waves (small-M launches, 16x16 / 8x8 UNet levels): twice the workgroups per split-K slice, i.e. half the fp32 partial-slab traffic for
+// the same number of workgroups
 template <typename TI, typename TO>
 hipError_t launch2_t(const IGemmParams& p, int BP, int BC, int nz, hipStream_t st) {
-    if (BP == 256) {
-        switch (BC) {
-            case 160: return launch2_cfg<TI, TO, 256, 160, 2>(p, nz, st);
-            case 192: return launch2_cfg<TI, TO, 256, 192, 2>(p, nz, st);
-            default: return launch2_cfg<TI, TO, 256, 128, 3>(p, nz, st);
-        }
-    }
-    if (BP == 132) {
-        // launches with fewer workgroups than CUs (16x16 / 8x8 UNet levels): latency-bound K loop -> deepest ring that fits
-        switch (BC) {
-            case 160: return launch2_cfg<TI, TO, 128, 160, 3>(p, nz, st);
-            case 192: return launch2_cfg<TI, TO, 128, 192, 3>(p, nz, st);
-            default: return launch2_cfg<TI, TO, 128, 128, 4>(p, nz, st);
-        }
-    }
-    if (BP == 131) {
-        // 16-wave variant: 256-pixel tile (25 % less L2->LDS traffic per FLOP than 128x128) with the same 32 x BC/2 wave tiles
-        switch (BC) {
-            case 160: return launch2_cfg<TI, TO, 256, 160, 2, 16>(p, nz, st);
-            case 192: return launch2_cfg<TI, TO, 256, 192, 2, 16>(p, nz, st);
-            default: return launch2_cfg<TI, TO, 256, 128, 2, 16>(p, nz, st);
-        }
-    }
-    if (BP == 130) {
-        // 4-wave variant: wave tile 64 x BC/2 (fewer LDS fragment reads per MFMA), two workgroups per CU
-        switch (BC) {
-            case 160: return launch2_cfg<TI, TO, 128, 160, 2, 4>(p, nz, st);
-            case 192: return launch2_cfg<TI, TO, 128, 192, 2, 4>(p, nz, st);
-            default: return launch2_cfg<TI, TO, 128, 128, 2, 4>(p, nz, st);
-        }
-    }
-    if (BP == 133) {
-        // small-M launches (16x16 / 8x8 UNet levels): 64-pixel tiles on 4 waves give twice the workgroups per split-K slice,
-        // i.e. half the fp32 partial-slab traffic for the same number of workgroups
-        switch (BC) {
-            case 160: return launch2_cfg<TI, TO, 64, 160, 2, 4>(p, nz, st);
-            case 192: return launch2_cfg<TI, TO, 64, 192, 2, 4>(p, nz, st);
-            default: return launch2_cfg<TI, TO, 64, 128, 2, 4>(p, nz, st);
-        }
-    }
-    if (BP == 129) {
-        // short-K GEMMs (K <= 4 stages: Swin qkv/proj/fc1, patch embeds): the launch is dominated by prologue + epilogue,
-        // so use the 2-stage ring (<= 80 KB of LDS) that lets TWO workgroups share a CU and overlap each other
-        switch (BC) {
-            case 160: return launch2_cfg<TI, TO, 128, 160, 2>(p, nz, st);
-            case 192: return launch2_cfg<TI, TO, 128, 192, 2>(p, nz, st);
-            default: return launch2_cfg<TI, TO, 128, 128, 2>(p, nz, st);
-        }
-    }
-    switch (BC) {
-        case 160: return launch2_cfg<TI, TO, 128, 160, 3>(p, nz, st);
-        case 192: return launch2_cfg<TI, TO, 128, 192, 3>(p, nz, st);
-        default: return launch2_cfg<TI, TO, 128, 128, 3>(p, nz, st);
-    }
+    return BP == 64 ? launch2_bc<TI, TO, 64>(p, BC, nz, st) : launch2_bc<TI, TO, 128>(p, BC, nz, st);
 }
 
 }  // namespace
 
-// Tile choice of the second-generation kernel; returns 0 when the launch should stay on igemm.hip (tiny Cout,
-// too few tiles to fill the chip -> split-K there).
 #ifdef RS_SPLIT_ABLATE
 // ablate builds: mean cycles of the three kernel phases over the first `nwg` workgroups of the last igemm2 launch
 extern "C" int rs_igemm2_phase_cycles(int nwg, double* out3) {
@@ -508,7 +438,9 @@ extern "C" int rs_igemm2_phase_cycles(int nwg, double* out3) {
 }
 #endif
 
-extern "C" int rs_igemm2_pick(int M, int Cout, int Kbytes, int nz, int* BP, int* BC) {
+// Tile choice of the second-generation kernel (*BP: pixels per tile, 64 or 128; *BC: channels per tile); returns 0 when the
+// launch should stay on igemm.hip (tiny Cout).
+extern "C" int rs_igemm2_pick(int M, int Cout, int nz, int* BP, int* BC) {
     if (Cout <= 64) return 0;
     auto waste = [&](int bc) { return ((Cout + bc - 1) / bc) * bc - Cout; };
     int best = 128, bw = waste(128);
@@ -516,26 +448,13 @@ extern "C" int rs_igemm2_pick(int M, int Cout, int Kbytes, int nz, int* BP, int*
     if (waste(192) < bw) { best = 192; bw = waste(192); }
     *BC = best;
     const long long tiles128 = (long long)((M + 127) / 128) * ((Cout + best - 1) / best) * nz;
-    (void)tiles128;
-    *BP = (tiles128 >= 512) ? 256 : 128;   // 256-pixel tiles once they still give >= 1 workgroup per CU
-    // measured (profiles/r1_igemm_microbench_*): the 128-pixel, 2-stage, two-workgroups-per-CU variant wins on every layer
-    // shape of the model; RS_IGEMM_SHORTK=<bytes> restricts it to short-K GEMMs (256-pixel tiles otherwise) for A/B runs
-    static const int shortk = []() { const char* e = getenv("RS_IGEMM_SHORTK"); return e ? atoi(e) : (1 << 30); }();
-    if (Kbytes <= shortk) *BP = 129;
-    static const int var4 = []() { const char* e = getenv("RS_IGEMM_4WAVE"); return e ? atoi(e) : 0; }();
-    static const int deep = []() { const char* e = getenv("RS_IGEMM_DEEP"); return e ? atoi(e) : 0; }();  // measured: no gain on the 8x8/16x16 levels (fixed launch cost dominates)
-    if (tiles128 <= deep) *BP = 132;
-    // measured (profiles/r1_igemm_microbench_v6_smallm.txt): -16 % on the 16x16 / 8x8 level launches of one pass
-    static const int smallm = []() { const char* e = getenv("RS_IGEMM_SMALLM"); return e ? atoi(e) : 8192; }();
-    static const int force64 = []() { const char* e = getenv("RS_IGEMM_FORCE64"); return e ? atoi(e) : 0; }();   // A/B knob
-    if ((M <= smallm && tiles128 < 512) || force64) *BP = 133;   // (batched GEMMs with many small batches keep the 128-pixel tile)
-    if (var4 == 1) *BP = 130;
-    if (var4 == 16 && tiles128 >= 1024) *BP = 131;   // marker for the 128-pixel / 2-stage / 2-workgroups-per-CU variant
+    // measured (profiles/r1_igemm_microbench_*): the 128-pixel tile wins on every layer shape of the model but the small-M launches of
+    // the 16x16 / 8x8 levels (profiles/r1_igemm_microbench_v6_smallm.txt: -16 % on those launches of one pass with 64-pixel tiles);
+    // batched GEMMs with many small batches keep the 128-pixel tile
+    static const int smallm = (int)rs_env_int("RS_IGEMM_SMALLM", 8192);
+    *BP = (M <= smallm && tiles128 < 512) ? 64 : 128;
     return 1;
 }
-
-// pixels per tile of the variant code rs_igemm2_pick returns in *BP (launch2_t)
-extern "C" int rs_igemm2_tile_px(int BP) { return BP == 133 ? 64 : (BP == 256 || BP == 131) ? 256 : 128; }
 
 extern "C" int rs_igemm2_launch(const IGemmParams* pp, int in_dt, int out_dt, int BP, int BC, int nz, hipStream_t st) {
     const IGemmParams& p = *pp;

@@ -19,15 +19,6 @@ namespace {
 
 using namespace igemm_detail;
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// NB: keep the LDS-DMA builtin inside a plain __device__ function (see igemm2.hip)
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds, 16, voff, 0, 0, 0);
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 template <typename TO, int BC>
 __global__ __launch_bounds__(512, 2) void igemm3_kernel(IGemmParams p) {
     typedef f16 TI;
@@ -334,7 +325,7 @@ hipError_t launch3_cfg(IGemmParams p, hipStream_t st) {
     const bool pow2 = howo > 0 && (howo & (howo - 1)) == 0 && (p.Wo & (p.Wo - 1)) == 0;
     p.sh_howo = pow2 ? __builtin_ctz(howo) : -1;
     p.sh_wo = pow2 ? __builtin_ctz(p.Wo) : -1;
-    { static const int dbg = []() { const char* e = getenv("RS_IGEMM_DBG"); return e ? atoi(e) : 0; }(); p.dbg = dbg; }   // timing ablations
+    { static const int dbg = (int)rs_env_int("RS_IGEMM_DBG", 0); p.dbg = dbg; }   // timing ablations
     hipLaunchKernelGGL((igemm3_kernel<TO, BC>), dim3(tiles), dim3(512), lds, st, p);
     return hipGetLastError();
 }
@@ -348,10 +339,10 @@ hipError_t launch3_cfg(IGemmParams p, hipStream_t st) {
 // the 64x64 UNet level (512 tiles = two full rounds against one round of co-resident 128-pixel workgroups), which
 // therefore stay on igemm2.  RS_IGEMM_V3=0 disables it; RS_IGEMM_V3_MINTILES / _MAXTILES / _MINK move the thresholds.
 extern "C" int rs_igemm3_pick(int M, int Cout, int Ktot, int in_dt, int nz, int splitk, int* BC) {
-    static const int on = []() { const char* e = getenv("RS_IGEMM_V3"); return e ? atoi(e) : 1; }();
-    static const int min_tiles = []() { const char* e = getenv("RS_IGEMM_V3_MINTILES"); return e ? atoi(e) : 224; }();
-    static const int max_tiles = []() { const char* e = getenv("RS_IGEMM_V3_MAXTILES"); return e ? atoi(e) : 320; }();
-    static const int min_k = []() { const char* e = getenv("RS_IGEMM_V3_MINK"); return e ? atoi(e) : 1024; }();
+    static const int on = (int)rs_env_int("RS_IGEMM_V3", 1);
+    static const int min_tiles = (int)rs_env_int("RS_IGEMM_V3_MINTILES", 224);
+    static const int max_tiles = (int)rs_env_int("RS_IGEMM_V3_MAXTILES", 320);
+    static const int min_k = (int)rs_env_int("RS_IGEMM_V3_MINK", 1024);
     if (!on || in_dt != RS_F16 || nz != 1 || splitk > 1) return 0;
     int bc = 0;
     if (Cout % 160 == 0) bc = 160;

@@ -121,16 +121,16 @@ extern "C" int rs_splitk_reduce_stats_launch(const IGemmParams* p, int out_dt, h
 // (1: fp16 only, 2: split only); RS_IGEMM_V4_SEG=0 keeps the small planes on the generic kernels (A/B runs).
 // Fills the plan (kernel, TW in BP, BC, SEG, splitk, stats_px) and returns 1, or returns 0: not a halo-kernel launch.  Called by rs_conv_plan only.
 extern "C" int rs_igemm4_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz, ConvPlan* pl) {
-    static const int on = []() { const char* e = getenv("RS_IGEMM_V4"); return e ? atoi(e) : 3; }();
+    static const int on = (int)rs_env_int("RS_IGEMM_V4", 3);
     // bit 0: fp16, bit 1: split storage, bit 2: the 16 x 16 planes as well.  Default 2 = the 8 x 8 planes in split storage - measured
     // (profiles/r3_small_planes.txt, us per launch at batch 32, generic kernel -> halo kernel): split 8 x 8, 640 -> 640: 96 -> 62, 1280 ->
     // 640: 179 -> 105; split 16 x 16, 320 -> 320: 56 -> 70; fp16 8 x 8: 33 -> 39; fp16 16 x 16: 37 -> 41 (fp16 slices are 11 stages short:
     // prologue, partial slab and reduce dominate and igemm2's 64-pixel tiles win; the 16 x 16 planes already give the generic split
     // kernel 256 tiles)
-    static const int seg_on = []() { const char* e = getenv("RS_IGEMM_V4_SEG"); return e ? atoi(e) : 2; }();
-    static const int min_tiles = []() { const char* e = getenv("RS_IGEMM_V4_MINTILES"); return e ? atoi(e) : 192; }();
-    static const int sk_target = []() { const char* e = getenv("RS_IGEMM_V4_SKTARGET"); return e ? atoi(e) : 256; }();
-    static const int sk_minst = []() { const char* e = getenv("RS_IGEMM_V4_SKMINSTAGES"); return e ? atoi(e) : 6; }();
+    static const int seg_on = (int)rs_env_int("RS_IGEMM_V4_SEG", 2);
+    static const int min_tiles = (int)rs_env_int("RS_IGEMM_V4_MINTILES", 192);
+    static const int sk_target = (int)rs_env_int("RS_IGEMM_V4_SKTARGET", 256);
+    static const int sk_minst = (int)rs_env_int("RS_IGEMM_V4_SKMINSTAGES", 6);
     const IGemmParams& p = *pp;
     if (in_dt != out_dt || nz != 1 || p.C1 != 0 || p.unscaled_w) return 0;
     if (!((in_dt == RS_F16 && (on & 1)) || (in_dt == RS_F16S && (on & 2)))) return 0;

@@ -45,17 +45,6 @@ namespace {
 
 using namespace igemm_detail;
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// NB: keep the LDS-DMA builtin inside a plain __device__ function (see igemm2.hip)
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds, 16, voff, 0, 0, 0);
-}
-
-__device__ __forceinline__ void lds_dma16s(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff, unsigned soff) {   // + a scalar byte offset
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds, 16, voff, soff, 0, 0);
-}
-
 // k-step 1 of a fragment address (chunk index ^ 4 = byte ^ 64), computed where it is used: as plain C++ the compiler hoists all
 // twelve variants out of the tap loop and the kernel spills
 __device__ __forceinline__ int xor64(int v) {
@@ -288,7 +277,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void igemm4_kernel(IGemmParams p) {
         if (wave + NWV * k >= XPIECES) return;                       // wave-uniform
         unsigned v = xv[k];
         if constexpr (!SPLIT) v = (c * 64 + 64 > Cin && kcp >= 4) ? INV : v;   // half chunk: its upper 32 channels do not exist
-        lds_dma16s(rx, smem + (c & 1) * XBUF + (wave + NWV * k) * 1024, v, (unsigned)(c * KC) * 2u);
+        lds_dma16(rx, smem + (c & 1) * XBUF + (wave + NWV * k) * 1024, v, (unsigned)(c * KC) * 2u);
     };
     auto issue_w_fast = [&](int s, int slot) __attribute__((always_inline)) {
         char* sbase = smem + WBASE + slot * WSLOT + (8 * wave) * 128;
@@ -298,7 +287,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void igemm4_kernel(IGemmParams p) {
 #pragma unroll
         for (int i = 0; i < RW; ++i) {
             if (RWP && i == RW - 1 && !wpart) continue;
-            lds_dma16s(rw, sbase + (RR * i) * 128, (halfc && kcp >= 4) ? INV : wv[i], so);
+            lds_dma16(rw, sbase + (RR * i) * 128, (halfc && kcp >= 4) ? INV : wv[i], so);
         }
     };
 
@@ -1031,7 +1020,7 @@ hipError_t launch4_cfg(IGemmParams p, hipStream_t st) {
     }
 #if defined(RS_SPLIT_ABLATE) && defined(RS_IGEMM4_MAIN_TU)
     if constexpr (!SPLIT && BC == 160 && SEG == 0 && NWV == 8) {
-        static const int abl = []() { const char* v = getenv("RS_IGEMM4_ABL"); return v ? atoi(v) : 0; }();
+        static const int abl = (int)rs_env_int("RS_IGEMM4_ABL", 0);
 #define RS_ABL4_CASE(A)                                                                                                              \
     if (abl == A) {                                                                                                                    \
         (void)hipFuncSetAttribute((const void*)igemm4_kernel<TW, BC, SPLIT, 0, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \

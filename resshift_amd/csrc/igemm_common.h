@@ -1,5 +1,5 @@
 // Device helpers shared by the implicit-GEMM kernels (igemm.hip: register-staged double buffer + split-K;
-// igemm2.hip: direct-to-LDS 3-stage ring).  See igemm.hip for the formulation.
+// igemm2.hip: direct-to-LDS two-slot ring).  See igemm.hip for the formulation.
 #pragma once
 #include "common.h"
 

@@ -24,15 +24,6 @@ namespace {
 
 using namespace igemm_detail;
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// NB: keep the LDS-DMA builtin inside a plain __device__ function (see igemm2.hip)
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds, 16, voff, 0, 0, 0);
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // ABL (builds with -DRS_SPLIT_ABLATE only): timing ablations of the K loop, results wrong: 1 = no refill loads after the
 // prologue, 2 = no ds_read / MFMA, 4 = no barrier (compile-time: runtime switches in the loop cost registers)
 #ifdef RS_SPLIT_ABLATE
@@ -41,7 +32,7 @@ __device__ long long g_igs_clk[4 * 8192];   // per workgroup: cycle counter at k
 #else
 #define RS_IGS_STAMP(k)
 #endif
-template <typename TO, int BP, int BC, int NWV, bool PIPE, int ABL = 0>
+template <typename TO, int BP, int BC, int NWV, int ABL = 0>
 __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 : 1) void igemm_split_kernel(IGemmParams p) {
     RS_IGS_STAMP(0);
     constexpr int WPN = NWV / 2;               // pixel-waves (x 2 channel-waves)
@@ -178,136 +169,95 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 : 1) void igemm_split_kernel
     RS_IGS_STAMP(1);
     if (nk > 0) issue(0);
     if (nk > 1) issue(1);
-    if constexpr (!PIPE) {
-        // reference schedule (round 2's A/B partner, not instantiated any more): the whole refill is issued right behind the barrier
-        for (int kt = 0; kt < nk; ++kt) {
-            if (kt == 0 && nk > 1) {   // stage 1 was issued with stage 0; its loads (two fewer on the waves that skip the partial round) may fly on
-                if (RWP && !wpart) wait_vmcnt<L - 2>(); else wait_vmcnt<L>();
-            } else {
-                wait_vmcnt<0>();
-            }
-            __builtin_amdgcn_s_barrier();
-            if (kt >= 1 && kt + 1 < nk) issue((kt + 1) & 1);   // refill the slot every wave finished reading before this barrier
-            const char* sb = smem + (kt & 1) * STAGE;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const int sw = ks ? swz1 : swz0;
-                f16x8 ah[FC], al[FC], bh[FP], bl[FP];
-#pragma unroll
-                for (int i = 0; i < FC; ++i) {
-                    ah[i] = *(const f16x8*)(sb + la + sw + i * 2048);
-                    al[i] = *(const f16x8*)(sb + PLANE + la + sw + i * 2048);
-                }
-#pragma unroll
-                for (int j = 0; j < FP; ++j) {
-                    bh[j] = *(const f16x8*)(sb + lb + sw + j * 2048);
-                    bl[j] = *(const f16x8*)(sb + PLANE + lb + sw + j * 2048);
-                }
-#pragma unroll
-                for (int i = 0; i < FC; ++i)
-#pragma unroll
-                    for (int j = 0; j < FP; ++j) am[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], am[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < FC; ++i)
-#pragma unroll
-                    for (int j = 0; j < FP; ++j) ac[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], ac[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < FC; ++i)
-#pragma unroll
-                    for (int j = 0; j < FP; ++j) ac[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], ac[i][j], 0, 0, 0);
-            }
+    // The K loop.  A stage is 2 * FC blocks of 3 * FP MFMAs (one channel fragment of one k-step each).  The L
+    // LDS-DMA instructions of the refill are NOT issued in one burst behind the barrier - every wave would sit in the
+    // texture-address queue for ~L KB / (52 B/clk) while the matrix pipe idles - but one or two per block, in front of
+    // that block's MFMAs, over the first DBLK blocks (the rest of the stage gives the last pieces time to land before
+    // the next barrier's vmcnt(0)).  The fragments of k-step 1 are read into a second register set while k-step 0
+    // computes.  sched_barrier(0) pins the block order; inside a block the compiler schedules freely.
+    constexpr int NBLK = 2 * FC;
+    constexpr int DBLK = NBLK - (NBLK >= 8 ? 3 : 1);            // blocks that carry DMA pieces
+    constexpr bool DBUF = (FC + FP) * 16 + FC * FP * 8 <= 200;  // second fragment set only where it fits 256 VGPRs
+    // piece d of the refill: d < 2 RX -> pixel rows (round d/2, half d&1), then weight rows
+    auto piece = [&](char* sbase, unsigned cb, unsigned kb, bool wk, int d) {
+        if (d < 2 * RX) {
+            const int i = d >> 1, half = d & 1;
+            lds_dma16(rx, sbase + half * PLANE + (RND * i) * 128, off[i] == INV ? INV : off[i] + cb + (half ? xlo : 0u));
+        } else {
+            const int e = d - 2 * RX, i = e >> 1, half = e & 1;
+            if (RWP && i == RW - 1 && !wpart) return;
+            const bool ok = wk && woff[i] != INV;
+            lds_dma16(rw, sbase + half * PLANE + (BP + RND * i) * 128, ok ? woff[i] + kb + (half ? wlo : 0u) : INV);
         }
-    } else {
-        // Pipelined schedule.  A stage is 2 * FC blocks of 3 * FP MFMAs (one channel fragment of one k-step each).  The L
-        // LDS-DMA instructions of the refill are NOT issued in one burst behind the barrier - every wave would sit in the
-        // texture-address queue for ~L KB / (52 B/clk) while the matrix pipe idles - but one or two per block, in front of
-        // that block's MFMAs, over the first DBLK blocks (the rest of the stage gives the last pieces time to land before
-        // the next barrier's vmcnt(0)).  The fragments of k-step 1 are read into a second register set while k-step 0
-        // computes.  sched_barrier(0) pins the block order; inside a block the compiler schedules freely.
-        constexpr int NBLK = 2 * FC;
-        constexpr int DBLK = NBLK - (NBLK >= 8 ? 3 : 1);            // blocks that carry DMA pieces
-        constexpr bool DBUF = (FC + FP) * 16 + FC * FP * 8 <= 200;  // second fragment set only where it fits 256 VGPRs
-        // piece d of the refill: d < 2 RX -> pixel rows (round d/2, half d&1), then weight rows
-        auto piece = [&](char* sbase, unsigned cb, unsigned kb, bool wk, int d) {
-            if (d < 2 * RX) {
-                const int i = d >> 1, half = d & 1;
-                lds_dma16(rx, sbase + half * PLANE + (RND * i) * 128, off[i] == INV ? INV : off[i] + cb + (half ? xlo : 0u));
-            } else {
-                const int e = d - 2 * RX, i = e >> 1, half = e & 1;
-                if (RWP && i == RW - 1 && !wpart) return;
-                const bool ok = wk && woff[i] != INV;
-                lds_dma16(rw, sbase + half * PLANE + (BP + RND * i) * 128, ok ? woff[i] + kb + (half ? wlo : 0u) : INV);
+    };
+    auto stage = [&](int kt, auto refill_tag, auto compute_tag) {
+        constexpr bool REFILL = decltype(refill_tag)::value;
+        constexpr bool COMPUTE = decltype(compute_tag)::value;   // false: timing ablation (RS_IGEMM_DBG & 2), results wrong
+        const char* sb = smem + (kt & 1) * STAGE;
+        char* sbase = smem + ((kt + 1) & 1) * STAGE + (8 * wave) * 128;
+        const unsigned cb = (unsigned)cc * 2u, kb = (unsigned)kk * 2u;
+        const bool wk = kk < p.Ktot;
+        f16x8 ah[2][FC], al[2][FC], bh[2][FP], bl[2][FP];
+        auto read_set = [&](int ks, int set) {
+            const int sw = ks ? swz1 : swz0;
+#pragma unroll
+            for (int j = 0; j < FP; ++j) {
+                bh[set][j] = *(const f16x8*)(sb + lb + sw + j * 2048);
+                bl[set][j] = *(const f16x8*)(sb + PLANE + lb + sw + j * 2048);
+            }
+#pragma unroll
+            for (int i = 0; i < FC; ++i) {
+                ah[set][i] = *(const f16x8*)(sb + la + sw + i * 2048);
+                al[set][i] = *(const f16x8*)(sb + PLANE + la + sw + i * 2048);
             }
         };
-        auto stage = [&](int kt, auto refill_tag, auto compute_tag) {
-            constexpr bool REFILL = decltype(refill_tag)::value;
-            constexpr bool COMPUTE = decltype(compute_tag)::value;   // false: timing ablation (RS_IGEMM_DBG & 2), results wrong
-            const char* sb = smem + (kt & 1) * STAGE;
-            char* sbase = smem + ((kt + 1) & 1) * STAGE + (8 * wave) * 128;
-            const unsigned cb = (unsigned)cc * 2u, kb = (unsigned)kk * 2u;
-            const bool wk = kk < p.Ktot;
-            f16x8 ah[2][FC], al[2][FC], bh[2][FP], bl[2][FP];
-            auto read_set = [&](int ks, int set) {
-                const int sw = ks ? swz1 : swz0;
+        if (COMPUTE) read_set(0, 0);
 #pragma unroll
-                for (int j = 0; j < FP; ++j) {
-                    bh[set][j] = *(const f16x8*)(sb + lb + sw + j * 2048);
-                    bl[set][j] = *(const f16x8*)(sb + PLANE + lb + sw + j * 2048);
-                }
+        for (int blk = 0; blk < NBLK; ++blk) {
+            const int ks = blk / FC, i = blk % FC;
+            const int set = DBUF ? ks : 0;
+            if (REFILL) {
 #pragma unroll
-                for (int i = 0; i < FC; ++i) {
-                    ah[set][i] = *(const f16x8*)(sb + la + sw + i * 2048);
-                    al[set][i] = *(const f16x8*)(sb + PLANE + la + sw + i * 2048);
-                }
-            };
-            if (COMPUTE) read_set(0, 0);
-#pragma unroll
-            for (int blk = 0; blk < NBLK; ++blk) {
-                const int ks = blk / FC, i = blk % FC;
-                const int set = DBUF ? ks : 0;
-                if (REFILL) {
-#pragma unroll
-                    for (int d = 0; d < L; ++d)
-                        if (d * DBLK / L == blk) piece(sbase, cb, kb, wk, d);
-                }
-                if (COMPUTE) {
-                    if (DBUF ? blk == 1 : blk == FC) read_set(1, DBUF ? 1 : 0);
-#pragma unroll
-                    for (int j = 0; j < FP; ++j) am[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[set][i], bh[set][j], am[i][j], 0, 0, 0);
-#pragma unroll
-                    for (int j = 0; j < FP; ++j) ac[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[set][i], bl[set][j], ac[i][j], 0, 0, 0);
-#pragma unroll
-                    for (int j = 0; j < FP; ++j) ac[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[set][i], bh[set][j], ac[i][j], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                for (int d = 0; d < L; ++d)
+                    if (d * DBLK / L == blk) piece(sbase, cb, kb, wk, d);
             }
-            if (REFILL) {   // step this lane's K cursor past the stage just requested
-                kk += BK;
-                cc += BK;
-                if (cc >= Ctot) {
-                    do {
-                        cc -= Ctot; ++tap;
-                        if (++kx == p.KW) { kx = 0; ++ky; }
-                    } while (cc >= Ctot);
-                    set_tap();
-                }
+            if (COMPUTE) {
+                if (DBUF ? blk == 1 : blk == FC) read_set(1, DBUF ? 1 : 0);
+#pragma unroll
+                for (int j = 0; j < FP; ++j) am[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[set][i], bh[set][j], am[i][j], 0, 0, 0);
+#pragma unroll
+                for (int j = 0; j < FP; ++j) ac[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[set][i], bl[set][j], ac[i][j], 0, 0, 0);
+#pragma unroll
+                for (int j = 0; j < FP; ++j) ac[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[set][i], bh[set][j], ac[i][j], 0, 0, 0);
             }
-        };
-        if (nk > 0) {
-            if (nk > 1) { if (RWP && !wpart) wait_vmcnt<L - 2>(); else wait_vmcnt<L>(); } else wait_vmcnt<0>();
-            __builtin_amdgcn_s_barrier();
-            stage(0, std::false_type{}, std::true_type{});
+            __builtin_amdgcn_sched_barrier(0);
         }
-        for (int kt = 1; kt + 1 < nk; ++kt) {
-            wait_vmcnt<0>();
-            if (!(ABL & 4)) __builtin_amdgcn_s_barrier();
-            stage(kt, std::integral_constant<bool, !(ABL & 1)>{}, std::integral_constant<bool, !(ABL & 2)>{});
+        if (REFILL) {   // step this lane's K cursor past the stage just requested
+            kk += BK;
+            cc += BK;
+            if (cc >= Ctot) {
+                do {
+                    cc -= Ctot; ++tap;
+                    if (++kx == p.KW) { kx = 0; ++ky; }
+                } while (cc >= Ctot);
+                set_tap();
+            }
         }
-        if (nk > 1) {
-            wait_vmcnt<0>();
-            __builtin_amdgcn_s_barrier();
-            stage(nk - 1, std::false_type{}, std::true_type{});
-        }
+    };
+    if (nk > 0) {
+        if (nk > 1) { if (RWP && !wpart) wait_vmcnt<L - 2>(); else wait_vmcnt<L>(); } else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        stage(0, std::false_type{}, std::true_type{});
+    }
+    for (int kt = 1; kt + 1 < nk; ++kt) {
+        wait_vmcnt<0>();
+        if (!(ABL & 4)) __builtin_amdgcn_s_barrier();
+        stage(kt, std::integral_constant<bool, !(ABL & 1)>{}, std::integral_constant<bool, !(ABL & 2)>{});
+    }
+    if (nk > 1) {
+        wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        stage(nk - 1, std::false_type{}, std::true_type{});
     }
     RS_IGS_STAMP(2);
     __syncthreads();  // all waves done with the ring: the epilogue reuses it as staging space
@@ -501,14 +451,14 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 : 1) void igemm_split_kernel
     RS_IGS_STAMP(3);
 }
 
-template <typename TO, int BP, int BC, int NWV, bool PIPE, int ABL = 0>
+template <typename TO, int BP, int BC, int NWV, int ABL = 0>
 hipError_t launch_cfg2(IGemmParams p, int nz, hipStream_t st) {
     const int tiles = ((p.M + BP - 1) / BP) * ((p.Cout + BC - 1) / BC);
     constexpr size_t lds = (size_t)2 * 2 * (BP + BC) * 128;
     static_assert(lds <= 160 * 1024, "LDS");
     static RsAttrFlags attr_flags;
     if (attr_flags.need()) {
-        (void)hipFuncSetAttribute((const void*)igemm_split_kernel<TO, BP, BC, NWV, PIPE, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)igemm_split_kernel<TO, BP, BC, NWV, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     const size_t xb = (size_t)p.B * p.Hs * p.Ws * p.ld0 * 4, wb = (size_t)p.Cout * p.Ktot * 4;
     if (xb >= 0xF0000000ull || wb >= 0xF0000000ull) return hipErrorInvalidValue;  // 32-bit buffer offsets
@@ -538,7 +488,7 @@ hipError_t launch_cfg2(IGemmParams p, int nz, hipStream_t st) {
             }
         }
     }
-    hipLaunchKernelGGL((igemm_split_kernel<TO, BP, BC, NWV, PIPE, ABL>), dim3(tiles, 1, p.splitk > 1 ? p.splitk : nz), dim3(64 * NWV), lds, st, p);
+    hipLaunchKernelGGL((igemm_split_kernel<TO, BP, BC, NWV, ABL>), dim3(tiles, 1, p.splitk > 1 ? p.splitk : nz), dim3(64 * NWV), lds, st, p);
     if (p.splitk > 1) {
         p.ystats = want_stats; p.tail = want_tail;
         const int out_dt = std::is_same<TO, h2s>::value ? RS_F16S : RS_F32;
@@ -551,17 +501,17 @@ template <typename TO, int BP, int BC, int NWV>
 hipError_t launch_cfg(const IGemmParams& p, int nz, hipStream_t st) {
 #ifdef RS_SPLIT_ABLATE
     if constexpr (std::is_same<TO, h2s>::value && NWV == 8) {
-        static const int abl = []() { const char* e = getenv("RS_IGEMM_DBG"); return e ? atoi(e) : 0; }();
+        static const int abl = (int)rs_env_int("RS_IGEMM_DBG", 0);
         switch (abl) {
-            case 1: return launch_cfg2<TO, BP, BC, NWV, true, 1>(p, nz, st);
-            case 2: return launch_cfg2<TO, BP, BC, NWV, true, 2>(p, nz, st);
-            case 4: return launch_cfg2<TO, BP, BC, NWV, true, 4>(p, nz, st);
-            case 6: return launch_cfg2<TO, BP, BC, NWV, true, 6>(p, nz, st);
+            case 1: return launch_cfg2<TO, BP, BC, NWV, 1>(p, nz, st);
+            case 2: return launch_cfg2<TO, BP, BC, NWV, 2>(p, nz, st);
+            case 4: return launch_cfg2<TO, BP, BC, NWV, 4>(p, nz, st);
+            case 6: return launch_cfg2<TO, BP, BC, NWV, 6>(p, nz, st);
             default: break;
         }
     }
 #endif
-    return launch_cfg2<TO, BP, BC, NWV, true>(p, nz, st);   // (the un-pipelined reference schedule, PIPE = false, is no longer instantiated)
+    return launch_cfg2<TO, BP, BC, NWV>(p, nz, st);
 }
 
 template <typename TO>
@@ -599,7 +549,7 @@ static void split_pick(int M, int Cout, int nz, int* BP, int* BC) {
     // 128 tiles x 2 slices of 8 waves - two waves per SIMD on every CU, half the K loop per workgroup, + the reduce kernel - against 256
     // tiles of 4 waves, one wave per SIMD: 68 us for 18 us of MFMA work).  Measured in round 5 (profiles/r5_fold_ab.txt): igemm_split family
     // 51.9 -> 49.0 ms per parity pass, the pass - 2.1 ms, + 210 reduce launches.  RS_SPLIT_BP128_SK=0: the round-4 choice.
-    static const int bp128_min = []() { const char* e = getenv("RS_SPLIT_BP128_SK"); return e ? atoi(e) : 64; }();
+    static const int bp128_min = (int)rs_env_int("RS_SPLIT_BP128_SK", 64);
     if (bp128_min > 0 && nz == 1 && tiles128 >= bp128_min) *BP = 128;
 }
 

@@ -11,8 +11,7 @@ int rs_conv_plan(const IGemmParams* p, int in_dt, int out_dt, int nz, ConvPlan* 
 int rs_conv_launch(const IGemmParams* p, int in_dt, int out_dt, int nz, const ConvPlan* plan, hipStream_t st);
 int rs_splitk_reduce_launch(const IGemmParams* p, int out_dt, hipStream_t st);         // igemm.hip
 int rs_splitk_reduce_stats_launch(const IGemmParams* p, int out_dt, hipStream_t st);   // igemm4.hip: reduce + statistics (+ GroupNorm tail)
-int rs_igemm2_pick(int M, int Cout, int Kbytes, int nz, int* BP, int* BC);
-int rs_igemm2_tile_px(int BP);
+int rs_igemm2_pick(int M, int Cout, int nz, int* BP, int* BC);   // *BP: 64 or 128 pixels per tile
 int rs_igemm2_launch(const IGemmParams* pp, int in_dt, int out_dt, int BP, int BC, int nz, hipStream_t st);
 int rs_igemm3_pick(int M, int Cout, int Ktot, int in_dt, int nz, int splitk, int* BC);
 int rs_igemm3_launch(const IGemmParams* pp, int out_dt, int BC, hipStream_t st);

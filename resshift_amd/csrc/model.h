@@ -9,10 +9,8 @@
 #include <unordered_map>
 #include <vector>
 
-// The RS_* environment knobs: a call site keeps the value in a function-local static (read once per process, at first use; nothing sets an
-// RS_ knob after the first engine call), a knob that two places need has ONE accessor below.
-static inline bool rs_env_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }   // on unless the value starts with 0
-static inline long long rs_env_int(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
+// The RS_* environment knobs (rs_env_on / rs_env_int / rs_env_set, common.h): a call site keeps the value in a function-local static (read
+// once per process, at first use; nothing sets an RS_ knob after the first engine call), a knob that two places need has ONE accessor below.
 static inline bool rs_knob_gn_epi_stats() { static const bool on = rs_env_on("RS_GN_EPI_STATS"); return on; }
 static inline bool rs_knob_gn_gen_stats() { static const bool on = rs_env_on("RS_GN_GEN_STATS"); return on; }
 static inline bool rs_knob_gn_conv_fold() { static const bool on = rs_env_on("RS_GN_CONV_FOLD"); return on; }

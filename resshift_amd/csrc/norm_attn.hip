@@ -197,32 +197,33 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GNParams p) {
 }
 
 // Fused GroupNorm for small planes (HW <= 256: the 16x16 / 8x8 UNet levels): grid (C / SC, B), one workgroup owns a slice of
-// SC channels (whole groups, a multiple of 8 channels) of ONE image, keeps it in registers (<= MAXI 16-byte items per
+// SC channels (whole groups, a multiple of 8 channels) of ONE image, keeps it in registers (<= GN_FUSED_MAXI 16-byte items per
 // thread), derives the group statistics through LDS and writes the normalised result - one launch and one read of x
 // instead of stats + apply.  Thread (pp, j) owns chunk j of the slice for pixels pp, pp+PP, ...
-template <typename T, int ACT, int MAXI, int NT>
+constexpr int GN_FUSED_MAXI = 12, GN_FUSED_NT = 256;   // items per thread, threads per workgroup
+template <typename T, int ACT>
 __device__ __forceinline__ void gn_fused_body(const GNParams& p, int SC, float (*red)[17], float* ca, float* cb) {
     constexpr bool FAST = Store<T>::FAST;
     const long long rx = (long long)p.ldx * Store<T>::PM, ry = (long long)p.ldy * Store<T>::PM;
     const int tid = threadIdx.x, b = blockIdx.y;
     const int cpg = p.C / p.groups;
-    const int nch = SC >> 3, PP = NT / nch;
+    const int nch = SC >> 3, PP = GN_FUSED_NT / nch;
     const int j = tid % nch, pp = tid / nch;
     const int cs = blockIdx.x * SC;               // first channel of the slice
     const bool active = pp < PP;
     const T* x = (const T*)p.x + ((long long)b * p.HW) * rx + cs + j * 8;
     T* y = (T*)p.y + ((long long)b * p.HW) * ry + cs + j * 8;
-    Vec8<T> v[MAXI];
+    Vec8<T> v[GN_FUSED_MAXI];
     float sum[8], sq[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { sum[e] = 0.f; sq[e] = 0.f; }
 #pragma unroll
-    for (int k = 0; k < MAXI; ++k) {
+    for (int k = 0; k < GN_FUSED_MAXI; ++k) {
         const int pix = pp + k * PP;
         if (active && pix < p.HW) v[k].load(x + (long long)pix * rx, p.ldx);
     }
 #pragma unroll
-    for (int k = 0; k < MAXI; ++k) {
+    for (int k = 0; k < GN_FUSED_MAXI; ++k) {
         const int pix = pp + k * PP;
         if (active && pix < p.HW) {
 #pragma unroll
@@ -263,7 +264,7 @@ __device__ __forceinline__ void gn_fused_body(const GNParams& p, int SC, float (
     }
     __syncthreads();
     if (p.coef) {   // coefficient-only mode
-        for (int c = tid; c < SC; c += NT) { p.coef[((long long)b * 2) * p.C + cs + c] = ca[c]; p.coef[((long long)b * 2 + 1) * p.C + cs + c] = cb[c]; }
+        for (int c = tid; c < SC; c += GN_FUSED_NT) { p.coef[((long long)b * 2) * p.C + cs + c] = ca[c]; p.coef[((long long)b * 2 + 1) * p.C + cs + c] = cb[c]; }
         return;
     }
     if (!active) return;
@@ -271,7 +272,7 @@ __device__ __forceinline__ void gn_fused_body(const GNParams& p, int SC, float (
 #pragma unroll
     for (int e = 0; e < 8; ++e) { a[e] = ca[j * 8 + e]; c[e] = cb[j * 8 + e]; }
 #pragma unroll
-    for (int k = 0; k < MAXI; ++k) {
+    for (int k = 0; k < GN_FUSED_MAXI; ++k) {
         const int pix = pp + k * PP;
         if (pix < p.HW) {
             Vec8<T> o;
@@ -282,18 +283,18 @@ __device__ __forceinline__ void gn_fused_body(const GNParams& p, int SC, float (
     }
 }
 
-template <typename T, int MAXI, int NT>
-__global__ __launch_bounds__(NT) void gn_fused_kernel(GNParams p, int SC) {
-    __shared__ float red[NT][17];
+template <typename T>
+__global__ __launch_bounds__(GN_FUSED_NT) void gn_fused_kernel(GNParams p, int SC) {
+    __shared__ float red[GN_FUSED_NT][17];
     __shared__ float ca[256], cb[512];
-    if (p.act == RS_ACT_SILU) gn_fused_body<T, RS_ACT_SILU, MAXI, NT>(p, SC, red, ca, cb);
-    else if (p.act == RS_ACT_GELU) gn_fused_body<T, RS_ACT_GELU, MAXI, NT>(p, SC, red, ca, cb);
-    else gn_fused_body<T, RS_ACT_NONE, MAXI, NT>(p, SC, red, ca, cb);
+    if (p.act == RS_ACT_SILU) gn_fused_body<T, RS_ACT_SILU>(p, SC, red, ca, cb);
+    else if (p.act == RS_ACT_GELU) gn_fused_body<T, RS_ACT_GELU>(p, SC, red, ca, cb);
+    else gn_fused_body<T, RS_ACT_NONE>(p, SC, red, ca, cb);
 }
 
 // slice width for the fused kernel: whole groups, a multiple of 8 channels, >= 40 channels where possible (80-byte runs per
-// pixel), and narrow enough that the plane fits MAXI items per thread; 0 when no such width exists (two-kernel path)
-template <int MAXI, int NT> int gn_fused_slice(const GNParams& p) {
+// pixel), and narrow enough that the plane fits GN_FUSED_MAXI items per thread; 0 when no such width exists (two-kernel path)
+int gn_fused_slice(const GNParams& p) {
     const int cpg = p.C / p.groups;
     int g = 1;
     while ((g * cpg) % 8) ++g;                       // g in {1,2,4,8}
@@ -301,8 +302,8 @@ template <int MAXI, int NT> int gn_fused_slice(const GNParams& p) {
     int best = 0;
     for (int SC = g * cpg; SC <= 256 && SC <= p.C; SC *= 2) {
         if (p.C % SC) break;
-        const int PP = NT / (SC / 8);
-        if (PP < 1 || (p.HW + PP - 1) / PP > MAXI) break;
+        const int PP = GN_FUSED_NT / (SC / 8);
+        if (PP < 1 || (p.HW + PP - 1) / PP > GN_FUSED_MAXI) break;
         best = SC;
         if (SC >= 40) break;
     }
@@ -319,33 +320,21 @@ extern "C" int rs_groupnorm_launch(const GNParams* pp, int dt, int apply_slabs, 
     if ((p.C % 8) || (p.C % p.groups) || p.C / 8 > 256 || p.groups > 256 || (p.ldx % 8) || (p.ldy % 8)) return -2;
     GNTail tail{};
     // small planes: one fused launch (RS_GN_FUSED=0 keeps the two-kernel path for A/B runs)
-    static const bool fused_on = []() { const char* e = getenv("RS_GN_FUSED"); return !(e && e[0] == '0'); }();
-    // measured at B=32 (8-step bench, ms/step): fused up to 256 px 174.1, up to 1024 px 174.1, up to 4096 px 176.8 (too few,
-    // too fat workgroups at 64x64) -> the 1024-thread variant stays off by default
-    static const int fused_max = []() { const char* e = getenv("RS_GN_FUSED_MAXHW"); return e ? atoi(e) : 256; }();
+    static const bool fused_on = rs_env_on("RS_GN_FUSED");
     if (fused_on && p.HW <= 256 && !p.cpartial) {
-        constexpr int MAXI = 12;
-        const int SC = gn_fused_slice<MAXI, 256>(p);
+        const int SC = gn_fused_slice(p);
         if (SC > 0) {
             dim3 g(p.C / SC, p.B);
-            if (dt == RS_F16) hipLaunchKernelGGL((gn_fused_kernel<f16, MAXI, 256>), g, dim3(256), 0, st, p, SC);
-            else if (dt == RS_F16S) hipLaunchKernelGGL((gn_fused_kernel<h2s, MAXI, 256>), g, dim3(256), 0, st, p, SC);
-            else hipLaunchKernelGGL((gn_fused_kernel<float, MAXI, 256>), g, dim3(256), 0, st, p, SC);
-            return hipGetLastError() == hipSuccess ? 1 : -1;
-        }
-    } else if (fused_on && dt == RS_F16 && p.HW <= fused_max && !p.cpartial) {
-        // 32x32 / 64x64 planes in fp16: 1024 threads hold up to 20 items (80 VGPRs) each; the tensor is read once instead of twice
-        constexpr int MAXI = 20;
-        const int SC = gn_fused_slice<MAXI, 1024>(p);
-        if (SC > 0) {
-            hipLaunchKernelGGL((gn_fused_kernel<f16, MAXI, 1024>), dim3(p.C / SC, p.B), dim3(1024), 0, st, p, SC);
+            if (dt == RS_F16) hipLaunchKernelGGL((gn_fused_kernel<f16>), g, dim3(GN_FUSED_NT), 0, st, p, SC);
+            else if (dt == RS_F16S) hipLaunchKernelGGL((gn_fused_kernel<h2s>), g, dim3(GN_FUSED_NT), 0, st, p, SC);
+            else hipLaunchKernelGGL((gn_fused_kernel<float>), g, dim3(GN_FUSED_NT), 0, st, p, SC);
             return hipGetLastError() == hipSuccess ? 1 : -1;
         }
     }
     dim3 g1(p.S, p.B), g2(p.coef ? 1 : apply_slabs, p.B);
     const size_t lds = (2 * p.C + 2 * p.groups + 2 * 256) * sizeof(float);
     const bool need_stats = p.cpartial == nullptr;   // (else the producing conv's epilogue already left per-channel partial sums)
-    static const bool tail_on = []() { const char* e = getenv("RS_GN_TAIL"); return !(e && e[0] == '0'); }();
+    static const bool tail_on = rs_env_on("RS_GN_TAIL");
     // (the tail's finish works in gn_stats_kernel's red[256][17] array: 2 C + 2 groups floats below the flag word at red[255][16], a slice
     // tree of 256 / groups lanes per group - ADVICE r4: enforce what the engine's groups = 32 satisfies by construction)
     const bool use_tail = tail_on && need_stats && p.coef && p.ticket && 2 * p.C + 2 * p.groups <= 4351 && p.groups > 0 && (256 % p.groups) == 0;
@@ -754,15 +743,6 @@ __global__ __launch_bounds__(512) void win_attn_split_kernel(WinAttnParams p) {
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr3_t;
-__device__ __forceinline__ void lds_dma16_na(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr3_t)lds, 16, voff, 0, 0, 0);
-}
-// per-lane byte offset + wave-uniform byte offset (the instruction's scalar offset operand: no VGPR arithmetic for the uniform part)
-__device__ __forceinline__ void lds_dma16_vs(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr3_t)lds, 16, voff, (int)soff, 0, 0);
-}
-
 // Window attention with the qkv projection fused in (fp16 storage, E = 32 * heads <= 192, heads = 6 in every shipped config):
 // one workgroup per window, one wave per head.  The window's 64 normalised tokens are gathered (roll + partition folded
 // into the addressing) into LDS once; wave h multiplies them with ITS 96 rows of the qkv weight (q_h, k_h, v_h: no other
@@ -808,7 +788,7 @@ __global__ __launch_bounds__(384) void win_attn_qkv_kernel(WinAttnParams p, unsi
     // of the token requests; the gather loop of dependent loads it replaces stood in front of them, see win_attn_split.hip)
     {
         const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias_c, 0, 6 * 1024, 0x00020000);
-        lds_dma16_vs(rb, (char*)btab + h * 1024, (unsigned)(h * 1024 + lane * 16), 0u);
+        lds_dma16(rb, (char*)btab + h * 1024, (unsigned)(h * 1024 + lane * 16), 0u);
     }
     auto win_y = [&](int w) { return (int)(blockIdx.x * NW + w) / nwx; };
     auto pixel = [&](int w, int t) -> long long {
@@ -829,7 +809,7 @@ __global__ __launch_bounds__(384) void win_attn_qkv_kernel(WinAttnParams p, unsi
         for (int q = 0; q < 4; ++q) {
             const int it = h * 4 + q, st = it >> 3, grp = it & 7;
             int sy = wy * WS + grp + p.shift; if (sy >= p.H) sy -= p.H;
-            lds_dma16_vs(r, dst + st * XS_STAGE + (grp * 8) * 128, voff, (unsigned)(((b * p.H + sy) * p.W) * ld + st * 64) * 2u);
+            lds_dma16(r, dst + st * XS_STAGE + (grp * 8) * 128, voff, (unsigned)(((b * p.H + sy) * p.W) * ld + st * 64) * 2u);
         }
     };
     {
@@ -1131,7 +1111,7 @@ extern "C" int rs_win_attn_qkv_launch(const WinAttnParams* pp, hipStream_t st) {
     const size_t xb = (size_t)p.B * p.H * p.W * p.ldx * 2;
     if (xb >= 0xF0000000ull) return -2;
     // two windows per workgroup wherever an image has an even number of them (RS_ATTN_NW=1: one, for A/B runs)
-    static const int nw_max = []() { const char* v = getenv("RS_ATTN_NW"); return v ? atoi(v) : 2; }();
+    static const int nw_max = (int)rs_env_int("RS_ATTN_NW", 2);
     const int nwin = (p.H / 8) * (p.W / 8);
     const int NW = (nw_max >= 2 && nwin % 2 == 0) ? 2 : 1;
     const size_t rb = p.res ? (size_t)p.B * p.H * p.W * p.ldres * 2 : 0;
@@ -1140,7 +1120,7 @@ extern "C" int rs_win_attn_qkv_launch(const WinAttnParams* pp, hipStream_t st) {
     const size_t lds = (size_t)NW * (3 * 64 * 128 + (size_t)p.heads * 32 * (64 + 8) * sizeof(f16)) + 6144 + (p.wproj ? (size_t)NW * 3 * 64 * 128 : 0);
 #ifdef RS_SPLIT_ABLATE
     {
-        static const int abl = []() { const char* v = getenv("RS_ATTN_ABL"); const int a = v ? atoi(v) : 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_abl), &a, sizeof(int)); return a; }();
+        static const int abl = []() { const int a = (int)rs_env_int("RS_ATTN_ABL", 0); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_abl), &a, sizeof(int)); return a; }();
         (void)abl;
     }
 #endif
@@ -1172,7 +1152,7 @@ extern "C" int rs_win_attn_launch(const WinAttnParams* pp, int dt, hipStream_t s
         (void)hipFuncSetAttribute((const void*)win_attn_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         hipLaunchKernelGGL((win_attn_kernel<f16>), grid, block, lds, st, p);
     } else if (dt == RS_F16S) {
-        static const bool valu = []() { const char* e = getenv("RS_ATTN_SPLIT_VALU"); return e && e[0] == '1'; }();   // A/B knob: fp32 VALU kernel
+        static const bool valu = rs_env_int("RS_ATTN_SPLIT_VALU", 0) == 1;   // A/B knob: fp32 VALU kernel
         if (p.bias_n && !valu) {
             const size_t lds_m = (size_t)p.heads * 2 * 32 * (64 + 8) * sizeof(f16);   // 72 KB at 8 heads: over the 64 KB default
             (void)hipFuncSetAttribute((const void*)win_attn_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -162,8 +162,8 @@ int rs_op_conv3x3_wino(const void* x, const float* coef_dev, int act_in, const f
     float* stamps = nullptr;   // RS_WINO_STAMPS=1 with a -DRS_WINO_PHASES build: per-workgroup phase cycles of wave 0 (see wino.hip), averaged to stderr
     const int ntile = rs_wino_tiles(&p);
     p.dbg = 64;   // (an op-level entry: no fill-the-chip threshold)
-    if (const char* ab = getenv("RS_WINO_ABL")) p.dbg |= atoi(ab);   // (-DRS_WINO_PHASES builds: timing ablations, wino.hip)
-    if (getenv("RS_WINO_STAMPS")) { (void)hipMalloc((void**)&stamps, (size_t)ntile * 16 * sizeof(float)); (void)hipMemset(stamps, 0, (size_t)ntile * 16 * sizeof(float)); p.partial = stamps; }
+    p.dbg |= (int)rs_env_int("RS_WINO_ABL", 0);   // (-DRS_WINO_PHASES builds: timing ablations, wino.hip)
+    if (rs_env_set("RS_WINO_STAMPS")) { (void)hipMalloc((void**)&stamps, (size_t)ntile * 16 * sizeof(float)); (void)hipMemset(stamps, 0, (size_t)ntile * 16 * sizeof(float)); p.partial = stamps; }
     ConvPlan pl{};
     (void)rs_conv_plan(&p, RS_F16S, RS_F16S, 1, &pl);
     if (pl.kernel != CK_WINO) rc = rs_set_last_error("shape is not eligible for the wino kernel", -1);

@@ -20,8 +20,6 @@
 #include "launchers.h"
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <string>
 
 constexpr int RZ_TR = 16;
@@ -205,8 +203,7 @@ int rs_resize(const float* in, float* out, int B, int C, int H, int W, int Ho, i
     if (o0 < i1 && i0 < o1) return rs_set_last_error((who + "`out` overlaps `in` (workgroups read their neighbours' pixels of in: not in place)").c_str(), -2);
     const RzAxis ah = rz_axis(scale_h, H, Ho), aw = rz_axis(scale_w, W, Wo);
     if (ah.P > RZ_PMAX || aw.P > RZ_PMAX) return rs_set_last_error((who + "more than 34 taps per axis").c_str(), -2);
-    const char* e = getenv("RS_RESIZE_LDS");   // A/B knob of scripts/resize_bench.py, read per call
-    const int pad = !(e && !strcmp(e, "linear"));
+    const int pad = !rs_env_is("RS_RESIZE_LDS", "linear");   // A/B knob of scripts/resize_bench.py, read per call
     const int tiles_x = (Wo + RZ_TC - 1) / RZ_TC, tiles_y = (Ho + RZ_TR - 1) / RZ_TR;
     const long long total = planes * tiles_x * tiles_y;
     hipLaunchKernelGGL(resize_kernel, dim3((unsigned)std::min<long long>(total, 1 << 20)), dim3(RZ_THREADS), 0, (hipStream_t)stream, in, out, ah,

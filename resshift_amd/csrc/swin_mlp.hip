@@ -25,12 +25,6 @@ namespace {
 
 using namespace igemm_detail;
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds, 16, voff, 0, 0, 0);
-}
-
 // per-channel sum / sum of squares of a wave tile (32 tokens x 16 FC2 channels, lane (lr, lg) holds 4 channels of 2 tokens per channel
 // fragment) -> ystats[image][slab of 32 tokens][channel][2]; every token of the tile belongs to one image (HW % 32 == 0)
 template <int FC2>

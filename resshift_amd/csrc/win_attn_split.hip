@@ -21,11 +21,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr3_t;
-__device__ __forceinline__ void lds_dma16_ws(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr3_t)lds, 16, voff, 0, 0, 0);
-}
-
 #ifdef RS_SPLIT_ABLATE
 __device__ long long g_attns_clk[16 * 4096];   // phase stamps of wave 0 of the first 4096 workgroups
 #define RS_ATTN_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (tid == 0) { const int wg_ = blockIdx.y * gridDim.x + blockIdx.x; if (wg_ < 4096) g_attns_clk[16 * wg_ + (k)] = clock64(); } } while (0)
@@ -66,14 +61,14 @@ __global__ __launch_bounds__(384) void win_attn_qkv_split_kernel(WinAttnParams p
     // at the head of every window's 30 us.)
     {
         const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias_c, 0, 6 * 1024, 0x00020000);
-        lds_dma16_ws(rb, (char*)btab + h * 1024, (unsigned)(h * 1024 + lane * 16));
+        lds_dma16(rb, (char*)btab + h * 1024, (unsigned)(h * 1024 + lane * 16));
     }
     // norm1's coefficients of this image ([2][E] floats = 1536 B) the same way: the fold below reads them from LDS instead of waiting for four
     // dependent L2 round trips behind the barrier (waves 0 and 1, 1 KB each; the descriptor's bound zero-fills the last 512 B)
     float* const cf = (float*)((char*)btab + 6 * 1024 + 256);
     if (p.xcoef && h < 2) {
         const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.xcoef + (long long)b * 2 * E), 0, 2 * E * 4, 0x00020000);
-        lds_dma16_ws(rc, (char*)cf + h * 1024, (unsigned)(h * 1024 + lane * 16));
+        lds_dma16(rc, (char*)cf + h * 1024, (unsigned)(h * 1024 + lane * 16));
     }
     const int shift = p.shift, H = p.H, W = p.W;
     auto pixel = [&](int t) -> long long {
@@ -90,7 +85,7 @@ __global__ __launch_bounds__(384) void win_attn_qkv_split_kernel(WinAttnParams p
             const int it = h * 8 + q, plane = it / 24, r24 = it - plane * 24, st = r24 >> 3, grp = r24 & 7;
             // pixel record [ldx halfs hi | ldx halfs lo]
             const unsigned off = (unsigned)(pixel(grp * 8 + rsub) * p.ldx * 2 + plane * p.ldx + st * 64 + kcp * 8) * 2u;
-            lds_dma16_ws(rx, smem + plane * XS_PLANE + st * XS_STAGE + (grp * 8) * 128, off);
+            lds_dma16(rx, smem + plane * XS_PLANE + st * XS_STAGE + (grp * 8) * 128, off);
         }
     }
     // the hand-counted vmcnt(24) below assumes the bias table's and the 8 token DMAs are OLDER than the 24 q-weight loads: pin that order (ae_attn.hip does the same)
@@ -275,7 +270,7 @@ __global__ __launch_bounds__(384) void win_attn_qkv_split_kernel(WinAttnParams p
         for (int q = 0; q < 8; ++q) {
             const int it = h * 8 + q, plane = it / 24, r24 = it - plane * 24, st = r24 >> 3, grp = r24 & 7;
             const unsigned off = (unsigned)(pixel(grp * 8 + rsub) * p.ldres * 2 + plane * p.ldres + st * 64 + kcp * 8) * 2u;
-            lds_dma16_ws(rr, rt + plane * XS_PLANE + st * XS_STAGE + (grp * 8) * 128, off);
+            lds_dma16(rr, rt + plane * XS_PLANE + st * XS_STAGE + (grp * 8) * 128, off);
         }
     }
     f32x4 s[4][4];  // [fj][fi]

@@ -46,15 +46,6 @@ namespace {
 
 using namespace igemm_detail;
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// NB: keep the LDS-DMA builtin inside a plain __device__ function (see igemm2.hip)
-__device__ __forceinline__ void wdma16s(__amdgpu_buffer_rsrc_t r, char* lds, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds, 16, voff, soff, 0, 0);
-}
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 constexpr int W_TH = 8, W_TW = 16;          // output pixels of a workgroup: 4 x 8 Winograd tiles = two MFMA column fragments of 16 tiles
 constexpr int W_PITCH = 20;                 // halo row pitch in LDS rows (18 columns deinterleaved: evens at 0..8, odds at 10..18; 9 and 19 stay zero)
 constexpr int W_HROWS = (W_TH + 2) * W_PITCH;   // 200 LDS rows of 128 B
@@ -163,7 +154,7 @@ __global__ __launch_bounds__(512, 2) void wino_kernel(IGemmParams p) {
 #pragma unroll
         for (int k = 0; k < W_UPW; ++k)
 #pragma unroll
-            for (int h = 0; h < 2; ++h) wdma16s(rx, hb + (wave + 8 * k) * 2048 + h * 1024, live ? xv[k][h] : W_INV, (unsigned)(live ? chunk_of(c) : 0) * 64u);
+            for (int h = 0; h < 2; ++h) lds_dma16(rx, hb + (wave + 8 * k) * 2048 + h * 1024, live ? xv[k][h] : W_INV, (unsigned)(live ? chunk_of(c) : 0) * 64u);
     };
     // in-place conversion of this wave's units of chunk c: (hi, lo) pair -> GroupNorm affine (+FiLM) -> SiLU -> fp32.  Lane = (row, g'): the
     // 32 bytes [hi x 8 | lo x 8] of channel group g become [v0..3 | v4..7].  Rows outside the image stay exact zeros.
@@ -266,7 +257,7 @@ __global__ __launch_bounds__(512, 2) void wino_kernel(IGemmParams p) {
         // halo requests: it lands behind the same wait + barrier as chunk 0.  (The copy loop it replaces - load, wait, ds_write, up to three
         // dependent round trips - stood in front of the first halo request of every workgroup.)
         const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)(xcoef + (long long)b * 2 * Cin), 0, 2 * Cin * 4, 0x00020000);
-        wdma16s(rc, smem + W_COEF + wave * 1024, (unsigned)(wave * 1024 + lane * 16), 0u);
+        lds_dma16(rc, smem + W_COEF + wave * 1024, (unsigned)(wave * 1024 + lane * 16), 0u);
     }
     issue_halo(0, 0);
     issue_halo(1, 1);
@@ -276,7 +267,7 @@ __global__ __launch_bounds__(512, 2) void wino_kernel(IGemmParams p) {
     for (int s = 0; s < W_DEPTH; ++s) load_w(0, 0, 0, s, wh[s], wl[s]);
     __builtin_amdgcn_sched_barrier(0);
     // chunk 0 (and the coefficients in front of it) have landed: everything issued behind them - chunk 1's four pieces, the fragment loads - flies on
-    wait_vm<2 * W_UPW + 2 * W_DEPTH>();
+    wait_vmcnt<2 * W_UPW + 2 * W_DEPTH>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();   // the coefficients; chunk 0's LDS-DMA data behind a wait AND a barrier
     asm volatile("" ::: "memory");
@@ -286,7 +277,7 @@ __global__ __launch_bounds__(512, 2) void wino_kernel(IGemmParams p) {
     int buf = 0;               // halo buffer of chunk c
     for (int c = 0; c < nch; ++c) {
         // chunk c + 1 has landed (everything this wave issued except the fragment loads of the W_DEPTH steps ahead) ...
-        wait_vm<2 * W_DEPTH>();
+        wait_vmcnt<2 * W_DEPTH>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();   // ... and is behind a barrier: convertible.  Chunk c is fp32 for everybody; nobody reads chunk c - 1's buffer any more
         asm volatile("" ::: "memory");
@@ -547,8 +538,8 @@ extern "C" float rs_wino_pack(const float* w, int Cin, int Cout, void* dst_) {
 // (IGemmParams::ww), no output activation, no folded shortcut, enough tiles to fill the chip.  RS_WINO=0: off.  Fills the plan (no
 // split-K, one statistics slab per 8 x 16 pixel tile) and returns 1, or returns 0.
 extern "C" int rs_wino_plan(const IGemmParams* pp, int in_dt, int out_dt, int nz, ConvPlan* pl) {
-    static const int on = []() { const char* e = getenv("RS_WINO"); return e ? atoi(e) : 1; }();
-    static const int min_tiles = []() { const char* e = getenv("RS_WINO_MINTILES"); return e ? atoi(e) : 192; }();
+    static const int on = (int)rs_env_int("RS_WINO", 1);
+    static const int min_tiles = (int)rs_env_int("RS_WINO_MINTILES", 192);
     const IGemmParams& p = *pp;
     if (!on || in_dt != RS_F16S || out_dt != RS_F16S || nz != 1 || !p.ww || p.C1 != 0 || p.unscaled_w || p.sC || p.act != RS_ACT_NONE) return 0;
     if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad_t != 1 || p.pad_l != 1 || p.up != 1 || p.Ho != p.Hs || p.Wo != p.Ws || p.osc == 2) return 0;

@@ -82,19 +82,20 @@ def test_conv_igemm(gpu, dtype, case):
 
 
 BIG_CONV_CASES = [
-    # shapes large enough for the second-generation LDS-DMA kernel (igemm2.hip): B, H, W, Cin, Cout, k, up, act, res
-    (8, 64, 64, 160, 160, 3, 1, 0, True),     # 128-pixel tiles, BC=160, 3-stage ring
-    (16, 64, 64, 160, 160, 3, 1, 0, True),    # 256-pixel tiles, BC=160, 2-stage ring
-    (16, 64, 64, 192, 576, 1, 1, 0, False),   # qkv: BC=192, K = 192 (3 stages, ring tail handling)
-    (16, 64, 64, 192, 768, 1, 1, 1, False),   # fc1 + GELU
-    (16, 32, 32, 320, 320, 3, 2, 0, False),   # nearest-x2 upsample folded, 256-pixel tiles
-    (4, 128, 128, 128, 128, 3, 1, 0, True),   # AE level: BC=128, 3-stage ring, 256-pixel tiles
-    (9, 60, 52, 160, 320, 3, 1, 0, False),    # ragged M (not a multiple of the tile), two channel tiles
-    # third-generation kernel (igemm3.hip: 256-pixel tiles, 224..320 tiles, K >= 1024, Cout % 160 == 0 or % 128 == 0);
-    # (16,64,64,160,160) and (4,128,128,128,128) above are in its range as well
+    # shapes large enough for the LDS-DMA kernels: B, H, W, Cin, Cout, k, up, act, res.  Which kernel rs_conv_plan gives each case today -
+    # fp32 (batch cut to 8 on the 64 x 64 planes): always igemm2.hip's 128-pixel / 8-wave tile; fp16: as noted (halo = igemm4.hip)
+    (8, 64, 64, 160, 160, 3, 1, 0, True),     # fp16: igemm2, 128-pixel tiles, BC=160 (too few tiles for the halo kernel)
+    (16, 64, 64, 160, 160, 3, 1, 0, True),    # fp16: halo kernel, BC=160; fp32: igemm2, BC=160
+    (16, 64, 64, 192, 576, 1, 1, 0, False),   # qkv: igemm2, BC=192, K = 192 (3 stages on the two-slot ring: one refill)
+    (16, 64, 64, 192, 768, 1, 1, 1, False),   # fc1 + GELU: igemm2, BC=128
+    (16, 32, 32, 320, 320, 3, 2, 0, False),   # nearest-x2 upsample folded: igemm2, BC=160
+    (4, 128, 128, 128, 128, 3, 1, 0, True),   # AE level, fp16: halo kernel, BC=128; fp32: igemm2, BC=128
+    (9, 60, 52, 160, 320, 3, 1, 0, False),    # ragged M (not a multiple of the tile), two channel tiles: igemm2, BC=160
+    # fp16: third-generation kernel (igemm3.hip: 256-pixel tiles, 224..320 tiles, K >= 1024, Cout % 160 == 0 or % 128 == 0)
     (10, 60, 52, 160, 320, 3, 1, 0, True),    # ragged M, non-power-of-two planes (division path), residual, BC=160
     (8, 32, 32, 320, 320, 3, 2, 0, False),    # nearest-x2 upsample folded
-    (16, 32, 32, 320, 640, 3, 1, 1, False),   # four channel tiles, GELU epilogue
+    # fp16: halo kernel; fp32: igemm2, BC=128
+    (16, 32, 32, 320, 640, 3, 1, 1, False),   # five channel tiles, GELU epilogue
     (2, 128, 128, 256, 256, 3, 1, 2, True),   # BC=128, SiLU epilogue + residual
 ]
 
