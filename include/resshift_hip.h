@@ -388,6 +388,40 @@ int rs_add_noise(const float* x, float* out, const rs_noise_key* keys, const int
                  int W, int clamp, void* stream);
 int rs_unit_to_u8(const float* src_f32_nchw, void* dst_u8_nhwc, int B, int C, int H, int W, void* stream);
 
+/* ---- face degradation: a real JPEG codec and a 41-tap blur under a resize -------------------------------------------
+ * The two operators the reference's face recipe (datapipe/face_degradation_testing.py face_degradation) needs beyond the ones above;
+ * resshift_amd/degrade.py FacePlan / Degrader.run_face runs it.  Same conventions: stateless, fp32 NCHW contiguous, inputs only read,
+ * one launch, a batch is bit for bit its B = 1 calls, argument errors -2 with rs_last_error() starting "rs_<name>: " before any launch.
+ *
+ * rs_jpeg_codec: libjpeg's baseline JPEG round trip at 4:2:0 - what cv2.imencode('.jpg', .., [IMWRITE_JPEG_QUALITY, q]) + imdecode and
+ *   PIL save(quality=q, subsampling=2) + open compute; the (lossless) entropy stage is never materialised.  C = 3 in RGB order; H, W >= 8;
+ *   quality [B] is a HOST array of integers 1 .. 100 (by value to the kernel, B <= RS_MAX_ROWS).  Not in place.
+ *   In:  u = (int) rintf(fminf(fmaxf(x, 0), 1) * 255.f);   out: (float) v / 255.f, a true fp32 division.  Everything between is 32-bit
+ *   integer arithmetic (>> arithmetic, FIX16(c) = (int)(c 65536 + .5), DESCALE(x, n) = (x + (1 << (n - 1))) >> n), so the result does not
+ *   depend on the mapping, the batch or the position in it.  tests/_jpeg_ref.py is this definition in numpy, equal to Pillow's libjpeg-turbo
+ *   on every byte.
+ *   Forward: Y = (FIX16(.299) R + FIX16(.587) G + FIX16(.114) B + 32768) >> 16;  Cb = (-FIX16(.16874) R - FIX16(.33126) G + FIX16(.5) B +
+ *   (128 << 16) + 32767) >> 16;  Cr = (FIX16(.5) R - FIX16(.41869) G - FIX16(.08131) B + (128 << 16) + 32767) >> 16.  Edges: pixels are
+ *   replicated on the right at full resolution up to a multiple of 16, at the bottom at full resolution up to an EVEN row count only;
+ *   chroma is down-sampled 2 x 2 as (a + b + c + d + bias) >> 2 with bias 1 on even output columns and 2 on odd ones; then the down-sampled
+ *   chroma rows and the Y rows are replicated up to the MCU multiple.  - 128; jfdctint.c's "islow" DCT (rows, then columns; CONST_BITS 13,
+ *   PASS1_BITS 2; output x 8) on every 8 x 8 block; q = sign(c) ((|c| + (d >> 1)) / d) with d = 8 t[u,v];  t = clamp((base s + 50) / 100,
+ *   1, 255), s = q < 50 ? 5000 / q : 200 - 2 q in integer divisions, base = Annex K's luminance / chrominance table in natural order.
+ *   Inverse: q t; jidctint.c's "islow" IDCT (columns with DESCALE 11, then rows with DESCALE 18); + 128; clamp to 0 .. 255.  Chroma
+ *   "fancy" (triangle) up-sampling over the REAL ceil(H/2) x ceil(W/2) samples: vertically s = 3 near + far (far = the row above for the
+ *   upper output row, below for the lower; the first / last real row stand in for a missing one), horizontally even = (3 s[j] + s[j-1] +
+ *   8) >> 4, odd = (3 s[j] + s[j+1] + 7) >> 4 (the first / last real column stand in likewise).  R = Y + ((FIX16(1.402) cr + 32768) >>
+ *   16), B = Y + ((FIX16(1.772) cb + 32768) >> 16), G = Y + ((-FIX16(.34414) cb - FIX16(.71414) cr + 32768) >> 16) with cb, cr = chroma -
+ *   128; clamp to 0 .. 255.
+ * rs_blur_resize: out = bilinear(filter2D(in, kernels), size = (Ho, Wo)), the filter evaluated only at the samples the resize reads; no
+ *   blurred tensor exists.  filter2D is rs_filter2d's function (same taps, same order) with k odd, k <= 41, k / 2 < min(H, W), Bk = 1 or
+ *   B; bilinear is rs_interp's size-given rule (steps H / Ho, W / Wo) with the scales Ho / H, Wo / W in [1/64, 64].  kernels == NULL (then
+ *   k must be 0): the resize alone.  At Ho = H, Wo = W the result is rs_filter2d's, bit for bit.  clamp = 1 clamps the result to [0, 1].
+ *   Not in place. */
+int rs_jpeg_codec(const float* in, float* out, const int* quality, int B, int C, int H, int W, void* stream);
+int rs_blur_resize(const float* in, const float* kernels, float* out, int B, int C, int H, int W, int Ho, int Wo, int k, int Bk, int clamp,
+                   void* stream);
+
 /* uint8 pre / post processing on the device.
  * rs_u8_to_input:  interleaved uint8 [B,H,W,C] -> planar fp32 [B,C,H,W] in [-1,1]  ((v/255 - 0.5)/0.5; replaces
  *                  datapipe/datasets.py:59-63 ToTensor + Normalize on the host)

@@ -150,6 +150,8 @@ SIGNATURES = {
     "rs_jpeg": (_I, [_P, _P, C.POINTER(C.c_float)] + [_I] * 4 + [_P]),
     "rs_add_noise": (_I, [_P, _P, C.POINTER(NoiseKey), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)] + [_I] * 5 + [_P]),
     "rs_unit_to_u8": (_I, [_P, _P] + [_I] * 4 + [_P]),
+    "rs_jpeg_codec": (_I, [_P, _P, C.POINTER(C.c_int)] + [_I] * 4 + [_P]),
+    "rs_blur_resize": (_I, [_P, _P, _P] + [_I] * 9 + [_P]),
     "rs_u8_to_input": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rs_output_to_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rs_arena_bytes": (_SZ, [_P]),
@@ -492,6 +494,60 @@ def unit_to_u8(x):
     B, Cc, H, W = _image_batch(x, "unit_to_u8")
     out = torch.empty((B, H, W, Cc), device=x.device, dtype=torch.uint8)
     check(load().rs_unit_to_u8(x.data_ptr(), out.data_ptr(), B, Cc, H, W, current_stream_ptr()), "rs_unit_to_u8")
+    return out
+
+
+# ---- face degradation operators (include/resshift_hip.h "face degradation") ----------------------------------------------
+BLUR_RESIZE_KMAX = 41
+BLUR_RESIZE_SCALES = (1.0 / 64, 64.0)
+JPEG_CODEC_MIN = 8   # rs_jpeg_codec: the least height and width
+
+
+def jpeg_codec(x, quality):
+    """rs_jpeg_codec: libjpeg's baseline JPEG round trip at 4:2:0 (cv2's imencode + imdecode, PIL's save(quality=q, subsampling=2) + open) on
+    x [B,3,H,W] in RGB order, a contiguous fp32 device tensor that is clipped to [0, 1] and rounded to 8 bits; H, W >= 8; `quality` one
+    integer per image (or one for all) in 1 .. 100.  Batches above RS_MAX_ROWS go in chunks.  Returns a new tensor on the 1/255 grid."""
+    B, Cc, H, W = _image_batch(x, "jpeg_codec")
+    if Cc != 3:
+        raise ValueError(f"jpeg_codec: C must be 3 (RGB), not {Cc}")
+    if H < JPEG_CODEC_MIN or W < JPEG_CODEC_MIN:
+        raise ValueError(f"jpeg_codec: H and W must be at least {JPEG_CODEC_MIN}, not {H} x {W}")
+    q = [quality] * B if isinstance(quality, bool) else _per_image(quality, B, "jpeg_codec", "qualities")
+    if not all(isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= 100 for v in q):
+        raise ValueError(f"jpeg_codec: every quality must be an integer in 1 .. 100, not {q}")
+    out = torch.empty_like(x)
+    lib = load()
+    for b0 in range(0, B, RS_MAX_ROWS):
+        n = min(RS_MAX_ROWS, B - b0)
+        check(lib.rs_jpeg_codec(x[b0:].data_ptr(), out[b0:].data_ptr(), (C.c_int * n)(*q[b0:b0 + n]), n, 3, H, W, current_stream_ptr()), "rs_jpeg_codec")
+    return out
+
+
+def blur_resize(x, kernels, size, clamp=False):
+    """rs_blur_resize: bilinear(filter2d(x, kernels), size=(Ho, Wo)) in one launch, the filter evaluated only where the resize reads it.  x
+    [B,C,H,W] and kernels [Bk,k,k] as `filter2d` takes them, with k odd and at most 41; `kernels=None`: the bilinear resize alone.  The
+    scales Ho / H and Wo / W must lie in [1/64, 64].  `clamp` clamps the result to [0, 1].  Returns a new tensor."""
+    B, Cc, H, W = _image_batch(x, "blur_resize")
+    if not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and not isinstance(v, bool) and v > 0 for v in size)):
+        raise ValueError(f"blur_resize: size must be two positive integers (Ho, Wo), not {size!r}")
+    Ho, Wo = size
+    Bk = k = 0
+    if kernels is not None:
+        if not (isinstance(kernels, torch.Tensor) and kernels.is_cuda and kernels.dtype == torch.float32 and kernels.is_contiguous() and kernels.dim() == 3
+                and kernels.shape[1] == kernels.shape[2] and kernels.device == x.device):
+            raise ValueError("blur_resize: kernels [Bk,k,k] must be a contiguous float32 tensor on x's device (or None)")
+        Bk, k = int(kernels.shape[0]), int(kernels.shape[1])
+        if k % 2 == 0 or k > BLUR_RESIZE_KMAX:
+            raise ValueError(f"blur_resize: k must be odd and at most {BLUR_RESIZE_KMAX}, not {k}")
+        if k // 2 >= min(H, W):
+            raise ValueError(f"blur_resize: k // 2 = {k // 2} must be below min(H, W) = {min(H, W)} (one reflection per border)")
+        if Bk not in (1, B):
+            raise ValueError(f"blur_resize: {Bk} kernels for {B} images (1 or B)")
+    if not all(BLUR_RESIZE_SCALES[0] <= v <= BLUR_RESIZE_SCALES[1] for v in (Ho / H, Wo / W)):
+        raise ValueError(f"blur_resize: the scales of {H} x {W} -> {Ho} x {Wo} must lie in [1/64, 64]")
+    out = torch.empty((B, Cc, Ho, Wo), device=x.device, dtype=torch.float32)
+    check(load().rs_blur_resize(x.data_ptr(), kernels.data_ptr() if kernels is not None else None, out.data_ptr(), B, Cc, H, W, Ho, Wo, k, Bk,
+                                1 if clamp else 0, current_stream_ptr()), "rs_blur_resize")
     return out
 
 

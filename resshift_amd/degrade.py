@@ -7,10 +7,14 @@ DiffJPEG and a sinc filter, on a CPU with cv2 / torchvision.  Here the random ch
 rs_jpeg, rs_unit_to_u8).  `make_testset` turns a folder of ground-truth images into a folder of LQ PNGs plus plans.json, after which
 `ResShiftSampler.inference(lq_dir, out, gt_path=gt_dir)` scores the restoration.  No sampler and no weights are needed.
 
-    python -m resshift_amd.degrade GT_DIR LQ_DIR [--sf 4] [--seed 10000]
+    python -m resshift_amd.degrade GT_DIR LQ_DIR [--sf 4] [--seed 10000] [--recipe realesrgan | face]
+
+The face recipe - scripts/prepare_testing_celeba_faceir.py -> datapipe/face_degradation_testing.py face_degradation: a
+41-tap anisotropic Gaussian blur, a bilinear resize down by a real factor up to 32, noise, cv2's JPEG codec, a bilinear resize back -
+is `FaceOptions` / `FacePlan` / `draw_face_plan` / `Degrader.run_face` / `make_face_testset` on rs_blur_resize and rs_jpeg_codec.
 
 Not built: Poisson noise (`draw_plan` raises for gaussian_noise_prob < 1; the preset sets both to 1.0 where the
-reference's recipe has 0.5), the ground truth's SmallestMaxSize + CenterCrop preparation, the face recipe, the reference's RNG stream.
+reference's recipe has 0.5), the ground truth's SmallestMaxSize + CenterCrop preparation, the reference's RNG stream.
 """
 from __future__ import annotations
 
@@ -304,6 +308,96 @@ def draw_plan(opts: DegradeOptions, B: int, H: int, W: int, seed: int) -> Degrad
                        final_mode=final_mode, final_kernels=tuple(final), jpeg2=jpeg2, noise_seeds=noise_seeds)
 
 
+# ---------------------------------------------------------------------------------------------------------------- the face recipe
+@dataclass(frozen=True)
+class FaceOptions:
+    """the ranges scripts/prepare_testing_celeba_faceir.py draws from (uniform on [lo, hi)), and face_degradation's kernel size"""
+    sf: Tuple[float, float] = (1.0, 32.0)
+    qf: Tuple[float, float] = (30.0, 70.0)
+    nf: Tuple[float, float] = (1.0, 20.0)
+    sig: Tuple[float, float] = (4.0, 16.0)
+    theta: Tuple[float, float] = (0.0, math.pi)
+    kernel_size: int = 41
+
+
+FACE_TESTING = FaceOptions()
+FACE_MIN_SIDE = 256   # below it `small` = side // sf can fall under rs_jpeg_codec's 8 at sf = 32
+
+
+@dataclass(frozen=True)
+class FacePlan:
+    """every random choice of one face_degradation call on an image of H x W; `quality` = int(qf), which is what cv2 receives; `small` =
+    (int(H // sf), int(W // sf)), the size between the two resizes"""
+    H: int
+    W: int
+    sf: float
+    sig_x: float
+    sig_y: float
+    theta: float
+    nf: float
+    quality: int
+    small: Tuple[int, int]
+    kernel_size: int
+    seed: int
+    noise_seed: int
+
+    def stages(self) -> list:
+        return ["blur_down", "noise", "jpeg", "up", "round"]
+
+    def kernel(self) -> np.ndarray:
+        return blur_kernel("aniso", self.kernel_size, self.sig_x, self.sig_y, self.theta)
+
+    def to_dict(self) -> dict:
+        return dataclasses.asdict(self)
+
+    def to_json(self) -> str:
+        return json.dumps(self.to_dict())
+
+    @staticmethod
+    def from_dict(d) -> "FacePlan":
+        return FacePlan(H=int(d["H"]), W=int(d["W"]), sf=float(d["sf"]), sig_x=float(d["sig_x"]), sig_y=float(d["sig_y"]), theta=float(d["theta"]),
+                        nf=float(d["nf"]), quality=int(d["quality"]), small=(int(d["small"][0]), int(d["small"][1])),
+                        kernel_size=int(d["kernel_size"]), seed=int(d["seed"]), noise_seed=int(d["noise_seed"]))
+
+    @staticmethod
+    def from_json(text) -> "FacePlan":
+        return FacePlan.from_dict(json.loads(text))
+
+
+def face_plan(H, W, sf, sig_x, sig_y, theta, nf, qf, kernel_size=41, seed=0, noise_seed=0) -> FacePlan:
+    """a FacePlan from face_degradation's own arguments: quality and small are derived as the reference derives them"""
+    H, W, k = int(H), int(W), int(kernel_size)
+    if H < 1 or W < 1:
+        raise ValueError(f"face_plan: H and W must be positive, not {H}, {W}")
+    if not 1.0 <= float(sf) <= 64.0:
+        raise ValueError(f"face_plan: sf = {sf} must lie in [1, 64]")
+    if k % 2 != 1 or not 1 <= k <= _lib.BLUR_RESIZE_KMAX:
+        raise ValueError(f"face_plan: the kernel size must be odd and at most {_lib.BLUR_RESIZE_KMAX}, not {k}")
+    if k // 2 >= min(H, W):
+        raise ValueError(f"face_plan: {H} x {W} is too small for a blur kernel of {k} taps")
+    quality, small = int(qf), (int(H // float(sf)), int(W // float(sf)))
+    if not 1 <= quality <= 100:
+        raise ValueError(f"face_plan: int(qf) = {quality} must lie in 1 .. 100")
+    if min(small) < _lib.JPEG_CODEC_MIN:
+        raise ValueError(f"face_plan: {H} x {W} at sf = {sf} gives {small[0]} x {small[1]}, below the JPEG codec's {_lib.JPEG_CODEC_MIN}")
+    if not (float(nf) >= 0 and float(sig_x) > 0 and float(sig_y) > 0):
+        raise ValueError(f"face_plan: nf must not be negative and the sigmas must be positive, not {nf}, {sig_x}, {sig_y}")
+    return FacePlan(H=H, W=W, sf=float(sf), sig_x=float(sig_x), sig_y=float(sig_y), theta=float(theta), nf=float(nf), quality=quality, small=small,
+                    kernel_size=k, seed=int(seed), noise_seed=int(noise_seed))
+
+
+def draw_face_plan(opts: FaceOptions, H: int, W: int, seed: int) -> FacePlan:
+    """The random choices of scripts/prepare_testing_celeba_faceir.py for one image, from numpy.random.Generator(Philox(seed)) in the
+    script's order - sf, qf, nf, sig_x, sig_y, theta - then the noise seed.  As `draw_plan`: the recipe's distribution, not the
+    reference's RNG stream (Python's `random`)."""
+    if min(int(H), int(W)) < FACE_MIN_SIDE:
+        raise ValueError(f"draw_face_plan: {H} x {W} has a side below {FACE_MIN_SIDE} (H // sf can fall under the JPEG codec's {_lib.JPEG_CODEC_MIN})")
+    rng = np.random.Generator(np.random.Philox(int(seed) % 2 ** 64))
+    sf, qf, nf = (float(rng.uniform(*r)) for r in (opts.sf, opts.qf, opts.nf))
+    sig_x, sig_y, theta = (float(rng.uniform(*r)) for r in (opts.sig, opts.sig, opts.theta))
+    return face_plan(H, W, sf, sig_x, sig_y, theta, nf, qf, opts.kernel_size, seed=seed, noise_seed=int(rng.integers(0, 2 ** 63)))
+
+
 # ---------------------------------------------------------------------------------------------------------------- execution
 class _LibOps:
     """the engine's degradation methods for a caller without an Engine: the same _lib calls on `device`"""
@@ -329,6 +423,12 @@ class _LibOps:
 
     def unit_to_u8(self, x):
         return self._call(_lib.unit_to_u8, x)
+
+    def jpeg_codec(self, x, quality):
+        return self._call(_lib.jpeg_codec, x, quality)
+
+    def blur_resize(self, x, kernels, size, clamp=False):
+        return self._call(_lib.blur_resize, x, kernels, size, clamp=clamp)
 
 
 class Degrader:
@@ -389,6 +489,35 @@ class Degrader:
         _, log = self.run(gt01, plan, trace=True)
         return log[-1][2]
 
+    def run_face(self, gt01, plan: FacePlan, trace=False):
+        """gt01 [1,3,H,W] in [0,1], RGB -> the face LQ image [1,3,H,W], fp32 on the 1/255 grid, in face_degradation's order: `blur_down` (the
+        41-tap Gaussian under the bilinear resize to plan.small, one launch), `noise` (clamped), `jpeg` (libjpeg's codec at plan.quality),
+        `up` (the bilinear resize back to H x W), `round`.  One image per call: `small` differs from image to image.  trace=True: (lq,
+        [(stage, input, output)]) as `run` returns it."""
+        if tuple(gt01.shape) != (1, 3, plan.H, plan.W):
+            raise ValueError(f"Degrader.run_face: the plan is for {(1, 3, plan.H, plan.W)}, the batch is {tuple(gt01.shape)}")
+        ops, log = self.ops, []
+
+        def step(name, x, y):
+            log.append((name, x, y))
+            return y
+
+        x = gt01.to(self.device, torch.float32).contiguous()
+        kernel = torch.from_numpy(plan.kernel()[None]).to(self.device)
+        x = step("blur_down", x, ops.blur_resize(x, kernel, tuple(plan.small)))
+        x = step("noise", x, ops.add_noise(x, [(plan.noise_seed, 0)], [plan.nf], gray=False, draw=0, clamp=True))
+        x = step("jpeg", x, ops.jpeg_codec(x, [plan.quality]))
+        x = step("up", x, ops.blur_resize(x, None, (plan.H, plan.W)))
+        u8 = step("round", x, ops.unit_to_u8(x))
+        lq = u8.permute(0, 3, 1, 2).to(torch.float32).div(255.0).contiguous()
+        return (lq, log) if trace else lq
+
+    def run_face_u8(self, gt_u8, plan: FacePlan):
+        """uint8 [1,H,W,3] -> uint8 [1,H,W,3] (device tensors): what `make_face_testset` reads and writes"""
+        gt01 = gt_u8.to(self.device).permute(0, 3, 1, 2).to(torch.float32).div(255.0).contiguous()
+        _, log = self.run_face(gt01, plan, trace=True)
+        return log[-1][2]
+
 
 # ---------------------------------------------------------------------------------------------------------------- files
 def list_images(path) -> list:
@@ -438,16 +567,51 @@ def make_testset(gt_dir, lq_dir, sf=4, opts: DegradeOptions = REALESRGAN_TESTING
     return plans
 
 
+def make_face_testset(gt_dir, lq_dir, opts: FaceOptions = FACE_TESTING, seed=10000, device=None, positions=None) -> dict:
+    """`make_testset` for the face recipe: lq_dir/<stem>.png of the GROUND TRUTH'S size plus lq_dir/plans.json {stem: FacePlan}; the image at
+    position i of the sorted listing gets the plan draw_face_plan(opts, H, W, request_seed(seed, i)).  Every side must be at least 256
+    (ValueError naming the file, before anything is written).  `device`, `positions` and the return value as `make_testset` has them."""
+    from PIL import Image
+
+    files = list_images(gt_dir)
+    todo = list(range(len(files))) if positions is None else list(positions)
+    sizes = {}
+    for i in todo:
+        with Image.open(files[i]) as im:
+            w, h = im.size
+        if min(h, w) < FACE_MIN_SIDE:
+            raise ValueError(f"{files[i]}: {h} x {w} has a side below {FACE_MIN_SIDE}")
+        sizes[i] = (h, w)
+    lq_dir = Path(lq_dir)
+    lq_dir.mkdir(parents=True, exist_ok=True)
+    dg = Degrader(device)
+    plans = {}
+    for i in todo:
+        plan = draw_face_plan(opts, *sizes[i], request_seed(seed, i))
+        gt = torch.from_numpy(np.asarray(Image.open(files[i]).convert("RGB"), dtype=np.uint8).copy()).unsqueeze(0)
+        lq = dg.run_face_u8(gt, plan)[0].cpu().numpy()
+        Image.fromarray(lq).save(lq_dir / f"{files[i].stem}.png")
+        plans[files[i].stem] = plan
+    if positions is None:
+        write_plans(lq_dir, plans)
+    return plans
+
+
 def main(argv=None):
     import argparse
 
-    ap = argparse.ArgumentParser(prog="python -m resshift_amd.degrade", description="Real-ESRGAN degradation of a folder of ground-truth images, on the device")
+    ap = argparse.ArgumentParser(prog="python -m resshift_amd.degrade", description="Real-ESRGAN or face degradation of a folder of ground-truth images, on the device")
     ap.add_argument("gt_dir")
     ap.add_argument("lq_dir")
     ap.add_argument("--sf", type=int, default=4)
     ap.add_argument("--seed", type=int, default=10000)
+    ap.add_argument("--recipe", choices=("realesrgan", "face"), default="realesrgan",
+                    help="face: datapipe/face_degradation_testing.py (the LQ images keep the ground truth's size; --sf is not used)")
     a = ap.parse_args(argv)
-    plans = make_testset(a.gt_dir, a.lq_dir, sf=a.sf, seed=a.seed)
+    if a.recipe == "face":
+        plans = make_face_testset(a.gt_dir, a.lq_dir, seed=a.seed)
+    else:
+        plans = make_testset(a.gt_dir, a.lq_dir, sf=a.sf, seed=a.seed)
     print(f"{len(plans)} images -> {a.lq_dir} (plans.json)")
 
 

@@ -238,6 +238,18 @@ class Engine:
         with torch.cuda.device(self.device):
             return _lib.unit_to_u8(self._f32c(x))
 
+    # the face recipe's operators
+    def jpeg_codec(self, x, quality):
+        """libjpeg's baseline JPEG round trip at 4:2:0 on x [B,3,H,W] (RGB, clipped to [0,1]), one integer quality 1 .. 100 per image
+        (rs_jpeg_codec): cv2's imencode + imdecode, byte for byte."""
+        with torch.cuda.device(self.device):
+            return _lib.jpeg_codec(self._f32c(x), quality)
+
+    def blur_resize(self, x, kernels, size, clamp=False):
+        """bilinear(filter2d(x, kernels), size) in one launch with kernels of up to 41 taps; kernels=None: the resize alone (rs_blur_resize)."""
+        with torch.cuda.device(self.device):
+            return _lib.blur_resize(self._f32c(x), None if kernels is None else self._f32c(kernels), size, clamp=clamp)
+
     def metrics(self, sr, gt, border=0, ycbcr=True):
         """PSNR / SSIM of the batch `sr` against the ground truth `gt` on uint8 pixels, as the reference's calculate_psnr / calculate_ssim
         score them (rs_metrics).  Each is uint8 [B,H,W,C] or a float tensor [B,C,H,W] in [-1,1], which is quantised exactly

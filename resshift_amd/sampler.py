@@ -374,13 +374,17 @@ class ResShiftSampler(BaseSampler):
         """A folder of ground-truth images -> a folder of LQ PNGs plus plans.json, by the reference's Real-ESRGAN degradation on the device
         (degrade.make_testset) with this sampler's `sf`, seed and device; the listing is sharded over the ranks like
         `inference`'s, rank 0 writes plans.json.  Then `inference(lq_path, out, gt_path=gt_path)` closes the loop.  Returns {stem: plan}
-        for the whole input on every rank."""
+        for the whole input on every rank.  `opts=degrade.FACE_TESTING` (a FaceOptions): the face recipe instead (degrade.make_face_testset,
+        DESIGN.md 7i), whose LQ images keep the ground truth's size."""
         from . import degrade
 
         files = degrade.list_images(gt_path)
         mine = [first + j for first, part in self._shares(files, self.num_gpus) for j in range(len(part))]
-        plans = degrade.make_testset(gt_path, lq_path, sf=self.sf, opts=degrade.REALESRGAN_TESTING if opts is None else opts,
-                                     seed=self.seed if seed is None else seed, device=getattr(self, "engine", None) or self.device, positions=mine)
+        common = dict(seed=self.seed if seed is None else seed, device=getattr(self, "engine", None) or self.device, positions=mine)
+        if isinstance(opts, degrade.FaceOptions):   # the face recipe (DESIGN.md 7i): LQ images of the ground truth's size
+            plans = degrade.make_face_testset(gt_path, lq_path, opts=opts, **common)
+        else:
+            plans = degrade.make_testset(gt_path, lq_path, sf=self.sf, opts=degrade.REALESRGAN_TESTING if opts is None else opts, **common)
         if self.num_gpus > 1 and dist.is_available() and dist.is_initialized():
             parts = [None] * dist.get_world_size()
             dist.all_gather_object(parts, plans)
