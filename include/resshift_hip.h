@@ -482,6 +482,17 @@ int rs_debug_fetch_rows(rs_engine* e, int i, int b0, int nb, float* out_nchw_dev
 int rs_op_conv2d(const void* x0, const void* x1, const float* w_ref_host, const float* bias_host, const void* res, void* y,
                  int B, int Hs, int Ws, int C0, int C1, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho,
                  int Wo, int up, int act, int in_prec, int out_prec, int force_direct, void* stream);
+/* rs_op_conv2d on views into wider buffers: ld0 / ld1 / ldy / ldres are the row strides, in elements, of x0 / x1 / y / res (the pixel record
+ * of split storage is [ld hi | ld lo]).  plan_out (may be NULL) receives the plan the launch EXECUTED - kernel (ConvKernel of csrc/common.h),
+ * pixel tile, channel tile, small-plane segment, split-K factor, pixels per statistics slab - or six zeros when a direct kernel took it. */
+int rs_op_conv2d_ex(const void* x0, const void* x1, const float* w_ref_host, const float* bias_host, const void* res, void* y,
+                    int B, int Hs, int Ws, int C0, int C1, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho,
+                    int Wo, int up, int act, int in_prec, int out_prec, int force_direct, int ld0, int ld1, int ldy, int ldres,
+                    int plan_out[6], void* stream);
+/* the plan rs_op_conv2d_ex would execute for this layer (has_res: a residual is added; nz: batched-GEMM count, 1 for a conv).  Host only:
+ * touches no device.  out[6] as plan_out above; returns the planner's return code (0, or -2: no kernel takes the launch). */
+int rs_op_conv_plan(int B, int Hs, int Ws, int C0, int C1, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo,
+                    int up, int act, int in_prec, int out_prec, int ld0, int ld1, int ldy, int ldres, int has_res, int nz, int out[6]);
 /* timing probe for one implicit-GEMM conv shape: device-resident NHWC input, weights already packed [Cout][KH*KW*Cin]
  * in the input precision; runs `reps` launches between two hipEvents and returns the average ms per launch. */
 int rs_op_conv2d_bench(const void* x0, const void* w_packed_dev, const float* bias_dev, const void* res, void* y, int B, int Hs,

@@ -166,6 +166,8 @@ SIGNATURES = {
     "rs_debug_fetch": (_I, [_P, _I, _P, _P]),
     "rs_debug_fetch_rows": (_I, [_P, _I, _I, _I, _P, _P]),
     "rs_op_conv2d": (_I, [_P, _P, _P, _P, _P, _P] + [_I] * 18 + [_P]),
+    "rs_op_conv2d_ex": (_I, [_P, _P, _P, _P, _P, _P] + [_I] * 22 + [C.POINTER(C.c_int), _P]),
+    "rs_op_conv_plan": (_I, [_I] * 23 + [C.POINTER(C.c_int)]),
     "rs_op_conv2d_bench": (_I, [_P, _P, _P, _P, _P] + [_I] * 16 + [C.POINTER(C.c_float), _P]),
     "rs_op_conv3x3_halo_stats_px": (_I, [_I, _I, _I, _I, _I, _I]),
     "rs_op_conv3x3_halo": (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),

@@ -61,13 +61,15 @@ static int time_launches(const IGemmParams& p, int in_prec, int out_prec, const 
 
 // The op-level conv entries: plan the launch (rs_conv_plan), give it its split-K slab, launch it once and - `timed` - `reps` more times
 // between two hipEvents (*ms_out = their average milliseconds), free the slab.  `halo_only`: fail unless the plan is the halo kernel's.
-static int op_conv_run(IGemmParams p, int in_prec, int out_prec, hipStream_t st, bool halo_only = false, bool timed = false, int reps = 0, float* ms_out = nullptr) {
+static int op_conv_run(IGemmParams p, int in_prec, int out_prec, hipStream_t st, bool halo_only = false, bool timed = false, int reps = 0, float* ms_out = nullptr,
+                       ConvPlan* executed = nullptr) {
     ConvPlan pl{};
     (void)rs_conv_plan(&p, in_prec, out_prec, 1, &pl);
     if (halo_only && pl.kernel != CK_HALO && pl.kernel != CK_HALO_SEG) return rs_set_last_error("shape is not eligible for the halo kernel", -1);
     float* part = nullptr;
     if (pl.splitk > 1) { (void)hipMalloc((void**)&part, (size_t)pl.splitk * p.M * p.Cout * sizeof(float)); p.partial = part; }
     int rc = rs_conv_launch(&p, in_prec, out_prec, 1, &pl, st);
+    if (executed) *executed = pl;   // the plan rs_conv_launch was handed, not a second answer of the planner
     if (rc) rs_set_last_error("igemm launch rejected the shape", -1);
     else if (timed) rc = time_launches(p, in_prec, out_prec, pl, reps, st, ms_out);
     (void)hipStreamSynchronize(st);
@@ -75,38 +77,75 @@ static int op_conv_run(IGemmParams p, int in_prec, int out_prec, hipStream_t st,
     return rc;
 }
 
-int rs_op_conv2d(const void* x0, const void* x1, const float* w_ref_host, const float* bias_host, const void* res, void* y, int B, int Hs,
-                 int Ws, int C0, int C1, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, int up, int act,
-                 int in_prec, int out_prec, int force_direct, void* stream) {
+// The IGemmParams of a conv layer as the op-level entries describe it (rs_op_conv2d_ex and rs_op_conv_plan fill it here, nowhere else):
+// ld0 / ld1 / ldy / ldres are the row strides in elements of the buffers the sources, y and the residual are views into
+static IGemmParams op_conv_params(const void* x0, const void* x1, const void* wdev, const float* bias, const void* res, void* y, int B, int Hs, int Ws,
+                                  int C0, int C1, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, int up, int act, int ld0,
+                                  int ld1, int ldy, int ldres) {
+    IGemmParams p{};
+    p.x0 = x0; p.x1 = x1; p.w = wdev; p.bias = bias; p.res = res; p.y = y; p.C0 = C0; p.C1 = C1; p.ld0 = ld0; p.ld1 = ld1;
+    p.B = B; p.Hs = Hs; p.Ws = Ws; p.up = up; p.Ho = Ho; p.Wo = Wo; p.KH = KH; p.KW = KW; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
+    p.Cout = Cout; p.ldy = ldy; p.ldres = ldres; p.M = B * Ho * Wo; p.Ktot = KH * KW * (C0 + C1); p.act = act; p.out_scale = 1.f;
+    return p;
+}
+// the layers rs_op_conv2d hands to the direct kernels: these never reach rs_conv_plan
+static bool op_conv_is_direct(int C0, int C1, int Cout) { return ((C0 + C1) % 8 != 0) || (C0 % 8 != 0) || Cout <= 8; }
+static void plan_to_ints(const ConvPlan& pl, int out[6]) {
+    out[0] = pl.kernel; out[1] = pl.BP; out[2] = pl.BC; out[3] = pl.SEG; out[4] = pl.splitk; out[5] = pl.stats_px;
+}
+
+int rs_op_conv_plan(int B, int Hs, int Ws, int C0, int C1, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, int up, int act,
+                    int in_prec, int out_prec, int ld0, int ld1, int ldy, int ldres, int has_res, int nz, int out[6]) {
+    static const char some_residual = 0;   // the planner asks only whether there is one
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    if (op_conv_is_direct(C0, C1, Cout)) return 0;
+    const IGemmParams p = op_conv_params(nullptr, nullptr, nullptr, nullptr, has_res ? &some_residual : nullptr, nullptr, B, Hs, Ws, C0, C1, Cout, KH, KW,
+                                         stride, pad_t, pad_l, Ho, Wo, up, act, ld0, ld1, ldy, ldres);
+    ConvPlan pl{};
+    const int rc = rs_conv_plan(&p, in_prec, out_prec, nz, &pl);
+    plan_to_ints(pl, out);
+    return rc;
+}
+
+int rs_op_conv2d_ex(const void* x0, const void* x1, const float* w_ref_host, const float* bias_host, const void* res, void* y, int B, int Hs,
+                    int Ws, int C0, int C1, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, int up, int act,
+                    int in_prec, int out_prec, int force_direct, int ld0, int ld1, int ldy, int ldres, int plan_out[6], void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const int Cin = C0 + C1;
     const size_t K = (size_t)KH * KW * Cin, n = K * Cout;
-    const bool direct = force_direct || (Cin % 8 != 0) || (C0 % 8 != 0) || Cout <= 8;
+    const bool direct = force_direct || op_conv_is_direct(C0, C1, Cout);
     float* bias = bias_host ? (float*)dev_copy(bias_host, Cout * 4) : nullptr;
     int rc;
     void* wdev = nullptr;
+    ConvPlan executed{};
     if (direct) {
         std::vector<float> o(n);
         rs_pack_tap_major(w_ref_host, Cout, Cin, KH * KW, o.data());
         wdev = dev_copy(o.data(), n * 4);
         DirectConvParams p{};
-        p.x0 = x0; p.x1 = x1; p.w = (const float*)wdev; p.bias = bias; p.y = y; p.C0 = C0; p.C1 = C1; p.ld0 = C0; p.ld1 = C1;
+        p.x0 = x0; p.x1 = x1; p.w = (const float*)wdev; p.bias = bias; p.y = y; p.C0 = C0; p.C1 = C1; p.ld0 = ld0; p.ld1 = ld1;
         p.B = B; p.Hs = Hs; p.Ws = Ws; p.up = up; p.Ho = Ho; p.Wo = Wo; p.KH = KH; p.KW = KW; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-        p.Cout = Cout; p.ldy = Cout; p.act = act;
+        p.Cout = Cout; p.ldy = ldy; p.act = act;
         if (res) { rc = rs_set_last_error("direct conv has no residual path", -1); }
         else rc = rs_direct_conv_launch(&p, in_prec, out_prec, st);
     } else {
         wdev = pack_rows_dev(w_ref_host, Cout, Cin, KH * KW, in_prec);
-        IGemmParams p{};
-        p.x0 = x0; p.x1 = x1; p.w = wdev; p.bias = bias; p.res = res; p.y = y; p.C0 = C0; p.C1 = C1; p.ld0 = C0; p.ld1 = C1;
-        p.B = B; p.Hs = Hs; p.Ws = Ws; p.up = up; p.Ho = Ho; p.Wo = Wo; p.KH = KH; p.KW = KW; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-        p.Cout = Cout; p.ldy = Cout; p.ldres = Cout; p.M = B * Ho * Wo; p.Ktot = (int)K; p.act = act; p.out_scale = 1.f;
-        rc = op_conv_run(p, in_prec, out_prec, st);
+        const IGemmParams p = op_conv_params(x0, x1, wdev, bias, res, y, B, Hs, Ws, C0, C1, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo, up, act, ld0, ld1,
+                                             ldy, ldres);
+        rc = op_conv_run(p, in_prec, out_prec, st, false, false, 0, nullptr, &executed);
     }
+    if (plan_out) plan_to_ints(executed, plan_out);
     (void)hipStreamSynchronize(st);
     if (wdev) (void)hipFree(wdev);
     if (bias) (void)hipFree(bias);
     return rc;
+}
+
+int rs_op_conv2d(const void* x0, const void* x1, const float* w_ref_host, const float* bias_host, const void* res, void* y, int B, int Hs,
+                 int Ws, int C0, int C1, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, int up, int act,
+                 int in_prec, int out_prec, int force_direct, void* stream) {
+    return rs_op_conv2d_ex(x0, x1, w_ref_host, bias_host, res, y, B, Hs, Ws, C0, C1, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo, up, act, in_prec,
+                           out_prec, force_direct, C0, C1, Cout, Cout, nullptr, stream);
 }
 
 // micro-benchmark of one implicit-GEMM conv shape (random device data is supplied by the caller): `reps` launches

@@ -7,6 +7,7 @@ Tensors are NHWC (channels last, contiguous) on the GPU; `prec` 0 = fp16 storage
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
@@ -38,30 +39,63 @@ def _hostf(t: torch.Tensor):
     return t, t.data_ptr()
 
 
+CONV_KERNELS = ("CK_NONE", "CK_WINO", "CK_HALO", "CK_HALO_SEG", "CK_SPLIT", "CK_IGEMM3", "CK_IGEMM2", "CK_IGEMM")   # enum ConvKernel, csrc/common.h
+ConvPlan = namedtuple("ConvPlan", "kernel BP BC SEG splitk stats_px")   # struct ConvPlan (csrc/common.h) with the kernel by name
+
+
+def _plan(ints):
+    return ConvPlan(CONV_KERNELS[ints[0]], *ints[1:6])
+
+
+def _out_hw(Hs, Ws, KH, KW, stride, pad, up):
+    return (Hs * up + 2 * pad[0] - KH) // stride + 1, (Ws * up + 2 * pad[1] - KW) // stride + 1
+
+
+def conv_plan(B, Hs, Ws, C0, Cout, k, in_prec, out_prec=None, C1=0, stride=1, pad=None, out_hw=None, up=1, act=0, has_res=False, ld=None, nz=1):
+    """The plan `conv2d` would execute for this layer (rs_op_conv_plan: host code only, no device): a ConvPlan, or None when no kernel takes
+    the launch.  k: the square kernel's size; pad defaults to (k // 2, k // 2); ld = (ld0, ldy, ldres) as `conv2d` takes it.  A layer that
+    `conv2d` hands to the direct kernels answers ConvPlan("CK_NONE", 0, 0, 0, 0, 0)."""
+    lib = _lib.load()
+    out_prec = in_prec if out_prec is None else out_prec
+    pad = (k // 2, k // 2) if pad is None else pad
+    Ho, Wo = _out_hw(Hs, Ws, k, k, stride, pad, up) if out_hw is None else out_hw
+    ld0, ldy, ldres = (C0, Cout, Cout) if ld is None else ld
+    out = (C.c_int * 6)()
+    rc = lib.rs_op_conv_plan(B, Hs, Ws, C0, C1, Cout, k, k, stride, pad[0], pad[1], Ho, Wo, up, act, in_prec, out_prec, ld0, C1, ldy, ldres,
+                             int(has_res), nz, out)
+    return None if rc else _plan(out)
+
+
 def conv2d(x0, w_ref, bias=None, x1=None, res=None, stride=1, pad=(1, 1), out_hw=None, up=1, act=0, out_prec=None,
-           force_direct=False):
-    """x0: [B,H,W,C0] (+x1 [B,H,W,C1]); w_ref: reference layout [Cout,Cin,KH,KW]; returns [B,Ho,Wo,Cout]."""
+           force_direct=False, ld=None, return_plan=False, out=None):
+    """x0: [B,H,W,C0] (+x1 [B,H,W,C1]); w_ref: reference layout [Cout,Cin,KH,KW]; returns [B,Ho,Wo,Cout].
+    ld = (ld0, ldy, ldres): the operands are views into wider buffers and the caller passes those - x0 [B,H,W,ld0] whose first C0 = Cin - C1
+    columns are the source, res [B,Ho,Wo,ldres]; y is allocated [B,Ho,Wo,ldy] (or is `out`, of that shape) and returned whole.
+    return_plan: returns (y, ConvPlan), the plan the launch executed (all zeros under CK_NONE when a direct kernel took it)."""
     lib = _lib.load()
     in_prec = _prec_of(x0)
     out_prec = in_prec if out_prec is None else out_prec
-    B, Hs, Ws, C0 = x0.shape
     C1 = 0 if x1 is None else x1.shape[-1]
     Cout, Cin, KH, KW = w_ref.shape
+    B, Hs, Ws, ld0 = x0.shape
+    C0 = ld0 if ld is None else Cin - C1
     assert Cin == C0 + C1
+    ld0_, ldy, ldres = (C0, Cout, Cout) if ld is None else ld
+    assert ld0_ == ld0 and C0 <= ld0 and Cout <= ldy and (res is None or (Cout <= ldres and res.shape[-1] == ldres))
     pad_t, pad_l = pad
-    if out_hw is None:
-        Ho = (Hs * up + 2 * pad_t - KH) // stride + 1
-        Wo = (Ws * up + 2 * pad_l - KW) // stride + 1
-    else:
-        Ho, Wo = out_hw
-    y = torch.empty(B, Ho, Wo, Cout, device=x0.device, dtype=_dt(out_prec))
+    Ho, Wo = _out_hw(Hs, Ws, KH, KW, stride, pad, up) if out_hw is None else out_hw
+    y = torch.empty(B, Ho, Wo, ldy, device=x0.device, dtype=_dt(out_prec)) if out is None else out
+    assert tuple(y.shape) == (B, Ho, Wo, ldy) and y.dtype == _dt(out_prec) and y.is_contiguous()
+    assert res is None or (tuple(res.shape[:3]) == (B, Ho, Wo) and res.is_contiguous())
     wh, wp = _hostf(w_ref)
     bh, bp = _hostf(bias) if bias is not None else (None, None)
-    rc = lib.rs_op_conv2d(x0.data_ptr(), x1.data_ptr() if x1 is not None else None, wp, bp,
-                          res.data_ptr() if res is not None else None, y.data_ptr(), B, Hs, Ws, C0, C1, Cout, KH, KW, stride,
-                          pad_t, pad_l, Ho, Wo, up, act, in_prec, out_prec, int(force_direct), _lib.current_stream_ptr())
-    _lib.check(rc, "rs_op_conv2d")
-    return y
+    plan = (C.c_int * 6)()
+    rc = lib.rs_op_conv2d_ex(x0.data_ptr(), x1.data_ptr() if x1 is not None else None, wp, bp,
+                             res.data_ptr() if res is not None else None, y.data_ptr(), B, Hs, Ws, C0, C1, Cout, KH, KW, stride,
+                             pad_t, pad_l, Ho, Wo, up, act, in_prec, out_prec, int(force_direct), ld0, C1, ldy, ldres, plan,
+                             _lib.current_stream_ptr())
+    _lib.check(rc, "rs_op_conv2d_ex")
+    return (y, _plan(plan)) if return_plan else y
 
 
 def conv3x3_halo(x, w_ref, bias=None, coef=None, act_in=0, res=None, want_stats=False):

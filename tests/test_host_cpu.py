@@ -31,6 +31,12 @@ def test_c_abi_library_loads_and_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/resshift_hip.h but not exported"
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    # the plan query and the layout-aware conv entry: rs_op_conv2d's arguments + ld0, ld1, ldy, ldres + plan_out[6]; the query takes no pointer
+    # but its int out[6]
+    assert {"rs_op_conv_plan", "rs_op_conv2d_ex", "rs_op_conv2d"} <= declared
+    ex, plain, query = (_lib.SIGNATURES[n][1] for n in ("rs_op_conv2d_ex", "rs_op_conv2d", "rs_op_conv_plan"))
+    assert ex[:-1] == plain[:-1] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int)] and ex[-1] == plain[-1] == ctypes.c_void_p
+    assert query == [ctypes.c_int] * 23 + [ctypes.POINTER(ctypes.c_int)]
     _lib.load()
     assert _lib.last_error() == "" or isinstance(_lib.last_error(), str)
 

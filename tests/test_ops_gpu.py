@@ -47,6 +47,8 @@ CONV_CASES = [
     (3, 8, 8, 64, 48, 3, 1, (1, 1), 1, 0, False, False),       # N tail (Cout not multiple of tile)
     (1, 8, 8, 480, 160, 1, 1, (0, 0), 1, 0, False, False),     # K tail with fp16 (480 % 64 != 0)
 ]
+# the kernel each case is there for (ops.conv2d's return_plan): igemm2.hip's 64-pixel tile, but for the one layer it leaves to igemm.hip (Cout <= 64)
+CONV_KERNEL = {c: "CK_IGEMM" if c[4] <= 64 else "CK_IGEMM2" for c in CONV_CASES}
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.float32])
@@ -76,14 +78,16 @@ def test_conv_igemm(gpu, dtype, case):
         r = torch.randn(ref.shape, generator=g)
         res_d = _nhwc(r, dtype, gpu)
         ref = ref + _ref_in(res_d)
-    y = ops.conv2d(xd, w, b, res=res_d, stride=stride, pad=pad, out_hw=(ref.shape[2], ref.shape[3]), up=up, act=act)
+    y, plan = ops.conv2d(xd, w, b, res=res_d, stride=stride, pad=pad, out_hw=(ref.shape[2], ref.shape[3]), up=up, act=act, return_plan=True)
     torch.cuda.synchronize()
+    assert (plan.kernel, plan.BP) == (CONV_KERNEL[case], 64), plan
     _close(y.permute(0, 3, 1, 2), ref, TOL[dtype], f"conv {case} {dtype}")
 
 
 BIG_CONV_CASES = [
-    # shapes large enough for the LDS-DMA kernels: B, H, W, Cin, Cout, k, up, act, res.  Which kernel rs_conv_plan gives each case today -
-    # fp32 (batch cut to 8 on the 64 x 64 planes): always igemm2.hip's 128-pixel / 8-wave tile; fp16: as noted (halo = igemm4.hip)
+    # shapes large enough for the LDS-DMA kernels: B, H, W, Cin, Cout, k, up, act, res.  Which kernel rs_conv_plan gives each case -
+    # fp32 (batch cut to 8 on the 64 x 64 planes): always igemm2.hip's 128-pixel / 8-wave tile; fp16: as noted (halo = igemm4.hip) - is
+    # asserted: BIG_CONV_PLANS below
     (8, 64, 64, 160, 160, 3, 1, 0, True),     # fp16: igemm2, 128-pixel tiles, BC=160 (too few tiles for the halo kernel)
     (16, 64, 64, 160, 160, 3, 1, 0, True),    # fp16: halo kernel, BC=160; fp32: igemm2, BC=160
     (16, 64, 64, 192, 576, 1, 1, 0, False),   # qkv: igemm2, BC=192, K = 192 (3 stages on the two-slot ring: one refill)
@@ -98,6 +102,10 @@ BIG_CONV_CASES = [
     (16, 32, 32, 320, 640, 3, 1, 1, False),   # five channel tiles, GELU epilogue
     (2, 128, 128, 256, 256, 3, 1, 2, True),   # BC=128, SiLU epilogue + residual
 ]
+# (kernel, BP, BC) of the executed plan per case, in fp16 storage; fp32 storage: ("CK_IGEMM2", 128, the same BC).  The halo kernel's BP is its tile width.
+BIG_CONV_PLANS = dict(zip(BIG_CONV_CASES, [
+    ("CK_IGEMM2", 128, 160), ("CK_HALO", 32, 160), ("CK_IGEMM2", 128, 192), ("CK_IGEMM2", 128, 128), ("CK_IGEMM2", 128, 160), ("CK_HALO", 64, 128),
+    ("CK_IGEMM2", 128, 160), ("CK_IGEMM3", 256, 160), ("CK_IGEMM3", 256, 160), ("CK_HALO", 32, 128), ("CK_HALO", 64, 128)]))
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.float32])
@@ -125,8 +133,10 @@ def test_conv_igemm2_large(gpu, dtype, case):
     if use_res:
         res_d = _nhwc(torch.randn(ref.shape, generator=g), dtype, gpu)
         ref = ref + _ref_in(res_d)
-    y = ops.conv2d(xd, w, b, res=res_d, pad=(k // 2, k // 2), up=up, act=act)
+    y, plan = ops.conv2d(xd, w, b, res=res_d, pad=(k // 2, k // 2), up=up, act=act, return_plan=True)
     torch.cuda.synchronize()
+    want = BIG_CONV_PLANS[case] if dtype == torch.float16 else ("CK_IGEMM2", 128, BIG_CONV_PLANS[case][2])
+    assert (plan.kernel, plan.BP, plan.BC, plan.splitk) == (*want, 1), plan
     _close(y.permute(0, 3, 1, 2), ref, TOL[dtype], f"big conv {case} {dtype}")
 
 
@@ -158,8 +168,9 @@ def test_conv_concat_two_sources(gpu, dtype):
     b = torch.randn(320, generator=g)
     d0, d1 = _nhwc(x0, dtype, gpu), _nhwc(x1, dtype, gpu)
     ref = F.conv2d(torch.cat([_ref_in(d0), _ref_in(d1)], 1), w.to(dtype).float(), b, padding=1)
-    y = ops.conv2d(d0, w, b, x1=d1)
+    y, plan = ops.conv2d(d0, w, b, x1=d1, return_plan=True)
     torch.cuda.synchronize()
+    assert plan.kernel == "CK_IGEMM" and plan.splitk > 1, plan   # two sources: the first-generation kernel alone gathers them (with split-K here)
     _close(y.permute(0, 3, 1, 2), ref, TOL[dtype], "concat conv")
 
 
@@ -507,10 +518,14 @@ SPLIT_CONV_CASES = CONV_CASES + [
     (4, 64, 64, 192, 576, 1, 1, (0, 0), 1, 0, False, False),
     (4, 64, 64, 192, 768, 1, 1, (0, 0), 1, 1, False, False),
     (9, 60, 52, 160, 320, 3, 1, (1, 1), 1, 2, True, False),
-    (2, 64, 64, 160, 3, 3, 1, (1, 1), 1, 0, False, False),     # out head: Cout = 3 -> 64-channel tile
+    (2, 64, 64, 160, 3, 3, 1, (1, 1), 1, 0, False, False),     # out head: Cout = 3 (the entry hands Cout <= 8 to the direct kernel: no plan)
     (2, 64, 64, 8, 160, 3, 1, (1, 1), 1, 0, False, False),     # input conv: 8 (zero padded) channels, K = 72
-    (32, 8, 8, 640, 640, 3, 1, (1, 1), 1, 0, True, False),     # 8x8 level at batch 32: 64-pixel tiles + split-K
+    (32, 8, 8, 640, 640, 3, 1, (1, 1), 1, 0, True, False),     # 8x8 level at batch 32: the halo kernel's four-images-per-tile geometry + split-K
 ]
+# the kernel each case is there for: igemm_split.hip, but for the two cases the planner does not give it
+SPLIT_CONV_KERNEL = {c: "CK_SPLIT" for c in SPLIT_CONV_CASES}
+SPLIT_CONV_KERNEL[SPLIT_CONV_CASES[-3]] = "CK_NONE"
+SPLIT_CONV_KERNEL[SPLIT_CONV_CASES[-1]] = "CK_HALO_SEG"
 
 
 @pytest.mark.parametrize("out_f32", [False, True])
@@ -541,9 +556,11 @@ def test_conv_igemm_split(gpu, case, out_f32):
         r = torch.randn(ref.shape, generator=g)
         res_d = _split(r, gpu)
         ref = ref + r.double()
-    y = ops.conv2d(_split(x, gpu), w, b, res=res_d, stride=stride, pad=pad, out_hw=(ref.shape[2], ref.shape[3]), up=up, act=act,
-                   out_prec=ops.F32 if out_f32 else None)
+    y, plan = ops.conv2d(_split(x, gpu), w, b, res=res_d, stride=stride, pad=pad, out_hw=(ref.shape[2], ref.shape[3]), up=up, act=act,
+                         out_prec=ops.F32 if out_f32 else None, return_plan=True)
     torch.cuda.synchronize()
+    assert plan.kernel == SPLIT_CONV_KERNEL[case], plan
+    assert case != SPLIT_CONV_CASES[-1] or (plan.SEG, plan.splitk > 1) == (8, True), plan
     yf = y.cpu() if out_f32 else _unsplit(y)
     _close(yf.permute(0, 3, 1, 2), ref, TOL_SPLIT, f"split conv {case}")
 
