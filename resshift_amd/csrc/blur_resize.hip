@@ -11,10 +11,8 @@
 //   blur_resize_sparse  beyond: an output reads four blurred samples that its neighbours do not.  A workgroup owns 8 x 8 outputs: the 16
 //                       rows {y0, y1} x 16 columns {x0, x1} they read are 256 blurred samples, one per thread, taps straight from global
 //                       memory.
-//   bilinear_kernel     kernels == NULL: rs_interp's bilinear branch, one thread per output.
-#include "launchers.h"
-#include <algorithm>
-#include <string>
+// kernels == NULL is rs_interp's own bilinear launch (rs_interp_launch, degrade.hip).
+#include "image_common.h"
 
 constexpr int BR_KMAX = 41;
 constexpr int BR_THREADS = 256;
@@ -27,35 +25,8 @@ constexpr int BR_PITCH = BR_CMAX + BR_KMAX - 1;
 constexpr int BR_ROWS = BR_RMAX + BR_KMAX - 1 + 3;                    // (+ 3: the last thread's four rows may overhang the block)
 constexpr int BR_SP = 8;                                              // sparse: 8 x 8 outputs
 
-struct BrAxis {
-    double step;   // source pixels per output pixel: n / m
-    int n, m;      // input and output length
-};
-
-__device__ __forceinline__ int br_reflect(int q, int n) {
-    if (q < 0) q = -q;
-    return q < n ? q : 2 * (n - 1) - q;
-}
-
-// rs_interp's bilinear source: the first tap (clamped), the second, and the fraction rounded to fp32 once
-__device__ __forceinline__ void br_source(const BrAxis& ax, int i, int* i0, int* i1, float* frac) {
-    double s = ax.step * ((double)i + 0.5) - 0.5;
-    if (s < 0.0) s = 0.0;
-    const double f = floor(s);
-    *frac = (float)(s - f);
-    *i0 = min((int)f, ax.n - 1);
-    *i1 = min(*i0 + 1, ax.n - 1);
-}
-
-__device__ __forceinline__ float br_bilinear(float v00, float v01, float v10, float v11, float ty, float tx, int clamp) {
-    const float top = fmaf(tx, v01, (1.0f - tx) * v00);
-    const float bot = fmaf(tx, v11, (1.0f - tx) * v10);
-    const float v = fmaf(ty, bot, (1.0f - ty) * top);
-    return clamp ? fminf(fmaxf(v, 0.0f), 1.0f) : v;
-}
-
 __global__ __launch_bounds__(BR_THREADS) void blur_resize_dense(const float* __restrict__ in, const float* __restrict__ kern, float* __restrict__ out,
-                                                                BrAxis ah, BrAxis aw, int C, int k, int per_image, int toy, int tox, int tiles_x,
+                                                                ImgAxis ah, ImgAxis aw, int C, int k, int per_image, int toy, int tox, int tiles_x,
                                                                 int tiles_y, long long total, int clamp) {
     __shared__ float tile[BR_ROWS * BR_PITCH];
     __shared__ float blur[BR_RMAX * BR_CMAX];
@@ -71,19 +42,14 @@ __global__ __launch_bounds__(BR_THREADS) void blur_resize_dense(const float* __r
         const int ny = min(toy, Ho - oy0), nx = min(tox, Wo - ox0);
         int ylo, yhi, xlo, xhi, unused;
         float fr;
-        br_source(ah, oy0, &ylo, &unused, &fr);
-        br_source(ah, oy0 + ny - 1, &unused, &yhi, &fr);
-        br_source(aw, ox0, &xlo, &unused, &fr);
-        br_source(aw, ox0 + nx - 1, &unused, &xhi, &fr);
+        img_source2(ah, oy0, &ylo, &unused, &fr);
+        img_source2(ah, oy0 + ny - 1, &unused, &yhi, &fr);
+        img_source2(aw, ox0, &xlo, &unused, &fr);
+        img_source2(aw, ox0 + nx - 1, &unused, &xhi, &fr);
         const int R = min(yhi - ylo + 1, BR_RMAX), Cn = min(xhi - xlo + 1, BR_CMAX);   // (the launcher's tile keeps them inside)
         const float* inp = in + plane * H * W;
         const float* kp = kern + (per_image ? (plane / C) * k * k : 0);
-        for (int i = tid; i < k * k; i += BR_THREADS) wk[i] = kp[i];
-        const int sr = R + k - 1, sc = Cn + k - 1;
-        for (int i = tid; i < sr * sc; i += BR_THREADS) {
-            const int y = i / sc, x = i - y * sc;
-            tile[y * BR_PITCH + x] = inp[(long long)br_reflect(ylo - p + y, H) * W + br_reflect(xlo - p + x, W)];
-        }
+        img_stage_footprint(inp, kp, tile, wk, BR_PITCH, ylo, xlo, R, Cn, k, p, H, W, tid, BR_THREADS);
         __syncthreads();
         const int groups = (R + 3) / 4;
         for (int i = tid; i < Cn * groups; i += BR_THREADS) {
@@ -105,18 +71,18 @@ __global__ __launch_bounds__(BR_THREADS) void blur_resize_dense(const float* __r
             const int ly = i / nx, lx = i - ly * nx;
             int y0, y1, x0, x1;
             float fy, fx;
-            br_source(ah, oy0 + ly, &y0, &y1, &fy);
-            br_source(aw, ox0 + lx, &x0, &x1, &fx);
+            img_source2(ah, oy0 + ly, &y0, &y1, &fy);
+            img_source2(aw, ox0 + lx, &x0, &x1, &fx);
             y0 = min(y0 - ylo, R - 1); y1 = min(y1 - ylo, R - 1); x0 = min(x0 - xlo, Cn - 1); x1 = min(x1 - xlo, Cn - 1);
             out[plane * Ho * Wo + (long long)(oy0 + ly) * Wo + ox0 + lx] =
-                br_bilinear(blur[y0 * BR_CMAX + x0], blur[y0 * BR_CMAX + x1], blur[y1 * BR_CMAX + x0], blur[y1 * BR_CMAX + x1], fy, fx, clamp);
+                img_unit_clamp(img_bilinear(blur[y0 * BR_CMAX + x0], blur[y0 * BR_CMAX + x1], blur[y1 * BR_CMAX + x0], blur[y1 * BR_CMAX + x1], fy, fx), clamp);
         }
         __syncthreads();   // (the next tile of this workgroup overwrites the LDS images)
     }
 }
 
 __global__ __launch_bounds__(BR_THREADS) void blur_resize_sparse(const float* __restrict__ in, const float* __restrict__ kern, float* __restrict__ out,
-                                                                 BrAxis ah, BrAxis aw, int C, int k, int per_image, int tiles_x, int tiles_y,
+                                                                 ImgAxis ah, ImgAxis aw, int C, int k, int per_image, int tiles_x, int tiles_y,
                                                                  long long total, int clamp) {
     __shared__ float blur[2 * BR_SP][2 * BR_SP];
     __shared__ float wk[BR_KMAX * BR_KMAX];
@@ -135,14 +101,14 @@ __global__ __launch_bounds__(BR_THREADS) void blur_resize_sparse(const float* __
         __syncthreads();
         int a0, a1;
         float fr;
-        br_source(ah, min(oy0 + (ry >> 1), Ho - 1), &a0, &a1, &fr);   // (outputs past the edge repeat the last one and are not stored)
+        img_source2(ah, min(oy0 + (ry >> 1), Ho - 1), &a0, &a1, &fr);   // (outputs past the edge repeat the last one and are not stored)
         const int y = (ry & 1) ? a1 : a0;
-        br_source(aw, min(ox0 + (rx >> 1), Wo - 1), &a0, &a1, &fr);
+        img_source2(aw, min(ox0 + (rx >> 1), Wo - 1), &a0, &a1, &fr);
         const int x = (rx & 1) ? a1 : a0;
         float acc = 0.f;
         for (int ky = 0; ky < k; ++ky) {
-            const float* row = inp + (long long)br_reflect(y - p + ky, H) * W;
-            for (int kx = 0; kx < k; ++kx) acc = fmaf(wk[ky * k + kx], row[br_reflect(x - p + kx, W)], acc);
+            const float* row = inp + (long long)img_reflect(y - p + ky, H) * W;
+            for (int kx = 0; kx < k; ++kx) acc = fmaf(wk[ky * k + kx], row[img_reflect(x - p + kx, W)], acc);
         }
         blur[ry][rx] = acc;
         __syncthreads();
@@ -151,66 +117,37 @@ __global__ __launch_bounds__(BR_THREADS) void blur_resize_sparse(const float* __
             if (oy0 + ly < Ho && ox0 + lx < Wo) {
                 int u0, u1;
                 float fy, fx;
-                br_source(ah, oy0 + ly, &u0, &u1, &fy);
-                br_source(aw, ox0 + lx, &u0, &u1, &fx);
+                img_source2(ah, oy0 + ly, &u0, &u1, &fy);
+                img_source2(aw, ox0 + lx, &u0, &u1, &fx);
                 out[plane * Ho * Wo + (long long)(oy0 + ly) * Wo + ox0 + lx] =
-                    br_bilinear(blur[2 * ly][2 * lx], blur[2 * ly][2 * lx + 1], blur[2 * ly + 1][2 * lx], blur[2 * ly + 1][2 * lx + 1], fy, fx, clamp);
+                    img_unit_clamp(img_bilinear(blur[2 * ly][2 * lx], blur[2 * ly][2 * lx + 1], blur[2 * ly + 1][2 * lx], blur[2 * ly + 1][2 * lx + 1], fy, fx), clamp);
             }
         }
         __syncthreads();   // (the next tile of this workgroup overwrites the LDS images)
     }
 }
 
-// (a thread forms the fp64 coordinates of its position once and applies them to BR_PLANES planes, as rs_interp's bilinear branch does)
-constexpr int BR_PLANES = 8;
-
-__global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__ in, float* __restrict__ out, BrAxis ah, BrAxis aw, long long planes, int clamp) {
-    const int H = ah.n, W = aw.n, Ho = ah.m, Wo = aw.m;
-    const int ox = blockIdx.x * 64 + threadIdx.x;
-    if (ox >= Wo) return;
-    int x0, x1;
-    float fx;
-    br_source(aw, ox, &x0, &x1, &fx);
-    const long long HW = (long long)H * W, HWo = (long long)Ho * Wo;
-    for (int oy = blockIdx.y * 4 + threadIdx.y; oy < Ho; oy += gridDim.y * 4) {
-        int y0, y1;
-        float fy;
-        br_source(ah, oy, &y0, &y1, &fy);
-        const long long r0 = (long long)y0 * W, r1 = (long long)y1 * W;
-        for (long long p0 = (long long)blockIdx.z * BR_PLANES; p0 < planes; p0 += (long long)gridDim.z * BR_PLANES) {
-            const int np = (int)min((long long)BR_PLANES, planes - p0);
-            const float* inp = in + p0 * HW;
-            float* outp = out + p0 * HWo + (long long)oy * Wo + ox;
-            for (int p = 0; p < np; ++p, inp += HW, outp += HWo) *outp = br_bilinear(inp[r0 + x0], inp[r0 + x1], inp[r1 + x0], inp[r1 + x1], fy, fx, clamp);
-        }
-    }
-}
-
 extern "C" int rs_blur_resize(const float* in, const float* kernels, float* out, int B, int C, int H, int W, int Ho, int Wo, int k, int Bk, int clamp,
                               void* stream) {
     const std::string who = "rs_blur_resize: ";
-    if (!in || !out) return rs_set_last_error((who + "null tensor (in / out)").c_str(), -2);
-    if (B < 1 || C < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1) return rs_set_last_error((who + "B, C, H, W, Ho and Wo must be positive").c_str(), -2);
-    if (!kernels && k != 0) return rs_set_last_error((who + "without kernels k must be 0").c_str(), -2);
+    if (!in || !out) return img_fail(who, "null tensor (in / out)");
+    if (B < 1 || C < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1) return img_fail(who, "B, C, H, W, Ho and Wo must be positive");
+    if (!kernels && k != 0) return img_fail(who, "without kernels k must be 0");
     if (kernels) {
-        if (k < 1 || k > BR_KMAX || k % 2 == 0) return rs_set_last_error((who + "k must be odd and at most 41").c_str(), -2);
-        if (k / 2 >= std::min(H, W)) return rs_set_last_error((who + "k / 2 must be below min(H, W) (one reflection per border)").c_str(), -2);
-        if (Bk != 1 && Bk != B) return rs_set_last_error((who + "Bk must be 1 (one kernel for the batch) or B (one per image)").c_str(), -2);
+        if (k < 1 || k > BR_KMAX || k % 2 == 0) return img_fail(who, "k must be odd and at most 41");
+        if (k / 2 >= std::min(H, W)) return img_fail(who, "k / 2 must be below min(H, W) (one reflection per border)");
+        if (Bk != 1 && Bk != B) return img_fail(who, "Bk must be 1 (one kernel for the batch) or B (one per image)");
     }
-    if (clamp != 0 && clamp != 1) return rs_set_last_error((who + "clamp must be 0 or 1").c_str(), -2);
-    if (std::max(std::max(H, W), std::max(Ho, Wo)) > (1 << 28) || (long long)H * W > (1LL << 40) || (long long)Ho * Wo > (1LL << 40))
-        return rs_set_last_error((who + "a plane is too large (a side above 2^28 or more than 2^40 pixels)").c_str(), -2);
+    if (!img_is_flag(clamp)) return img_fail(who, "clamp must be 0 or 1");
+    if (!img_plane_fits(H, W) || !img_plane_fits(Ho, Wo)) return img_fail(who, "a plane is too large (a side above 2^28 or more than 2^40 pixels)");
     const double sh = (double)Ho / H, sw = (double)Wo / W;
-    if (!(sh >= 1.0 / 64 && sh <= 64.0) || !(sw >= 1.0 / 64 && sw <= 64.0)) return rs_set_last_error((who + "the scales Ho / H and Wo / W must lie in [1/64, 64]").c_str(), -2);
+    if (!(sh >= 1.0 / 64 && sh <= 64.0) || !(sw >= 1.0 / 64 && sw <= 64.0)) return img_fail(who, "the scales Ho / H and Wo / W must lie in [1/64, 64]");
     const long long planes = (long long)B * C;
-    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (uintptr_t)(planes * H * W) * sizeof(float), o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(planes * Ho * Wo) * sizeof(float);
-    if (o0 < i1 && i0 < o1) return rs_set_last_error((who + "`out` overlaps `in` (not in place)").c_str(), -2);
-    const BrAxis ah{(double)H / Ho, H, Ho}, aw{(double)W / Wo, W, Wo};
+    if (img_overlaps(in, planes * H * W * sizeof(float), out, planes * Ho * Wo * sizeof(float))) return img_fail(who, "`out` overlaps `in` (not in place)");
+    const ImgAxis ah{(double)H / Ho, H, Ho}, aw{(double)W / Wo, W, Wo};
     const hipStream_t st = (hipStream_t)stream;
-    if (!kernels) {
-        const dim3 grid((unsigned)((Wo + 63) / 64), (unsigned)std::min((Ho + 3) / 4, 65535), (unsigned)std::min<long long>((planes + BR_PLANES - 1) / BR_PLANES, 65535));
-        hipLaunchKernelGGL(bilinear_kernel, grid, dim3(64, 4), 0, st, in, out, ah, aw, planes, clamp);
-    } else if (ah.step <= BR_SWITCH_STEP && aw.step <= BR_SWITCH_STEP && std::max(ah.step, aw.step) <= BR_RMAX - 2) {
+    if (!kernels) return rs_interp_launch(in, out, planes, H, W, Ho, Wo, ah.step, aw.step, RS_INTERP_BILINEAR, clamp, st);
+    if (ah.step <= BR_SWITCH_STEP && aw.step <= BR_SWITCH_STEP && std::max(ah.step, aw.step) <= BR_RMAX - 2) {
         // the outputs whose blurred samples span at most BR_RMAX x BR_CMAX: floor(a + step (n - 1)) - floor(a) + 2 <= ceil(step (n - 1)) + 2
         const int toy = std::max(1, std::min(BR_TOY_MAX, (int)((BR_RMAX - 2) / ah.step))), tox = std::max(1, std::min(BR_TOX_MAX, (int)((BR_CMAX - 2) / aw.step)));
         const int tiles_x = (Wo + tox - 1) / tox, tiles_y = (Ho + toy - 1) / toy;

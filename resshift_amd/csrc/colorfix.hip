@@ -7,9 +7,7 @@
 // adain:   out = clamp((sr - mean_sr) * std_lq / std_sr + mean_lq) per (image, channel) plane.  A statistics launch leaves one
 //          (mean, centred sum of squares) pair per 8192-element chunk of every plane; the apply launch merges a plane's pairs in a fixed
 //          order (Chan's update, fp64) and applies the affine.  No E[x^2] - mean^2, no floating-point atomics.
-#include "launchers.h"
-#include <algorithm>
-#include <string>
+#include "image_common.h"
 
 // ---- wavelet -------------------------------------------------------------------------------------------------------------------
 // LDS image of a tile: rows / columns [tile origin - 31, tile origin + 64 + 31) of the plane, local index = global index - origin; only
@@ -35,15 +33,12 @@ constexpr int CF_LDS_BYTES = 2 * CF_R * CF_PITCH * (int)sizeof(float);
 // scalings are exact, so the value is a function of the three inputs alone
 __device__ __forceinline__ float cf_121(float a, float b, float c) { return fmaf(0.25f, a + c, 0.5f * b); }
 
-__device__ __forceinline__ float cf_cubic1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
-__device__ __forceinline__ float cf_cubic2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
 // tap weights and first tap index of output coordinate o (bicubic_up_kernel's expressions, elementwise.hip)
 __device__ __forceinline__ int cf_bicubic_taps(int o, float rs, float* w) {
-    const float A = -0.75f;
     const float f = ((float)o + 0.5f) * rs - 0.5f;
     const float ff = floorf(f);
     const float t = f - ff;
-    w[0] = cf_cubic2(t + 1.f, A); w[1] = cf_cubic1(t, A); w[2] = cf_cubic1(1.f - t, A); w[3] = cf_cubic2(2.f - t, A);
+    img_cubic_weights(t, w);
     return (int)ff - 1;
 }
 
@@ -337,19 +332,17 @@ int rs_color_fix(const float* sr, const float* lq, float* out, int B, int C, int
                  void* stream) {
     static RsAttrFlags attr_flags;
     const std::string who = "rs_color_fix: ";
-    if (!sr || !lq || !out) return rs_set_last_error((who + "null tensor (sr / lq / out)").c_str(), -2);
-    if (const char* e = cf_geometry_error(B, C, H, W, sf, mode)) return rs_set_last_error((who + e).c_str(), -2);
+    if (!sr || !lq || !out) return img_fail(who, "null tensor (sr / lq / out)");
+    if (const char* e = cf_geometry_error(B, C, H, W, sf, mode)) return img_fail(who, e);
     const long long planes = (long long)B * C, n_lq = (long long)H * W, n_sr = n_lq * sf * sf;
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(planes * n_sr) * sizeof(float);
-    const uintptr_t s0 = (uintptr_t)sr, s1 = s0 + (uintptr_t)(planes * n_sr) * sizeof(float);
-    const uintptr_t l0 = (uintptr_t)lq, l1 = l0 + (uintptr_t)(planes * n_lq) * sizeof(float);
-    if ((o0 < s1 && s0 < o1) || (o0 < l1 && l0 < o1))
-        return rs_set_last_error((who + "`out` overlaps `sr` or `lq` (workgroups read their neighbours' pixels of sr: not in place)").c_str(), -2);
+    const size_t sr_bytes = planes * n_sr * sizeof(float);
+    if (img_overlaps(out, sr_bytes, sr, sr_bytes) || img_overlaps(out, sr_bytes, lq, planes * n_lq * sizeof(float)))
+        return img_fail(who, "`out` overlaps `sr` or `lq` (workgroups read their neighbours' pixels of sr: not in place)");
     const size_t need = rs_color_fix_work_bytes(B, C, H, W, sf, mode);
     if (need && (!work || work_bytes < need))
-        return rs_set_last_error((who + "the workspace is too small: " + std::to_string(work ? work_bytes : 0) + " bytes, rs_color_fix_work_bytes asks for " +
-                                  std::to_string(need)).c_str(), -2);
-    if (need && ((uintptr_t)work & 3)) return rs_set_last_error((who + "the workspace must be aligned to 4 bytes").c_str(), -2);
+        return img_fail(who, "the workspace is too small: " + std::to_string(work ? work_bytes : 0) + " bytes, rs_color_fix_work_bytes asks for " +
+                                  std::to_string(need));
+    if (need && ((uintptr_t)work & 3)) return img_fail(who, "the workspace must be aligned to 4 bytes");
     const hipStream_t st = (hipStream_t)stream;
     if (mode == RS_COLOR_FIX_WAVELET) {
         const int tiles_x = (W * sf + CF_TILE - 1) / CF_TILE, tiles_y = (H * sf + CF_TILE - 1) / CF_TILE;

@@ -7,16 +7,15 @@
 //                    of 256 threads owns a 16 x 64 output tile of one plane: it stages the mirrored (16 + k - 1) x (64 + k - 1) input
 //                    tile and the image's kernel in LDS; lanes run along columns (consecutive dwords of LDS, the weight is a broadcast),
 //                    a thread owns four rows of one column, taps accumulate in row-major ascending order.
-//   interp_kernel    F.interpolate(mode = area | bilinear | bicubic, align_corners=False), one thread per output value, lanes along a row; source
+//   interp_kernel    F.interpolate(mode = area | bicubic, align_corners=False), one thread per output value, lanes along a row; source
 //                    coordinates in fp64, rounded to fp32 once.
+//   interp_bilinear_kernel  mode = bilinear: a thread applies the coordinates of its position to eight planes.
 //   jpeg_kernel      basicsr/utils/diffjpeg.py DiffJPEG(differentiable=False).  ONE WAVE PER 16 x 16 MCU, four MCUs per workgroup.  Lane
 //                    l owns the 2 x 2 pixel quad (l / 8, l % 8) at both ends - the chroma mean and the pixel repetition stay in the
 //                    lane - and the coefficient (l / 8, l % 8) of each of the MCU's six 8 x 8 blocks in between; the blocks live in
 //                    two LDS images per wave, pitched 9 dwords per row of 8.
-#include "launchers.h"
-#include <algorithm>
+#include "image_common.h"
 #include <cmath>
-#include <string>
 
 // ---- filter2D ------------------------------------------------------------------------------------------------------------------
 constexpr int FL_TR = 16;
@@ -24,12 +23,6 @@ constexpr int FL_TC = 64;
 constexpr int FL_THREADS = 256;
 constexpr int FL_KMAX = 21;
 constexpr int FL_PITCH = FL_TC + FL_KMAX - 1;   // 84 dwords: lanes read consecutive dwords of one row
-
-// torch's `reflect`: the edge sample is not repeated; one reflection is enough for |overhang| < n
-__device__ __forceinline__ int fl_reflect(int q, int n) {
-    if (q < 0) q = -q;
-    return q < n ? q : 2 * (n - 1) - q;
-}
 
 __global__ __launch_bounds__(FL_THREADS) void filter2d_kernel(const float* __restrict__ in, const float* __restrict__ kern, float* __restrict__ out,
                                                               int C, int H, int W, int k, int per_image, int tiles_x, int tiles_y,
@@ -47,12 +40,7 @@ __global__ __launch_bounds__(FL_THREADS) void filter2d_kernel(const float* __res
         const int nr = min(FL_TR, H - oy0), nc = min(FL_TC, W - ox0);
         const float* inp = in + plane * H * W;
         const float* kp = kern + (per_image ? (plane / C) * k * k : 0);
-        for (int i = tid; i < k * k; i += FL_THREADS) wk[i] = kp[i];
-        const int sr = nr + k - 1, sc = nc + k - 1;      // staged rows / columns: the sources reach at most p past the image
-        for (int i = tid; i < sr * sc; i += FL_THREADS) {
-            const int y = i / sc, x = i - y * sc;
-            tile[y * FL_PITCH + x] = inp[(long long)fl_reflect(oy0 - p + y, H) * W + fl_reflect(ox0 - p + x, W)];
-        }
+        img_stage_footprint(inp, kp, tile, wk, FL_PITCH, oy0, ox0, nr, nc, k, p, H, W, tid, FL_THREADS);
         __syncthreads();
         if (c < nc) {
             float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -66,11 +54,7 @@ __global__ __launch_bounds__(FL_THREADS) void filter2d_kernel(const float* __res
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int r = r0 + 4 * j;
-                if (r < nr) {
-                    float v = acc[j];
-                    if (clamp) v = fminf(fmaxf(v, 0.0f), 1.0f);
-                    out[plane * H * W + (long long)(oy0 + r) * W + ox0 + c] = v;
-                }
+                if (r < nr) out[plane * H * W + (long long)(oy0 + r) * W + ox0 + c] = img_unit_clamp(acc[j], clamp);
             }
         }
         __syncthreads();   // (the next tile of this workgroup overwrites the LDS images)
@@ -78,98 +62,69 @@ __global__ __launch_bounds__(FL_THREADS) void filter2d_kernel(const float* __res
 }
 
 // ---- F.interpolate -------------------------------------------------------------------------------------------------------------
-enum { IP_AREA = 0, IP_BILINEAR = 1, IP_BICUBIC = 2 };
-
-struct IpAxis {
-    double step;   // source pixels per output pixel: 1 / scale_factor when a scale factor was given, n / m for a size
-    int n, m;      // input and output length
-};
-
-// Keys' cubic with A = -0.75: the four weights of the taps floor(src) - 1 .. floor(src) + 2 for the fraction t
-__device__ __forceinline__ void ip_cubic(float t, float w[4]) {
-    const float A = -0.75f;
-    const float x0 = t + 1.0f, x3 = 2.0f - t, x2 = 1.0f - t;
-    w[0] = ((A * x0 - 5.0f * A) * x0 + 8.0f * A) * x0 - 4.0f * A;
-    w[1] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
-    w[2] = ((A + 2.0f) * x2 - (A + 3.0f)) * x2 * x2 + 1.0f;
-    w[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
-}
-
-// source coordinate of output index i (fp64), its floor, and the fraction rounded to fp32 once
-__device__ __forceinline__ int ip_source(const IpAxis& ax, int i, bool clamp0, float* frac) {
-    double s = ax.step * ((double)i + 0.5) - 0.5;
-    if (clamp0 && s < 0.0) s = 0.0;
-    const double f = floor(s);
-    *frac = (float)(s - f);
-    return (int)f;
-}
-
-// A workgroup of 64 x 4 threads owns 64 columns of 4 output rows (no index division).  A thread forms the coordinates, tap indices and
-// weights of its output position ONCE and applies them to PP planes of blockIdx.z's share: they depend on the position only.  Measured
-// (scripts/degrade_bench.py, B = 32, 512 x 512): eight planes per thread take bilinear x 1.3 from 133 to 78 us - four taps, the fp64
-// coordinates are half of its work - and bicubic x 0.6 from 65 to 114 us, area / 4 from 27 to 34 us (sixteen gathers resp. a 4 x 4 window
-// per plane: fewer threads in flight cost more than the coordinates save), so bilinear gets eight planes per thread and the others one.
-constexpr int IP_PLANES_BILINEAR = 8;
-
-__device__ __forceinline__ float ip_finish(float v, int clamp) { return clamp ? fminf(fmaxf(v, 0.0f), 1.0f) : v; }
-
-template <int PP>
-__global__ __launch_bounds__(256) void interp_kernel(const float* __restrict__ in, float* __restrict__ out, IpAxis ah, IpAxis aw, long long planes,
+// A workgroup of 64 x 4 threads owns 64 columns of 4 output rows (no index division); a thread forms the coordinates, tap indices and
+// weights of its output position, which depend on the position only.  Area and bicubic: one plane per thread (interp_kernel).  Bilinear:
+// four taps, the fp64 coordinates are half of its work, so a thread forms the column's ONCE, a row's once per row, and applies them to
+// eight planes of blockIdx.z's share (interp_bilinear_kernel).  Measured (scripts/degrade_bench.py, B = 32, 512 x 512): eight planes per thread
+// take bilinear x 1.3 from 133 to 78 us, but bicubic x 0.6 from 65 to 114 us and area / 4 from 27 to 34 us (sixteen gathers resp. a 4 x 4
+// window per plane: fewer threads in flight cost more than the coordinates save).
+__global__ __launch_bounds__(256) void interp_kernel(const float* __restrict__ in, float* __restrict__ out, ImgAxis ah, ImgAxis aw, long long planes,
                                                      int mode, int clamp) {
     const int H = ah.n, W = aw.n, Ho = ah.m, Wo = aw.m;
     const int ox = blockIdx.x * 64 + threadIdx.x;
     if (ox >= Wo) return;
-    const long long HW = (long long)H * W, HWo = (long long)Ho * Wo;
-    for (long long p0 = (long long)blockIdx.z * PP; p0 < planes; p0 += (long long)gridDim.z * PP) {
-        const int np = PP == 1 ? 1 : (int)min((long long)PP, planes - p0);
+    for (long long plane = blockIdx.z; plane < planes; plane += gridDim.z) {
+        const float* inp = in + plane * H * W;
         for (int oy = blockIdx.y * 4 + threadIdx.y; oy < Ho; oy += gridDim.y * 4) {
-            const float* inp = in + p0 * HW;
-            float* outp = out + p0 * HWo + (long long)oy * Wo + ox;
-            if (mode == IP_AREA) {   // adaptive average pooling: the integer window [floor(i n / m), ceil((i + 1) n / m)), summed in row-major order
+            float* outp = out + plane * Ho * Wo + (long long)oy * Wo + ox;
+            if (mode == RS_INTERP_AREA) {   // adaptive average pooling: the integer window [floor(i n / m), ceil((i + 1) n / m)), summed in row-major order
                 const int y0 = (int)(((long long)oy * H) / Ho), y1 = (int)((((long long)oy + 1) * H + Ho - 1) / Ho);
                 const int x0 = (int)(((long long)ox * W) / Wo), x1 = (int)((((long long)ox + 1) * W + Wo - 1) / Wo);
-                const float cnt = (float)((y1 - y0) * (x1 - x0));
-                for (int p = 0; p < np; ++p, inp += HW, outp += HWo) {
-                    float sum = 0.f;
-                    for (int y = y0; y < y1; ++y)
-                        for (int x = x0; x < x1; ++x) sum += inp[(long long)y * W + x];
-                    *outp = ip_finish(sum / cnt, clamp);
-                }
-            } else if (mode == IP_BILINEAR) {
-                float ty, tx;
-                const int y0 = min(ip_source(ah, oy, true, &ty), H - 1), x0 = min(ip_source(aw, ox, true, &tx), W - 1);
-                const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
-                const float wy0 = 1.0f - ty, wx0 = 1.0f - tx;
-                const long long r0 = (long long)y0 * W, r1 = (long long)y1 * W;
-                for (int p = 0; p < np; ++p, inp += HW, outp += HWo) {
-                    const float top = fmaf(tx, inp[r0 + x1], wx0 * inp[r0 + x0]);
-                    const float bot = fmaf(tx, inp[r1 + x1], wx0 * inp[r1 + x0]);
-                    *outp = ip_finish(fmaf(ty, bot, wy0 * top), clamp);
-                }
+                float sum = 0.f;
+                for (int y = y0; y < y1; ++y)
+                    for (int x = x0; x < x1; ++x) sum += inp[(long long)y * W + x];
+                *outp = img_unit_clamp(sum / (float)((y1 - y0) * (x1 - x0)), clamp);
             } else {
                 float ty, tx, wy[4], wx[4];
-                const int y0 = ip_source(ah, oy, false, &ty), x0 = ip_source(aw, ox, false, &tx);
-                ip_cubic(ty, wy);
-                ip_cubic(tx, wx);
-                long long ro[4];
-                int xo[4];
+                const int y0 = img_source(ah, oy, false, &ty), x0 = img_source(aw, ox, false, &tx);
+                img_cubic_weights(ty, wy);
+                img_cubic_weights(tx, wx);
+                float v = 0.f;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    ro[j] = (long long)min(max(y0 - 1 + j, 0), H - 1) * W;
-                    xo[j] = min(max(x0 - 1 + j, 0), W - 1);
-                }
-                for (int p = 0; p < np; ++p, inp += HW, outp += HWo) {
-                    float v = 0.f;
+                    const float* row = inp + (long long)min(max(y0 - 1 + j, 0), H - 1) * W;
+                    float s = 0.f;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float s = 0.f;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) s = fmaf(wx[i], inp[ro[j] + xo[i]], s);
-                        v = fmaf(wy[j], s, v);
-                    }
-                    *outp = ip_finish(v, clamp);
+                    for (int i = 0; i < 4; ++i) s = fmaf(wx[i], row[min(max(x0 - 1 + i, 0), W - 1)], s);
+                    v = fmaf(wy[j], s, v);
                 }
+                *outp = img_unit_clamp(v, clamp);
             }
+        }
+    }
+}
+
+constexpr int IP_PLANES_BILINEAR = 8;
+
+__global__ __launch_bounds__(256) void interp_bilinear_kernel(const float* __restrict__ in, float* __restrict__ out, ImgAxis ah, ImgAxis aw, long long planes, int clamp) {
+    const int H = ah.n, W = aw.n, Ho = ah.m, Wo = aw.m;
+    const int ox = blockIdx.x * 64 + threadIdx.x;
+    if (ox >= Wo) return;
+    int x0, x1;
+    float fx;
+    img_source2(aw, ox, &x0, &x1, &fx);
+    const long long HW = (long long)H * W, HWo = (long long)Ho * Wo;
+    for (int oy = blockIdx.y * 4 + threadIdx.y; oy < Ho; oy += gridDim.y * 4) {
+        int y0, y1;
+        float fy;
+        img_source2(ah, oy, &y0, &y1, &fy);
+        const long long r0 = (long long)y0 * W, r1 = (long long)y1 * W;
+        for (long long p0 = (long long)blockIdx.z * IP_PLANES_BILINEAR; p0 < planes; p0 += (long long)gridDim.z * IP_PLANES_BILINEAR) {
+            const int np = (int)min((long long)IP_PLANES_BILINEAR, planes - p0);
+            const float* inp = in + p0 * HW;
+            float* outp = out + p0 * HWo + (long long)oy * Wo + ox;
+            for (int p = 0; p < np; ++p, inp += HW, outp += HWo)
+                *outp = img_unit_clamp(img_bilinear(inp[r0 + x0], inp[r0 + x1], inp[r1 + x0], inp[r1 + x1], fy, fx), clamp);
         }
     }
 }
@@ -322,23 +277,29 @@ __global__ __launch_bounds__(64 * JP_WAVES) void jpeg_kernel(const float* __rest
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------------
 extern "C" {
 
-static bool dg_overlap(const void* a, long long na, const void* b, long long nb) {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)na * sizeof(float), b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)nb * sizeof(float);
-    return b0 < a1 && a0 < b1;
+// the one launch of F.interpolate's kernels: rs_interp's, and rs_blur_resize's (bilinear) when it has no kernel.  The callers have checked.
+int rs_interp_launch(const float* in, float* out, long long planes, int H, int W, int Ho, int Wo, double step_h, double step_w, int mode, int clamp,
+                     hipStream_t st) {
+    const ImgAxis ah{step_h, H, Ho}, aw{step_w, W, Wo};
+    const int pp = mode == RS_INTERP_BILINEAR ? IP_PLANES_BILINEAR : 1;
+    const dim3 grid((unsigned)((Wo + 63) / 64), (unsigned)std::min((Ho + 3) / 4, 65535), (unsigned)std::min<long long>((planes + pp - 1) / pp, 65535));
+    if (mode == RS_INTERP_BILINEAR) hipLaunchKernelGGL(interp_bilinear_kernel, grid, dim3(64, 4), 0, st, in, out, ah, aw, planes, clamp);
+    else hipLaunchKernelGGL(interp_kernel, grid, dim3(64, 4), 0, st, in, out, ah, aw, planes, mode, clamp);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int rs_filter2d(const float* in, const float* kernels, float* out, int B, int C, int H, int W, int k, int Bk, int clamp, void* stream) {
     const std::string who = "rs_filter2d: ";
-    if (!in || !kernels || !out) return rs_set_last_error((who + "null tensor (in / kernels / out)").c_str(), -2);
-    if (B < 1 || C < 1 || H < 1 || W < 1) return rs_set_last_error((who + "B, C, H and W must be positive").c_str(), -2);
-    if (k < 1 || k > FL_KMAX || k % 2 == 0) return rs_set_last_error((who + "k must be odd and at most 21").c_str(), -2);
-    if (k / 2 >= std::min(H, W)) return rs_set_last_error((who + "k / 2 must be below min(H, W) (one reflection per border)").c_str(), -2);
-    if (Bk != 1 && Bk != B) return rs_set_last_error((who + "Bk must be 1 (one kernel for the batch) or B (one per image)").c_str(), -2);
-    if (clamp != 0 && clamp != 1) return rs_set_last_error((who + "clamp must be 0 or 1").c_str(), -2);
-    if (std::max(H, W) > (1 << 28) || (long long)H * W > (1LL << 40)) return rs_set_last_error((who + "a plane is too large (a side above 2^28 or more than 2^40 pixels)").c_str(), -2);
+    if (!in || !kernels || !out) return img_fail(who, "null tensor (in / kernels / out)");
+    if (B < 1 || C < 1 || H < 1 || W < 1) return img_fail(who, "B, C, H and W must be positive");
+    if (k < 1 || k > FL_KMAX || k % 2 == 0) return img_fail(who, "k must be odd and at most 21");
+    if (k / 2 >= std::min(H, W)) return img_fail(who, "k / 2 must be below min(H, W) (one reflection per border)");
+    if (Bk != 1 && Bk != B) return img_fail(who, "Bk must be 1 (one kernel for the batch) or B (one per image)");
+    if (!img_is_flag(clamp)) return img_fail(who, "clamp must be 0 or 1");
+    if (!img_plane_fits(H, W)) return img_fail(who, "a plane is too large (a side above 2^28 or more than 2^40 pixels)");
     const long long planes = (long long)B * C;
-    if (dg_overlap(in, planes * H * W, out, planes * H * W))
-        return rs_set_last_error((who + "`out` overlaps `in` (workgroups read their neighbours' pixels of in: not in place)").c_str(), -2);
+    if (img_overlaps(in, planes * H * W * sizeof(float), out, planes * H * W * sizeof(float)))
+        return img_fail(who, "`out` overlaps `in` (workgroups read their neighbours' pixels of in: not in place)");
     const int tiles_x = (W + FL_TC - 1) / FL_TC, tiles_y = (H + FL_TR - 1) / FL_TR;
     const long long total = planes * tiles_x * tiles_y;
     hipLaunchKernelGGL(filter2d_kernel, dim3((unsigned)std::min<long long>(total, 1 << 20)), dim3(FL_THREADS), 0, (hipStream_t)stream, in, kernels,
@@ -349,52 +310,46 @@ int rs_filter2d(const float* in, const float* kernels, float* out, int B, int C,
 int rs_interp(const float* in, float* out, int B, int C, int H, int W, int Ho, int Wo, double scale_h, double scale_w, int mode, int clamp,
               void* stream) {
     const std::string who = "rs_interp: ";
-    if (!in || !out) return rs_set_last_error((who + "null tensor (in / out)").c_str(), -2);
-    if (B < 1 || C < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1) return rs_set_last_error((who + "B, C, H, W, Ho and Wo must be positive").c_str(), -2);
-    if (mode != IP_AREA && mode != IP_BILINEAR && mode != IP_BICUBIC) return rs_set_last_error((who + "mode must be 0 (area), 1 (bilinear) or 2 (bicubic)").c_str(), -2);
-    if (clamp != 0 && clamp != 1) return rs_set_last_error((who + "clamp must be 0 or 1").c_str(), -2);
-    if (std::max(std::max(H, W), std::max(Ho, Wo)) > (1 << 28) || (long long)H * W > (1LL << 40) || (long long)Ho * Wo > (1LL << 40))
-        return rs_set_last_error((who + "a plane is too large (a side above 2^28 or more than 2^40 pixels)").c_str(), -2);
-    if ((scale_h == 0.0) != (scale_w == 0.0)) return rs_set_last_error((who + "scale_h and scale_w are both 0 (a size was given) or both a scale factor").c_str(), -2);
-    IpAxis ah{0.0, H, Ho}, aw{0.0, W, Wo};
+    if (!in || !out) return img_fail(who, "null tensor (in / out)");
+    if (B < 1 || C < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1) return img_fail(who, "B, C, H, W, Ho and Wo must be positive");
+    if (mode != RS_INTERP_AREA && mode != RS_INTERP_BILINEAR && mode != RS_INTERP_BICUBIC) return img_fail(who, "mode must be 0 (area), 1 (bilinear) or 2 (bicubic)");
+    if (!img_is_flag(clamp)) return img_fail(who, "clamp must be 0 or 1");
+    if (!img_plane_fits(H, W) || !img_plane_fits(Ho, Wo)) return img_fail(who, "a plane is too large (a side above 2^28 or more than 2^40 pixels)");
+    if ((scale_h == 0.0) != (scale_w == 0.0)) return img_fail(who, "scale_h and scale_w are both 0 (a size was given) or both a scale factor");
+    double step_h, step_w;
     if (scale_h == 0.0) {
         const double sh = (double)Ho / H, sw = (double)Wo / W;
-        if (!(sh >= 0.125 && sh <= 8.0) || !(sw >= 0.125 && sw <= 8.0)) return rs_set_last_error((who + "the scales Ho / H and Wo / W must lie in [1/8, 8]").c_str(), -2);
-        ah.step = (double)H / Ho;
-        aw.step = (double)W / Wo;
+        if (!(sh >= 0.125 && sh <= 8.0) || !(sw >= 0.125 && sw <= 8.0)) return img_fail(who, "the scales Ho / H and Wo / W must lie in [1/8, 8]");
+        step_h = (double)H / Ho;
+        step_w = (double)W / Wo;
     } else {
         if (!(scale_h >= 0.125 && scale_h <= 8.0) || !(scale_w >= 0.125 && scale_w <= 8.0))
-            return rs_set_last_error((who + "scale_h and scale_w must lie in [1/8, 8]").c_str(), -2);
+            return img_fail(who, "scale_h and scale_w must lie in [1/8, 8]");
         if ((double)Ho != std::floor((double)H * scale_h) || (double)Wo != std::floor((double)W * scale_w))
-            return rs_set_last_error((who + "with a scale factor the output must be floor(H * scale_h) x floor(W * scale_w)").c_str(), -2);
-        ah.step = 1.0 / scale_h;
-        aw.step = 1.0 / scale_w;
+            return img_fail(who, "with a scale factor the output must be floor(H * scale_h) x floor(W * scale_w)");
+        step_h = 1.0 / scale_h;
+        step_w = 1.0 / scale_w;
     }
-    const long long planes = (long long)B * C, total = planes * Ho * Wo;
-    if (dg_overlap(in, planes * H * W, out, total)) return rs_set_last_error((who + "`out` overlaps `in` (not in place)").c_str(), -2);
-    const int pp = mode == IP_BILINEAR ? IP_PLANES_BILINEAR : 1;
-    const dim3 grid((unsigned)((Wo + 63) / 64), (unsigned)std::min((Ho + 3) / 4, 65535), (unsigned)std::min<long long>((planes + pp - 1) / pp, 65535));
-    if (pp == 1) hipLaunchKernelGGL(interp_kernel<1>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, out, ah, aw, planes, mode, clamp);
-    else hipLaunchKernelGGL(interp_kernel<IP_PLANES_BILINEAR>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, out, ah, aw, planes, mode, clamp);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    const long long planes = (long long)B * C;
+    if (img_overlaps(in, planes * H * W * sizeof(float), out, planes * Ho * Wo * sizeof(float))) return img_fail(who, "`out` overlaps `in` (not in place)");
+    return rs_interp_launch(in, out, planes, H, W, Ho, Wo, step_h, step_w, mode, clamp, (hipStream_t)stream);
 }
 
 int rs_jpeg(const float* in, float* out, const float* quality, int B, int C, int H, int W, void* stream) {
     const std::string who = "rs_jpeg: ";
-    if (!in || !out || !quality) return rs_set_last_error((who + "null pointer (in / out / quality)").c_str(), -2);
-    if (B < 1 || B > RS_MAX_ROWS) return rs_set_last_error((who + "B must be 1 .. RS_MAX_ROWS (the qualities travel by value)").c_str(), -2);
-    if (C != 3) return rs_set_last_error((who + "C must be 3 (RGB)").c_str(), -2);
-    if (H < 1 || W < 1) return rs_set_last_error((who + "H and W must be positive").c_str(), -2);
-    if (std::max(H, W) > (1 << 28) || (long long)H * W > (1LL << 40)) return rs_set_last_error((who + "a plane is too large (a side above 2^28 or more than 2^40 pixels)").c_str(), -2);
+    if (!in || !out || !quality) return img_fail(who, "null pointer (in / out / quality)");
+    if (B < 1 || B > RS_MAX_ROWS) return img_fail(who, "B must be 1 .. RS_MAX_ROWS (the qualities travel by value)");
+    if (C != 3) return img_fail(who, "C must be 3 (RGB)");
+    if (H < 1 || W < 1) return img_fail(who, "H and W must be positive");
+    if (!img_plane_fits(H, W)) return img_fail(who, "a plane is too large (a side above 2^28 or more than 2^40 pixels)");
     JpFactors fac{};
     for (int b = 0; b < B; ++b) {
         const float q = quality[b];
-        if (!(q > 0.0f && q < 100.0f)) return rs_set_last_error((who + "every quality must lie in (0, 100) (at 100 the factor is 0 and the quantiser divides by it)").c_str(), -2);
+        if (!(q > 0.0f && q < 100.0f)) return img_fail(who, "every quality must lie in (0, 100) (at 100 the factor is 0 and the quantiser divides by it)");
         fac.f[b] = (q < 50.0f ? 5000.0f / q : 200.0f - q * 2.0f) / 100.0f;   // fp32, as the reference's tensor arithmetic
     }
     const long long n = (long long)B * 3 * H * W;
-    const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
-    if (i0 != o0 && dg_overlap(in, n, out, n)) return rs_set_last_error((who + "`out` partly overlaps `in` (in place or apart)").c_str(), -2);
+    if (in != out && img_overlaps(in, n * sizeof(float), out, n * sizeof(float))) return img_fail(who, "`out` partly overlaps `in` (in place or apart)");
     const int mcus_x = (W + 15) / 16, mcus_y = (H + 15) / 16;
     const long long total = (long long)B * mcus_x * mcus_y, groups = (total + JP_WAVES - 1) / JP_WAVES;
     hipLaunchKernelGGL(jpeg_kernel, dim3((unsigned)std::min<long long>(groups, 1 << 20)), dim3(64 * JP_WAVES), 0, (hipStream_t)stream, in, out, fac, H, W,

@@ -7,11 +7,9 @@
 //             A=-0.75, border-clamped taps, no antialias).
 //   VQ:       VectorQuantizer2.forward ldm/modules/vqvae/quantize.py:271-312 (expanded-form distance,
 //             first-minimum argmin, straight-through expression z + (z_q - z)).
-#include "launchers.h"
+#include "image_common.h"
 #include "philox.h"
-#include <algorithm>
 #include <cmath>
-#include <string>
 
 namespace {
 
@@ -252,15 +250,11 @@ __global__ __launch_bounds__(256) void small_linear_kernel(const float* x, const
 }
 
 // ---- bicubic ----------------------------------------------------------------
-__device__ __forceinline__ float cubic1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
-__device__ __forceinline__ float cubic2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
-
 // in: NCHW fp32 [B,C,H,W]; out: NHWC TO [B,H*sf,W*sf,ldo] channels [0,C)
 template <typename TO>
 __global__ void bicubic_up_kernel(const float* in, TO* out, int B, int C, int H, int W, int sf, int ldo) {
     const int Ho = H * sf, Wo = W * sf;
     const long long n = (long long)B * Ho * Wo * C;
-    const float A = -0.75f;
     const float rs = 1.0f / (float)sf;
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(g % C);
@@ -273,8 +267,9 @@ __global__ void bicubic_up_kernel(const float* in, TO* out, int B, int C, int H,
         const float fyf = floorf(fy), fxf = floorf(fx);
         const int iy = (int)fyf, ix = (int)fxf;
         const float ty = fy - fyf, tx = fx - fxf;
-        float wy[4] = {cubic2(ty + 1.f, A), cubic1(ty, A), cubic1(1.f - ty, A), cubic2(2.f - ty, A)};
-        float wx[4] = {cubic2(tx + 1.f, A), cubic1(tx, A), cubic1(1.f - tx, A), cubic2(2.f - tx, A)};
+        float wy[4], wx[4];
+        img_cubic_weights(ty, wy);
+        img_cubic_weights(tx, wx);
         const float* src = in + ((long long)b * C + c) * H * W;
         float acc = 0.f;
 #pragma unroll
@@ -662,22 +657,21 @@ int rs_noise_fill(const rs_noise_key* keys, const int* draw, float* out, long lo
 int rs_add_noise(const float* x, float* out, const rs_noise_key* keys, const int* draw, const float* sigma, const int* gray, int B, int C, int H,
                  int W, int clamp, void* stream) {
     const std::string who = "rs_add_noise: ";
-    if (B < 1 || B > RS_MAX_ROWS) return rs_set_last_error((who + "B must be 1 .. RS_MAX_ROWS").c_str(), -2);
-    if (const char* e = noise_keys_error(keys, B)) return rs_set_last_error((who + e).c_str(), -2);
-    if (!x || !out || !draw || !sigma || !gray) return rs_set_last_error((who + "null pointer (x / out / draw / sigma / gray)").c_str(), -2);
-    if (C < 1 || H < 1 || W < 1) return rs_set_last_error((who + "C, H and W must be positive").c_str(), -2);
-    if ((long long)C * H * W > 0x3ffffffffLL) return rs_set_last_error((who + "an image has more than 2^34 - 1 elements").c_str(), -2);
-    if (clamp != 0 && clamp != 1) return rs_set_last_error((who + "clamp must be 0 or 1").c_str(), -2);
+    if (B < 1 || B > RS_MAX_ROWS) return img_fail(who, "B must be 1 .. RS_MAX_ROWS");
+    if (const char* e = noise_keys_error(keys, B)) return img_fail(who, e);
+    if (!x || !out || !draw || !sigma || !gray) return img_fail(who, "null pointer (x / out / draw / sigma / gray)");
+    if (C < 1 || H < 1 || W < 1) return img_fail(who, "C, H and W must be positive");
+    if ((long long)C * H * W > 0x3ffffffffLL) return img_fail(who, "an image has more than 2^34 - 1 elements");
+    if (!img_is_flag(clamp)) return img_fail(who, "clamp must be 0 or 1");
     const long long HW = (long long)H * W, n = (long long)B * C * HW;
-    const uintptr_t x0 = (uintptr_t)x, o0 = (uintptr_t)out, bytes = (uintptr_t)n * sizeof(float);
-    if (x0 != o0 && o0 < x0 + bytes && x0 < o0 + bytes) return rs_set_last_error((who + "`out` partly overlaps `x` (in place or apart)").c_str(), -2);
+    if (x != out && img_overlaps(x, n * sizeof(float), out, n * sizeof(float))) return img_fail(who, "`out` partly overlaps `x` (in place or apart)");
     NoiseRows k{};
     RowKeys nk{};
     bool any_color = false;
     for (int b = 0; b < B; ++b) {
-        if (draw[b] < 0) return rs_set_last_error((who + "negative draw index").c_str(), -2);
-        if (!(sigma[b] >= 0.0f) || !std::isfinite(sigma[b])) return rs_set_last_error((who + "every sigma must be finite and not negative").c_str(), -2);
-        if (gray[b] != 0 && gray[b] != 1) return rs_set_last_error((who + "every gray flag must be 0 or 1").c_str(), -2);
+        if (draw[b] < 0) return img_fail(who, "negative draw index");
+        if (!(sigma[b] >= 0.0f) || !std::isfinite(sigma[b])) return img_fail(who, "every sigma must be finite and not negative");
+        if (!img_is_flag(gray[b])) return img_fail(who, "every gray flag must be 0 or 1");
         k.c[b] = (float)((double)sigma[b] / 255.0);
         k.gray[b] = (unsigned char)gray[b];
         any_color |= gray[b] == 0;

@@ -12,9 +12,7 @@
 //      dequantise, inverse DCT, with no transposes and no barriers in between.  The tile has 128 Y blocks and, with the ring, 120
 //      chroma blocks: 248 of the 256 threads, so the ring costs no time of its own.
 //   3. pixels: a thread per output pixel, lanes along a row: triangle up-sampling from the chroma planes, YCbCr -> RGB, / 255.
-#include "launchers.h"
-#include <algorithm>
-#include <string>
+#include "image_common.h"
 
 constexpr int JC_TX = 8, JC_TY = 4;                          // MCUs of a tile
 constexpr int JC_THREADS = 256;
@@ -241,19 +239,18 @@ __global__ __launch_bounds__(JC_THREADS) void jpeg_codec_kernel(const float* __r
 
 extern "C" int rs_jpeg_codec(const float* in, float* out, const int* quality, int B, int C, int H, int W, void* stream) {
     const std::string who = "rs_jpeg_codec: ";
-    if (!in || !out || !quality) return rs_set_last_error((who + "null pointer (in / out / quality)").c_str(), -2);
-    if (B < 1 || B > RS_MAX_ROWS) return rs_set_last_error((who + "B must be 1 .. RS_MAX_ROWS (the qualities travel by value)").c_str(), -2);
-    if (C != 3) return rs_set_last_error((who + "C must be 3 (RGB)").c_str(), -2);
-    if (H < 8 || W < 8) return rs_set_last_error((who + "H and W must be at least 8").c_str(), -2);
-    if (std::max(H, W) > (1 << 28) || (long long)H * W > (1LL << 40)) return rs_set_last_error((who + "a plane is too large (a side above 2^28 or more than 2^40 pixels)").c_str(), -2);
+    if (!in || !out || !quality) return img_fail(who, "null pointer (in / out / quality)");
+    if (B < 1 || B > RS_MAX_ROWS) return img_fail(who, "B must be 1 .. RS_MAX_ROWS (the qualities travel by value)");
+    if (C != 3) return img_fail(who, "C must be 3 (RGB)");
+    if (H < 8 || W < 8) return img_fail(who, "H and W must be at least 8");
+    if (!img_plane_fits(H, W)) return img_fail(who, "a plane is too large (a side above 2^28 or more than 2^40 pixels)");
     JcQuality qual{};
     for (int b = 0; b < B; ++b) {
-        if (quality[b] < 1 || quality[b] > 100) return rs_set_last_error((who + "every quality must be an integer in 1 .. 100").c_str(), -2);
+        if (quality[b] < 1 || quality[b] > 100) return img_fail(who, "every quality must be an integer in 1 .. 100");
         qual.q[b] = quality[b];
     }
     const long long n = (long long)B * 3 * H * W;
-    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (uintptr_t)n * sizeof(float), o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)n * sizeof(float);
-    if (o0 < i1 && i0 < o1) return rs_set_last_error((who + "`out` overlaps `in` (a tile reads the chroma ring of its neighbours: not in place)").c_str(), -2);
+    if (img_overlaps(in, n * sizeof(float), out, n * sizeof(float))) return img_fail(who, "`out` overlaps `in` (a tile reads the chroma ring of its neighbours: not in place)");
     const int mcus_x = (W + 15) / 16, mcus_y = (H + 15) / 16;
     const int tiles_x = (mcus_x + JC_TX - 1) / JC_TX, tiles_y = (mcus_y + JC_TY - 1) / JC_TY;
     const long long total = (long long)B * tiles_x * tiles_y;

@@ -62,6 +62,8 @@ int rs_swin_mlp_launch(const void* x, const void* w1, const float* b1, const voi
                        int ldres, int ldy, int E, int HD, const float* xcoef, int HW, float* ystats, int ystats_ld, hipStream_t st);
 int rs_small_linear_launch(const float* x, const float* w, const float* bias, float* y, int R, int K, int N, int silu_in, int silu_out, hipStream_t st);
 int rs_bicubic_launch(const float* in, void* out, int out_dt, int B, int C, int H, int W, int sf, int ldo, hipStream_t st);
+int rs_interp_launch(const float* in, float* out, long long planes, int H, int W, int Ho, int Wo, double step_h, double step_w, int mode, int clamp,
+                     hipStream_t st);   // degrade.hip: F.interpolate without antialiasing, mode = RS_INTERP_*; the caller has checked the arguments
 int rs_vq_launch(const float* z, const float* codebook, float* zq, int* idx, long long N, int NE, int D, hipStream_t st);
 int rs_copy_channels_launch(const void* src, int lds_, void* dst, int ldd, int C, long long npix, int dt, hipStream_t st);
 int rs_convert_launch(const void* src, int src_dt, void* dst, int dst_dt, int C, long long npix, hipStream_t st);

@@ -18,10 +18,8 @@
 //
 // fp64 throughout: E[a^2] - mu^2 cancels up to eight digits on flat regions, which raw fp32 moments do not survive.  The
 // map expression is kept from contraction: for identical images the numerator and the denominator are then the same bits, and SSIM is 1.
-#include "launchers.h"
-#include <algorithm>
+#include "image_common.h"
 #include <cmath>
-#include <string>
 
 constexpr int MT_T = 32;                   // SSIM-map positions per tile side
 constexpr int MT_TAPS = 11;
@@ -193,10 +191,10 @@ namespace {
 const char* mt_geometry_error(int B, int C, int H, int W, int border, int ycbcr, std::string* text, int* tiles_x, int* tiles_y) {
     if (B < 1 || H < 1 || W < 1) return "B, H and W must be positive";
     if (C != 1 && C != 3) return "C must be 1 or 3";
-    if (ycbcr != 0 && ycbcr != 1) return "ycbcr must be 0 or 1";
+    if (!img_is_flag(ycbcr)) return "ycbcr must be 0 or 1";
     if (ycbcr && C != 3) return "ycbcr needs C == 3";
     if (border < 0) return "border must not be negative";
-    if (H > (1 << 28) || W > (1 << 28) || (long long)H * W > (1LL << 40)) return "an image is too large (a side above 2^28 or more than 2^40 pixels)";
+    if (!img_plane_fits(H, W)) return "an image is too large (a side above 2^28 or more than 2^40 pixels)";
     const long long Hc = (long long)H - 2LL * border, Wc = (long long)W - 2LL * border;
     if (Hc < MT_TAPS || Wc < MT_TAPS) {
         *text = "the cropped image is " + std::to_string(Hc) + " x " + std::to_string(Wc) + " (" + std::to_string(H) + " x " + std::to_string(W) +
@@ -223,20 +221,19 @@ size_t rs_metrics_work_bytes(int B, int C, int H, int W, int border, int ycbcr) 
 int rs_metrics(const void* a, const void* b, int a_is_float, int b_is_float, int B, int C, int H, int W, int border, int ycbcr,
                long long* sse_out, double* ssim_out, void* work, size_t work_bytes, void* stream) {
     const std::string who = "rs_metrics: ";
-    if (!a || !b || !sse_out || !ssim_out) return rs_set_last_error((who + "null tensor (a / b / sse_out / ssim_out)").c_str(), -2);
-    if ((a_is_float != 0 && a_is_float != 1) || (b_is_float != 0 && b_is_float != 1))
-        return rs_set_last_error((who + "a_is_float and b_is_float must be 0 or 1").c_str(), -2);
+    if (!a || !b || !sse_out || !ssim_out) return img_fail(who, "null tensor (a / b / sse_out / ssim_out)");
+    if (!img_is_flag(a_is_float) || !img_is_flag(b_is_float)) return img_fail(who, "a_is_float and b_is_float must be 0 or 1");
     std::string text;
     int tiles_x = 0, tiles_y = 0;
-    if (const char* e = mt_geometry_error(B, C, H, W, border, ycbcr, &text, &tiles_x, &tiles_y)) return rs_set_last_error((who + e).c_str(), -2);
+    if (const char* e = mt_geometry_error(B, C, H, W, border, ycbcr, &text, &tiles_x, &tiles_y)) return img_fail(who, e);
     const size_t need = rs_metrics_work_bytes(B, C, H, W, border, ycbcr);
     if (!work || work_bytes < need)
-        return rs_set_last_error((who + "the workspace is too small: " + std::to_string(work ? work_bytes : 0) + " bytes, rs_metrics_work_bytes asks for " +
-                                  std::to_string(need)).c_str(), -2);
+        return img_fail(who, "the workspace is too small: " + std::to_string(work ? work_bytes : 0) + " bytes, rs_metrics_work_bytes asks for " +
+                                  std::to_string(need));
     if (((uintptr_t)work & 7) || ((uintptr_t)sse_out & 7) || ((uintptr_t)ssim_out & 7))
-        return rs_set_last_error((who + "the workspace, sse_out and ssim_out must be aligned to 8 bytes").c_str(), -2);
+        return img_fail(who, "the workspace, sse_out and ssim_out must be aligned to 8 bytes");
     if ((a_is_float && ((uintptr_t)a & 3)) || (b_is_float && ((uintptr_t)b & 3)))
-        return rs_set_last_error((who + "a float input must be aligned to 4 bytes").c_str(), -2);
+        return img_fail(who, "a float input must be aligned to 4 bytes");
     MtWindow win;
     double total = 0;
     for (int i = 0; i < MT_TAPS; ++i) total += (win.g[i] = std::exp(-(double)((i - 5) * (i - 5)) / 4.5));
@@ -256,10 +253,9 @@ int rs_metrics(const void* a, const void* b, int a_is_float, int b_is_float, int
 
 int rs_rgb_to_y_u8(const uint8_t* rgb_hwc, uint8_t* y, size_t pixels, void* stream) {
     const std::string who = "rs_rgb_to_y_u8: ";
-    if (!rgb_hwc || !y) return rs_set_last_error((who + "null tensor (rgb_hwc / y)").c_str(), -2);
-    if (pixels < 1 || pixels > ((size_t)1 << 40)) return rs_set_last_error((who + "pixels must lie in [1, 2^40]").c_str(), -2);
-    const uintptr_t i0 = (uintptr_t)rgb_hwc, i1 = i0 + 3 * pixels, o0 = (uintptr_t)y, o1 = o0 + pixels;
-    if (o0 < i1 && i0 < o1) return rs_set_last_error((who + "`y` overlaps `rgb_hwc`").c_str(), -2);
+    if (!rgb_hwc || !y) return img_fail(who, "null tensor (rgb_hwc / y)");
+    if (pixels < 1 || pixels > ((size_t)1 << 40)) return img_fail(who, "pixels must lie in [1, 2^40]");
+    if (img_overlaps(rgb_hwc, 3 * pixels, y, pixels)) return img_fail(who, "`y` overlaps `rgb_hwc`");
     const unsigned blocks = (unsigned)std::min<size_t>((pixels + 255) / 256, 65536);
     hipLaunchKernelGGL(rgb_to_y_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rgb_hwc, y, (long long)pixels);
     return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -17,10 +17,8 @@
 // stride of 2^q, q <= 3, then visits 32 different banks per group.  Measured on an MI355X (scripts/resize_bench.py): the
 // linear image is 0.1 %, 0.3 % and 1.5 % slower at 1/2, 1/4 and 1/8 - the vertical pass dominates.  RS_RESIZE_LDS=linear selects the
 // linear image for that measurement; the values are the same bits.
-#include "launchers.h"
-#include <algorithm>
+#include "image_common.h"
 #include <cmath>
-#include <string>
 
 constexpr int RZ_TR = 16;
 constexpr int RZ_TC = 64;
@@ -190,19 +188,17 @@ static RzAxis rz_axis(double s, int n, int m) {
 int rs_resize(const float* in, float* out, int B, int C, int H, int W, int Ho, int Wo, double scale_h, double scale_w, int clamp,
               void* stream) {
     const std::string who = "rs_resize: ";
-    if (!in || !out) return rs_set_last_error((who + "null tensor (in / out)").c_str(), -2);
-    if (B < 1 || C < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1) return rs_set_last_error((who + "B, C, H, W, Ho and Wo must be positive").c_str(), -2);
+    if (!in || !out) return img_fail(who, "null tensor (in / out)");
+    if (B < 1 || C < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1) return img_fail(who, "B, C, H, W, Ho and Wo must be positive");
     if (!(scale_h >= 0.125 && scale_h <= 8.0) || !(scale_w >= 0.125 && scale_w <= 8.0))
-        return rs_set_last_error((who + "scale_h and scale_w must lie in [1/8, 8] (the kernel holds at most 34 taps per axis)").c_str(), -2);
-    if (clamp != 0 && clamp != 1) return rs_set_last_error((who + "clamp must be 0 or 1").c_str(), -2);
-    if (std::max(std::max(H, W), std::max(Ho, Wo)) > (1 << 28) || (long long)H * W > (1LL << 40) || (long long)Ho * Wo > (1LL << 40))
-        return rs_set_last_error((who + "a plane is too large (a side above 2^28 or more than 2^40 pixels)").c_str(), -2);
+        return img_fail(who, "scale_h and scale_w must lie in [1/8, 8] (the kernel holds at most 34 taps per axis)");
+    if (!img_is_flag(clamp)) return img_fail(who, "clamp must be 0 or 1");
+    if (!img_plane_fits(H, W) || !img_plane_fits(Ho, Wo)) return img_fail(who, "a plane is too large (a side above 2^28 or more than 2^40 pixels)");
     const long long planes = (long long)B * C;
-    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (uintptr_t)(planes * H * W) * sizeof(float);
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(planes * Ho * Wo) * sizeof(float);
-    if (o0 < i1 && i0 < o1) return rs_set_last_error((who + "`out` overlaps `in` (workgroups read their neighbours' pixels of in: not in place)").c_str(), -2);
+    if (img_overlaps(in, planes * H * W * sizeof(float), out, planes * Ho * Wo * sizeof(float)))
+        return img_fail(who, "`out` overlaps `in` (workgroups read their neighbours' pixels of in: not in place)");
     const RzAxis ah = rz_axis(scale_h, H, Ho), aw = rz_axis(scale_w, W, Wo);
-    if (ah.P > RZ_PMAX || aw.P > RZ_PMAX) return rs_set_last_error((who + "more than 34 taps per axis").c_str(), -2);
+    if (ah.P > RZ_PMAX || aw.P > RZ_PMAX) return img_fail(who, "more than 34 taps per axis");
     const int pad = !rs_env_is("RS_RESIZE_LDS", "linear");   // A/B knob of scripts/resize_bench.py, read per call
     const int tiles_x = (Wo + RZ_TC - 1) / RZ_TC, tiles_y = (Ho + RZ_TR - 1) / RZ_TR;
     const long long total = planes * tiles_x * tiles_y;

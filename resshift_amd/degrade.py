@@ -30,6 +30,7 @@ import torch
 
 from . import _lib
 from .continuous import request_seed
+from .imageops import ImageOps
 
 KERNEL_KINDS = ("iso", "aniso", "generalized_iso", "generalized_aniso", "plateau_iso", "plateau_aniso")
 MODES = ("area", "bilinear", "bicubic")
@@ -399,48 +400,23 @@ def draw_face_plan(opts: FaceOptions, H: int, W: int, seed: int) -> FacePlan:
 
 
 # ---------------------------------------------------------------------------------------------------------------- execution
-class _LibOps:
-    """the engine's degradation methods for a caller without an Engine: the same _lib calls on `device`"""
-
-    def __init__(self, device=None):
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-
-    def _call(self, fn, *a, **kw):
-        with torch.cuda.device(self.device):
-            return fn(*a, **kw)
-
-    def filter2d(self, x, kernels, clamp=False):
-        return self._call(_lib.filter2d, x, kernels, clamp=clamp)
-
-    def interpolate(self, x, scale_factor=None, size=None, mode="bilinear", clamp=False):
-        return self._call(_lib.interpolate, x, scale_factor=scale_factor, size=size, mode=mode, clamp=clamp)
-
-    def jpeg(self, x, quality):
-        return self._call(_lib.jpeg, x, quality)
-
-    def add_noise(self, x, keys, sigma, gray=False, draw=0, clamp=True):
-        return self._call(_lib.add_noise, x, keys, sigma, gray=gray, draw=draw, clamp=clamp)
-
-    def unit_to_u8(self, x):
-        return self._call(_lib.unit_to_u8, x)
-
-    def jpeg_codec(self, x, quality):
-        return self._call(_lib.jpeg_codec, x, quality)
-
-    def blur_resize(self, x, kernels, size, clamp=False):
-        return self._call(_lib.blur_resize, x, kernels, size, clamp=clamp)
-
-
 class Degrader:
     """Executes DegradePlans on the device.  `engine_or_device`: an Engine (its filter2d / interpolate / jpeg / add_noise / unit_to_u8 are
     used), a device, or None for the current one."""
 
     def __init__(self, engine_or_device=None):
-        self.ops = engine_or_device if hasattr(engine_or_device, "filter2d") else _LibOps(engine_or_device)
+        self.ops = engine_or_device if hasattr(engine_or_device, "filter2d") else ImageOps(engine_or_device)
         self.device = self.ops.device
 
     def _kernels(self, specs):
         return torch.from_numpy(np.stack([s.array() for s in specs])).to(self.device)
+
+    def _finish(self, x, log, trace):
+        """the `round` stage and what `run` / `run_face` return"""
+        u8 = self.ops.unit_to_u8(x)
+        log.append(("round", x, u8))
+        lq = u8.permute(0, 3, 1, 2).to(torch.float32).div(255.0).contiguous()
+        return (lq, log) if trace else lq
 
     def run(self, gt01, plan: DegradePlan, trace=False):
         """gt01 [B,3,H,W] in [0,1] -> the LQ batch [B,3,H // sf,W // sf], fp32 in [0,1] on the 1/255 grid, in degrade_fun's order:
@@ -479,9 +455,7 @@ class Degrader:
             x = step("jpeg2", x, ops.jpeg(x, plan.jpeg2))                   # (its input is a JPEG's or a clamped noise stage's output)
             x = step("resize3", x, ops.interpolate(x, size=size, mode=plan.final_mode))
             x = step("sinc", x, ops.filter2d(x, sinc))
-        u8 = step("round", x, ops.unit_to_u8(x))
-        lq = u8.permute(0, 3, 1, 2).to(torch.float32).div(255.0).contiguous()
-        return (lq, log) if trace else lq
+        return self._finish(x, log, trace)
 
     def run_u8(self, gt_u8, plan: DegradePlan):
         """uint8 [B,H,W,3] -> uint8 [B,H // sf,W // sf,3] (device tensors): what `make_testset` reads and writes"""
@@ -508,9 +482,7 @@ class Degrader:
         x = step("noise", x, ops.add_noise(x, [(plan.noise_seed, 0)], [plan.nf], gray=False, draw=0, clamp=True))
         x = step("jpeg", x, ops.jpeg_codec(x, [plan.quality]))
         x = step("up", x, ops.blur_resize(x, None, (plan.H, plan.W)))
-        u8 = step("round", x, ops.unit_to_u8(x))
-        lq = u8.permute(0, 3, 1, 2).to(torch.float32).div(255.0).contiguous()
-        return (lq, log) if trace else lq
+        return self._finish(x, log, trace)
 
     def run_face_u8(self, gt_u8, plan: FacePlan):
         """uint8 [1,H,W,3] -> uint8 [1,H,W,3] (device tensors): what `make_face_testset` reads and writes"""
@@ -534,67 +506,53 @@ def write_plans(lq_dir, plans) -> None:
         json.dump({k: p.to_dict() for k, p in sorted(plans.items())}, fh, indent=1)
 
 
+def _make_set(gt_dir, lq_dir, size_error, plan_for, run_u8, device, seed, positions) -> dict:
+    """what `make_testset` and `make_face_testset` share.  size_error(h, w): None, or why the recipe does not take an image of that size;
+    plan_for(h, w, seed): the image's plan; run_u8(degrader, uint8 [1,H,W,3], plan): its LQ image, uint8 [1,h,w,3] on the device."""
+    from PIL import Image
+
+    files = list_images(gt_dir)
+    todo = list(range(len(files))) if positions is None else list(positions)
+    sizes = {}
+    for i in todo:
+        with Image.open(files[i]) as im:
+            w, h = im.size
+        why = size_error(h, w)
+        if why:
+            raise ValueError(f"{files[i]}: {h} x {w} {why}")
+        sizes[i] = (h, w)
+    lq_dir = Path(lq_dir)
+    lq_dir.mkdir(parents=True, exist_ok=True)
+    dg = Degrader(device)
+    plans = {}
+    for i in todo:
+        plan = plan_for(*sizes[i], request_seed(seed, i))
+        gt = torch.from_numpy(np.asarray(Image.open(files[i]).convert("RGB"), dtype=np.uint8).copy()).unsqueeze(0)
+        lq = run_u8(dg, gt, plan)[0].cpu().numpy()
+        Image.fromarray(lq).save(lq_dir / f"{files[i].stem}.png")
+        plans[files[i].stem] = plan
+    if positions is None:
+        write_plans(lq_dir, plans)
+    return plans
+
+
 def make_testset(gt_dir, lq_dir, sf=4, opts: DegradeOptions = REALESRGAN_TESTING, seed=10000, device=None, positions=None) -> dict:
     """A folder of ground-truth images -> lq_dir/<stem>.png, degraded on the device, plus lq_dir/plans.json {stem: plan}.  The image at
     position i of the sorted listing gets one plan with B = 1 from the seed continuous.request_seed(seed, i): a file's LQ image depends
     on its position and the seed only.  Every side of every image must be a multiple of `sf` (ValueError naming the file, before
     anything is written).  `device`: a device or an Engine.  `positions` (of the listing; default: all of it): the files this call
     degrades - the caller then writes plans.json itself (`write_plans`) from what its ranks return.  Returns {stem: DegradePlan}."""
-    from PIL import Image
-
     opts = dataclasses.replace(opts, sf=int(sf))
-    files = list_images(gt_dir)
-    todo = list(range(len(files))) if positions is None else list(positions)
-    sizes = {}
-    for i in todo:
-        with Image.open(files[i]) as im:
-            w, h = im.size
-        if h % opts.sf or w % opts.sf:
-            raise ValueError(f"{files[i]}: {h} x {w} is no multiple of sf = {opts.sf}")
-        sizes[i] = (h, w)
-    lq_dir = Path(lq_dir)
-    lq_dir.mkdir(parents=True, exist_ok=True)
-    dg = Degrader(device)
-    plans = {}
-    for i in todo:
-        plan = draw_plan(opts, 1, *sizes[i], request_seed(seed, i))
-        gt = torch.from_numpy(np.asarray(Image.open(files[i]).convert("RGB"), dtype=np.uint8).copy()).unsqueeze(0)
-        lq = dg.run_u8(gt, plan)[0].cpu().numpy()
-        Image.fromarray(lq).save(lq_dir / f"{files[i].stem}.png")
-        plans[files[i].stem] = plan
-    if positions is None:
-        write_plans(lq_dir, plans)
-    return plans
+    return _make_set(gt_dir, lq_dir, lambda h, w: f"is no multiple of sf = {opts.sf}" if h % opts.sf or w % opts.sf else None,
+                     lambda h, w, s: draw_plan(opts, 1, h, w, s), lambda dg, gt, plan: dg.run_u8(gt, plan), device, seed, positions)
 
 
 def make_face_testset(gt_dir, lq_dir, opts: FaceOptions = FACE_TESTING, seed=10000, device=None, positions=None) -> dict:
     """`make_testset` for the face recipe: lq_dir/<stem>.png of the GROUND TRUTH'S size plus lq_dir/plans.json {stem: FacePlan}; the image at
     position i of the sorted listing gets the plan draw_face_plan(opts, H, W, request_seed(seed, i)).  Every side must be at least 256
     (ValueError naming the file, before anything is written).  `device`, `positions` and the return value as `make_testset` has them."""
-    from PIL import Image
-
-    files = list_images(gt_dir)
-    todo = list(range(len(files))) if positions is None else list(positions)
-    sizes = {}
-    for i in todo:
-        with Image.open(files[i]) as im:
-            w, h = im.size
-        if min(h, w) < FACE_MIN_SIDE:
-            raise ValueError(f"{files[i]}: {h} x {w} has a side below {FACE_MIN_SIDE}")
-        sizes[i] = (h, w)
-    lq_dir = Path(lq_dir)
-    lq_dir.mkdir(parents=True, exist_ok=True)
-    dg = Degrader(device)
-    plans = {}
-    for i in todo:
-        plan = draw_face_plan(opts, *sizes[i], request_seed(seed, i))
-        gt = torch.from_numpy(np.asarray(Image.open(files[i]).convert("RGB"), dtype=np.uint8).copy()).unsqueeze(0)
-        lq = dg.run_face_u8(gt, plan)[0].cpu().numpy()
-        Image.fromarray(lq).save(lq_dir / f"{files[i].stem}.png")
-        plans[files[i].stem] = plan
-    if positions is None:
-        write_plans(lq_dir, plans)
-    return plans
+    return _make_set(gt_dir, lq_dir, lambda h, w: f"has a side below {FACE_MIN_SIDE}" if min(h, w) < FACE_MIN_SIDE else None,
+                     lambda h, w, s: draw_face_plan(opts, h, w, s), lambda dg, gt, plan: dg.run_face_u8(gt, plan), device, seed, positions)
 
 
 def main(argv=None):

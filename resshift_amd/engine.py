@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .imageops import ImageOps
 from .spec import _listify, unet_heads
 
 F16, F32, SPLIT = _lib.RS_PREC_F16, _lib.RS_PREC_F32, _lib.RS_PREC_SPLIT
@@ -70,15 +71,16 @@ def _fill_ae(ca: _lib.AEConfig, p: Mapping) -> None:
     ca.n_attn_res = len(ar)
 
 
-class Engine:
-    """One native engine on the current device.  `unet_params` / `ae_params` are the YAML `params` blocks."""
+class Engine(ImageOps):
+    """One native engine on the current device.  `unet_params` / `ae_params` are the YAML `params` blocks.  The image operators around the
+    sampler (color_fix .. rgb_to_y) are ImageOps' methods."""
 
     def __init__(self, unet_params: Optional[Mapping] = None, ae_params: Optional[Mapping] = None, enable_f16: bool = True,
                  enable_f32: bool = True, device: Optional[torch.device] = None, enable_split: bool = True):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("resshift_amd.Engine needs a HIP device; there is no CPU fallback")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        super().__init__(device)
         cfg = _lib.Config()
         if unet_params is not None:
             _fill_unet(cfg.unet, unet_params)
@@ -146,11 +148,7 @@ class Engine:
         self._chk(self.lib.rs_weights_ready(self._h), "rs_weights_ready")
         self.weights_loaded = True
 
-    # -- network calls (NCHW fp32 tensors, like the reference)
-    @staticmethod
-    def _f32c(t: torch.Tensor) -> torch.Tensor:
-        return t.detach().to(torch.float32).contiguous()
-
+    # -- network calls (NCHW fp32 tensors, like the reference); the image operators are ImageOps'
     def unet_forward(self, x, timesteps: Sequence[int], lq=None, mask=None, prec=F16):
         x = self._f32c(x)
         B, _, H, W = x.shape
@@ -196,73 +194,6 @@ class Engine:
             rc = self.lib.rs_bicubic(self._h, y.data_ptr(), out.data_ptr(), B, Cc, H, W, sf, self._stream())
         self._chk(rc, "rs_bicubic")
         return out
-
-    def color_fix(self, sr, lq, mode="wavelet"):
-        """The sample sr [B,C,H*sf,W*sf] corrected against its input lq [B,C,H,W], both in [-1,1]: "wavelet" keeps sr's detail and takes
-        the low frequencies of the bicubic up-sampled lq, "adain" takes lq's per-channel mean and deviation (rs_color_fix).
-        Returns a new tensor; whole images only - tiles are corrected after they are blended."""
-        with torch.cuda.device(self.device):
-            return _lib.color_fix(self._f32c(sr), self._f32c(lq), mode)
-
-    def resize(self, x, scale=None, size=None, clamp=False):
-        """x [B,C,H,W] resized with MATLAB's antialiased bicubic imresize (rs_resize): `scale` for both axes (output
-        ceil(H * scale) x ceil(W * scale)) or `size` = (Ho, Wo); `clamp` clamps the result to [-1, 1].  Returns a new fp32 tensor; whole
-        images only - tiles are resized after they are blended."""
-        with torch.cuda.device(self.device):
-            return _lib.resize(self._f32c(x), scale=scale, size=size, clamp=clamp)
-
-    # the degradation operators (DESIGN.md 7h; resshift_amd/degrade.py runs them in the recipe's order): images in [0, 1], new tensors
-    def filter2d(self, x, kernels, clamp=False):
-        """The reference's filter2D: x [B,C,H,W] cross-correlated with `kernels` [1 | B,k,k] behind `reflect` padding (rs_filter2d)."""
-        with torch.cuda.device(self.device):
-            return _lib.filter2d(self._f32c(x), self._f32c(kernels), clamp=clamp)
-
-    def interpolate(self, x, scale_factor=None, size=None, mode="bilinear", clamp=False):
-        """F.interpolate(x, scale_factor= | size=, mode="area" | "bilinear" | "bicubic") without antialiasing (rs_interp); `resize` is
-        MATLAB's antialiased resize."""
-        with torch.cuda.device(self.device):
-            return _lib.interpolate(self._f32c(x), scale_factor=scale_factor, size=size, mode=mode, clamp=clamp)
-
-    def jpeg(self, x, quality):
-        """The reference's DiffJPEG(differentiable=False) on x [B,3,H,W] in [0,1], one quality in (0, 100) per image (rs_jpeg)."""
-        with torch.cuda.device(self.device):
-            return _lib.jpeg(self._f32c(x), quality)
-
-    def add_noise(self, x, keys, sigma, gray=False, draw=0, clamp=True):
-        """x + (sigma / 255) n with n = noise_fill(keys, draw, (C | 1, H, W)) generated in registers, clamped to [0, 1] (rs_add_noise)."""
-        with torch.cuda.device(self.device):
-            return _lib.add_noise(self._f32c(x), keys, sigma, gray=gray, draw=draw, clamp=clamp)
-
-    def unit_to_u8(self, x):
-        """fp32 [B,C,H,W] in [0,1] -> uint8 [B,H,W,C], clamp(rint(x * 255), 0, 255) (rs_unit_to_u8)."""
-        with torch.cuda.device(self.device):
-            return _lib.unit_to_u8(self._f32c(x))
-
-    # the face recipe's operators (DESIGN.md 7i)
-    def jpeg_codec(self, x, quality):
-        """libjpeg's baseline JPEG round trip at 4:2:0 on x [B,3,H,W] (RGB, clipped to [0,1]), one integer quality 1 .. 100 per image
-        (rs_jpeg_codec): cv2's imencode + imdecode, byte for byte."""
-        with torch.cuda.device(self.device):
-            return _lib.jpeg_codec(self._f32c(x), quality)
-
-    def blur_resize(self, x, kernels, size, clamp=False):
-        """bilinear(filter2d(x, kernels), size) in one launch with kernels of up to 41 taps; kernels=None: the resize alone (rs_blur_resize)."""
-        with torch.cuda.device(self.device):
-            return _lib.blur_resize(self._f32c(x), None if kernels is None else self._f32c(kernels), size, clamp=clamp)
-
-    def metrics(self, sr, gt, border=0, ycbcr=True):
-        """PSNR / SSIM of the batch `sr` against the ground truth `gt` on uint8 pixels, as the reference's calculate_psnr / calculate_ssim
-        score them (rs_metrics).  Each is uint8 [B,H,W,C] or a float tensor [B,C,H,W] in [-1,1], which is quantised exactly
-        as `output_to_u8` does; C is 1 or 3; `ycbcr` scores MATLAB's Y channel (C == 3); `border` pixels are cropped from every side.
-        Returns {"psnr": float64 [B], "ssim": float64 [B], "sse": int64 [B]} on the device."""
-        prep = lambda t: t.contiguous() if t.dtype == torch.uint8 else self._f32c(t)
-        with torch.cuda.device(self.device):
-            return _lib.metrics(prep(sr), prep(gt), border=border, ycbcr=ycbcr)
-
-    def rgb_to_y(self, u8):
-        """uint8 [...,3] device tensor -> uint8 [...]: MATLAB's rounded Y channel in exact integer arithmetic (rs_rgb_to_y_u8)"""
-        with torch.cuda.device(self.device):
-            return _lib.rgb_to_y(u8.contiguous())
 
     def axpbypcz(self, x, z, n, a, b, c, out=None):
         """out = a*x + b*z + c*n elementwise on fp32 tensors of identical layout (z, n optional)."""

@@ -26,6 +26,7 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _timing import measure  # noqa: E402
 from resshift_amd import _lib  # noqa: E402
 
 HBM_PEAK = 8.0e12   # bytes/s, HBM3E specification of the MI355X
@@ -45,17 +46,6 @@ def torch_adain(sr, lq):
     v_lq, m_lq = torch.var_mean(lq, dim=(2, 3), keepdim=True)
     gain = ((v_lq + 1e-5) / (v_sr + 1e-5)).sqrt()
     return torch.addcmul(m_lq - m_sr * gain, sr, gain).clamp_(-1, 1)
-
-
-def event_ms(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
 
 
 def main():
@@ -95,25 +85,14 @@ def main():
         for mode in _lib.COLOR_FIX_MODES:
             legs[(mode, "hip")]()
             agree[mode] = float((out - legs[(mode, "torch")]()).abs().max().item())
-        # warm-up round: every leg, and its iteration count
-        iters = {}
-        for key, fn in legs.items():
-            event_ms(fn, 3)
-            per = event_ms(fn, 10)
-            iters[key] = int(min(20000, max(20, args.window * 1e3 / max(per, 1e-4))))
-        rounds = {key: [] for key in legs}
-        for _ in range(args.rounds):
-            for key, fn in legs.items():
-                rounds[key].append(event_ms(fn, iters[key]))
+        res = measure(legs, args.rounds, args.window)
         nbytes = 4 * (2 * sr.numel() + lq.numel())
         wl = {"shape": {"B": B, "C": Cc, "H": Hh, "W": W, "sf": sf}, "algorithmic_bytes": nbytes, "max_abs_hip_minus_torch": agree, "modes": {}}
         for mode in _lib.COLOR_FIX_MODES:
             row = {}
             for impl in ("hip", "torch"):
-                r = sorted(rounds[(mode, impl)])
-                med = r[len(r) // 2]
-                row[impl] = {"ms": med, "spread": (r[-1] - r[0]) / med, "iters": iters[(mode, impl)], "rounds_ms": rounds[(mode, impl)],
-                             "bytes_per_s": nbytes / (med * 1e-3), "hbm_fraction": nbytes / (med * 1e-3) / HBM_PEAK}
+                med = res[(mode, impl)]["ms"]
+                row[impl] = {**res[(mode, impl)], "bytes_per_s": nbytes / (med * 1e-3), "hbm_fraction": nbytes / (med * 1e-3) / HBM_PEAK}
             row["speedup"] = row["torch"]["ms"] / row["hip"]["ms"]
             wl["modes"][mode] = row
         result["workloads"][name] = wl

@@ -28,44 +28,16 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from _timing import measure  # noqa: E402
 from resshift_amd import _lib, degrade  # noqa: E402
 
 HBM_PEAK = 8.0e12   # bytes/s, HBM3E specification of the MI355X
 SIZES = (256, 512)
 BATCH = 32
+MEASURE = {"warm": (2, 5), "min_iters": 5, "max_iters": 5000}   # this script's (and face_degrade_bench.py's) arguments of _timing.measure
 INDEX_LINE = ("| `degrade_bench.json` | `scripts/degrade_bench.py` (DESIGN §7h): device-event times of `rs_filter2d`, `rs_interp`, `rs_add_noise`, `rs_jpeg`, "
               "`rs_unit_to_u8` and of a whole degradation plan against a torch composition of the same operators on the same GPU - 256² and 512² ground truth, "
               "batch 32 - median of alternating rounds, spread, fraction of the HBM peak on the algorithmic bytes |")
-
-
-def event_ms(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def measure(legs, rounds, window):
-    """one warm-up round (every leg, and its iteration count), then `rounds` alternating rounds: {leg: {ms, spread, iters, rounds_ms}}"""
-    iters = {}
-    for key, fn in legs.items():
-        event_ms(fn, 2)
-        per = event_ms(fn, 5)
-        iters[key] = int(min(5000, max(5, window * 1e3 / max(per, 1e-4))))
-    times = {key: [] for key in legs}
-    for _ in range(rounds):
-        for key, fn in legs.items():
-            times[key].append(event_ms(fn, iters[key]))
-    res = {}
-    for key, r in times.items():
-        srt = sorted(r)
-        med = srt[len(srt) // 2]
-        res[key] = {"ms": med, "spread": (srt[-1] - srt[0]) / med, "iters": iters[key], "rounds_ms": r}
-    return res
 
 
 # ---------------------------------------------------------------------------------------------------------------- the torch composition
@@ -195,7 +167,7 @@ def main():
             agree = None
             if name not in ("add_noise", "pipeline"):
                 agree = float((hip().float() - ref().float()).abs().max().item())
-            res = measure({"hip": hip, "torch": ref}, args.rounds, args.window)
+            res = measure({"hip": hip, "torch": ref}, args.rounds, args.window, **MEASURE)
             row = {"legs": res, "max_abs_hip_minus_torch": agree, "speedup_over_torch": res["torch"]["ms"] / res["hip"]["ms"],
                    "beats_torch": res["torch"]["ms"] > res["hip"]["ms"] * (1 + res["hip"]["spread"])}
             if traffic is not None:   # algorithmic bytes in units of the input tensor's

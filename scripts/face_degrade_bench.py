@@ -32,7 +32,8 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
-from degrade_bench import BATCH, HBM_PEAK, SIZES, measure, torch_filter2d  # noqa: E402
+from _timing import measure  # noqa: E402
+from degrade_bench import BATCH, HBM_PEAK, MEASURE, SIZES, torch_filter2d  # noqa: E402
 from resshift_amd import _lib, degrade  # noqa: E402
 
 RATIOS = (1.0, 2.0, 4.0, 6.0, 8.0, 16.0, 32.0)
@@ -114,7 +115,7 @@ def main():
                 if not name.startswith("blur_resize"):
                     continue
                 legs, against = {"hip": legs["hip"]}, "hip"
-            res = measure(legs, args.rounds, args.window)
+            res = measure(legs, args.rounds, args.window, **MEASURE)
             row = {"legs": res, "against": against, "speedup": res[against]["ms"] / res["hip"]["ms"],
                    "beats_it": res[against]["ms"] > res["hip"]["ms"] * (1 + res["hip"]["spread"]), **extra}
             if traffic is not None:

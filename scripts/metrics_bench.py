@@ -34,39 +34,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _metrics_ref as M  # noqa: E402
+from _timing import measure  # noqa: E402
 from resshift_amd import _lib  # noqa: E402
 
 WORKLOADS = {"batch": (32, 256, 256), "photo": (1, 2048, 2048)}
-
-
-def event_ms(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def measure(legs, rounds, window):
-    """one warm-up round (every leg, and its iteration count), then `rounds` alternating rounds: {leg: {ms, spread, iters, rounds_ms}}"""
-    iters = {}
-    for key, fn in legs.items():
-        event_ms(fn, 2)
-        per = event_ms(fn, 5)
-        iters[key] = int(min(20000, max(5, window * 1e3 / max(per, 1e-4))))
-    times = {key: [] for key in legs}
-    for _ in range(rounds):
-        for key, fn in legs.items():
-            times[key].append(event_ms(fn, iters[key]))
-    res = {}
-    for key, r in times.items():
-        srt = sorted(r)
-        med = srt[len(srt) // 2]
-        res[key] = {"ms": med, "spread": (srt[-1] - srt[0]) / med, "iters": iters[key], "rounds_ms": r}
-    return res
 
 
 def torch_y(t):
@@ -144,7 +115,7 @@ def main():
         raw()
         torch.cuda.synchronize()
         agree["hip_raw_same_bits"] = bool(torch.equal(sse, got["sse"]) and torch.equal(ssim, got["ssim"]))
-        res = measure(legs, args.rounds, args.window)
+        res = measure(legs, args.rounds, args.window, warm=(2, 5), min_iters=5)
         cpu = []
         for _ in range(args.cpu_runs):
             t0 = time.perf_counter()

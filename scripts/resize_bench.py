@@ -35,6 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _resize_ref as R  # noqa: E402
+from _timing import measure  # noqa: E402
 from resshift_amd import _lib  # noqa: E402
 
 HBM_PEAK = 8.0e12   # bytes/s, HBM3E specification of the MI355X
@@ -44,36 +45,6 @@ INDEX_LINE = ("| `resize_bench.json` | `scripts/resize_bench.py` (DESIGN §7f): 
               "`Mh @ x @ Mwᵀ` and `F.interpolate(bicubic, antialias=True)` on the same GPU - 1024² → 512² (B = 1), 256² → 128² (B = 32), 1024² → 1536² "
               "(B = 1) - median of alternating rounds, spread, fraction of the HBM peak on the algorithmic bytes; `lds_stride`: the padded against "
               "the linear LDS image at s = 1/2, 1/4, 1/8 |")
-
-
-def event_ms(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def measure(legs, rounds, window):
-    """one warm-up round (every leg, and its iteration count), then `rounds` alternating rounds: {leg: {ms, spread, iters, rounds_ms}}"""
-    iters = {}
-    for key, fn in legs.items():
-        event_ms(fn, 3)
-        per = event_ms(fn, 10)
-        iters[key] = int(min(20000, max(20, window * 1e3 / max(per, 1e-4))))
-    times = {key: [] for key in legs}
-    for _ in range(rounds):
-        for key, fn in legs.items():
-            times[key].append(event_ms(fn, iters[key]))
-    res = {}
-    for key, r in times.items():
-        srt = sorted(r)
-        med = srt[len(srt) // 2]
-        res[key] = {"ms": med, "spread": (srt[-1] - srt[0]) / med, "iters": iters[key], "rounds_ms": r}
-    return res
 
 
 def hip_leg(lib, x, out, sh, sw, layout=None):

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _timing import event_ms  # noqa: E402
 from resshift_amd import ResShiftSampler, _lib  # noqa: E402
 from resshift_amd.config import ConfigNode, load_config, to_plain  # noqa: E402
 from resshift_amd.spec import ae_param_spec, random_state_dict, unet_param_spec  # noqa: E402
@@ -54,18 +55,6 @@ def sync_time(fn):
     r = fn()
     torch.cuda.synchronize()
     return time.perf_counter() - t0, r
-
-
-def event_ms(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
 
 
 def blend_bench(smp, dev, plan, reps, result):
@@ -111,7 +100,7 @@ def blend_bench(smp, dev, plan, reps, result):
     ms = {b: [] for b in blends}
     for rnd in range(reps + 1):
         for b in blends:
-            t = event_ms(launches[b], 50)
+            t = event_ms(launches[b], 50, warm=1)
             if rnd:
                 ms[b].append(t)
     result["scatter_launch"] = {"tiles_per_step": n, "tile": "64x64 LR, sf 4", "ramp": ramp[0], "iters_per_round": 50}
@@ -206,10 +195,10 @@ def main():
 
     result["data_movement"] = {
         "tiles_per_step": n, "tile": "64x64 LR, sf 4",
-        "rs_tile_gather_ms": round(event_ms(lambda: _lib.tile_gather(g_rows, out_lq), 50), 4),
-        "per_tile_window_copy_ms": round(event_ms(per_tile_crops, 50), 4),
-        "rs_tile_scatter_ms": round(event_ms(lambda: _lib.tile_scatter(s_rows, batch, sf), 50), 4),
-        "per_tile_accumulate_ms": round(event_ms(per_tile_accumulate, 50), 4)}
+        "rs_tile_gather_ms": round(event_ms(lambda: _lib.tile_gather(g_rows, out_lq), 50, warm=1), 4),
+        "per_tile_window_copy_ms": round(event_ms(per_tile_crops, 50, warm=1), 4),
+        "rs_tile_scatter_ms": round(event_ms(lambda: _lib.tile_scatter(s_rows, batch, sf), 50, warm=1), 4),
+        "per_tile_accumulate_ms": round(event_ms(per_tile_accumulate, 50, warm=1), 4)}
     print(json.dumps(result), flush=True)
 
 

@@ -98,10 +98,10 @@ def test_codec_chunks_a_batch_of_65(gpu):
 
 def test_codec_through_the_engine_and_its_errors(gpu):
     from resshift_amd import _lib
-    from resshift_amd.degrade import _LibOps
+    from resshift_amd.imageops import ImageOps
 
     x = _dev(J.content("smooth", 24, 72, 3)[None], gpu)
-    assert torch.equal(_LibOps(gpu).jpeg_codec(x, [50]), _lib.jpeg_codec(x, 50))
+    assert torch.equal(ImageOps(gpu).jpeg_codec(x, [50]), _lib.jpeg_codec(x, 50))
     lib = _lib.load()
     out = torch.empty_like(x)
     import ctypes as C
