@@ -181,14 +181,14 @@ int launch_flash(const FlashParams& p, int nz, hipStream_t st) {
 
 // fp16 streaming attention of the autoencoder's AttnBlock: C in {128, 256, 512} channels, T a multiple of 128, 16-byte aligned rows
 extern "C" int rs_ae_flash_supported(int C, int T) { return (C == 128 || C == 256 || C == 512) && T >= 128 && (T % 128) == 0; }
-extern "C" int rs_ae_flash_launch(const void* q, int ldq, const void* k, int ldk, const void* vt, const float* bv, void* o, int ldo, int nz, int T, int C,
-                                  float scale, hipStream_t st) {
-    if (!rs_ae_flash_supported(C, T) || (ldq & 7) || (ldk & 7) || (ldo & 3)) return -2;
-    if ((long long)T * ldk * 2 >= 0xF0000000LL || (long long)C * T * 2 >= 0xF0000000LL) return -2;   // 32-bit buffer offsets per image
+extern "C" int rs_ae_flash_launch(const AeFlashCall* c, hipStream_t st) {
+    const int T = c->T, C = c->C;
+    if (!rs_ae_flash_supported(C, T) || (c->ldq & 7) || (c->ldk & 7) || (c->ldo & 3)) return -2;
+    if ((long long)T * c->ldk * 2 >= 0xF0000000LL || (long long)C * T * 2 >= 0xF0000000LL) return -2;   // 32-bit buffer offsets per image
     FlashParams p{};
-    p.q = (const f16*)q; p.k = (const f16*)k; p.vt = (const f16*)vt; p.bv = bv; p.o = (f16*)o;
-    p.T = T; p.ldq = ldq; p.ldk = ldk; p.ldo = ldo; p.scale = scale;
-    if (C == 512) return launch_flash<512>(p, nz, st);
-    if (C == 256) return launch_flash<256>(p, nz, st);
-    return launch_flash<128>(p, nz, st);
+    p.q = (const f16*)c->q; p.k = (const f16*)c->k; p.vt = (const f16*)c->vt; p.bv = c->bv; p.o = (f16*)c->o;
+    p.T = T; p.ldq = c->ldq; p.ldk = c->ldk; p.ldo = c->ldo; p.scale = c->scale;
+    if (C == 512) return launch_flash<512>(p, c->nz, st);
+    if (C == 256) return launch_flash<256>(p, c->nz, st);
+    return launch_flash<128>(p, c->nz, st);
 }

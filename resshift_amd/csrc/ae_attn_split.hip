@@ -208,12 +208,12 @@ int launch_flash_split(const FlashSplitParams& p, int nz, hipStream_t st) {
 // split-storage streaming attention of the autoencoder's AttnBlock: C = 512 channels (the shipped autoencoders' mid block), T a multiple
 // of 64, 16-byte aligned rows
 extern "C" int rs_ae_flash_split_supported(int C, int T) { return C == 512 && T >= 64 && (T % 64) == 0; }
-extern "C" int rs_ae_flash_split_launch(const void* q, int ldq, const void* k, int ldk, const void* vt, const float* bv, void* o, int ldo, int nz, int T,
-                                        int C, float scale, hipStream_t st) {
-    if (!rs_ae_flash_split_supported(C, T) || (ldq & 7) || (ldk & 7) || (ldo & 3)) return -2;
-    if ((long long)T * ldk * 4 >= 0xF0000000LL || (long long)C * T * 4 >= 0xF0000000LL) return -2;   // 32-bit buffer offsets per image
+extern "C" int rs_ae_flash_split_launch(const AeFlashCall* c, hipStream_t st) {
+    const int T = c->T, C = c->C;
+    if (!rs_ae_flash_split_supported(C, T) || (c->ldq & 7) || (c->ldk & 7) || (c->ldo & 3)) return -2;
+    if ((long long)T * c->ldk * 4 >= 0xF0000000LL || (long long)C * T * 4 >= 0xF0000000LL) return -2;   // 32-bit buffer offsets per image
     FlashSplitParams p{};
-    p.q = (const f16*)q; p.k = (const f16*)k; p.vt = (const f16*)vt; p.bv = bv; p.o = (f16*)o;
-    p.T = T; p.ldq = ldq; p.ldk = ldk; p.ldo = ldo; p.scale = scale;
-    return launch_flash_split<512>(p, nz, st);
+    p.q = (const f16*)c->q; p.k = (const f16*)c->k; p.vt = (const f16*)c->vt; p.bv = c->bv; p.o = (f16*)c->o;
+    p.T = T; p.ldq = c->ldq; p.ldk = c->ldk; p.ldo = c->ldo; p.scale = c->scale;
+    return launch_flash_split<512>(p, c->nz, st);
 }

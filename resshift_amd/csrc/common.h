@@ -292,7 +292,7 @@ struct IGemmParams {
     const void* sx; const void* sw; const float* sbias;
     int sC, sld;
     unsigned sx_bytes, sw_bytes;   // (filled in by the launcher)
-    // output scatter of the sub-pixel form of "nearest x2 upsample + conv3x3" (graphs.h upfold_conv; models/unet.py:53-81,
+    // output scatter of the sub-pixel form of "nearest x2 upsample + conv3x3" (graphs.h Graphs::upfold; models/unet.py:53-81,
     // ldm/modules/diffusionmodules/model.py:50-65): osc == 2 - this launch is one of four 2x2 convs over the LOW-resolution grid Ho x Wo and
     // GEMM row (b, oy, ox) is pixel (2 oy + ooy, 2 ox + oox) of the [B][2 Ho][2 Wo] output tensor.  Generic kernels only (igemm / igemm2 /
     // igemm3 / igemm_split), no residual, no split-K; output statistics from igemm_split only (the four launches fill ONE slab array -
@@ -382,4 +382,31 @@ struct WinAttnParams {
     // GroupNorm tail (gn_tail.h; the split-storage fused kernel): the wave that publishes the image's last statistics also writes norm2's
     // coefficients - every wave (head) of every window arrives once
     GNTail tail;
+};
+
+// Host-side call blocks of the two fused families whose kernels keep parameter structs of their own: the launchers check them and copy fields.
+
+// Fused Swin MLP (swin_mlp.hip): y = res + fc2(GELU(fc1(x))) over M tokens of E features, HD hidden units
+struct SwinMlpCall {
+    const void* x; const void* w1; const float* b1; const void* w2; const float* b2;
+    const void* res;      // shortcut [M][ldres] or null
+    void* y;
+    int M, ldx, ldres, ldy, E, HD;
+    int NO;               // output features; 0 or E: the block alone.  Else (split storage only) + patch_unembed: `w2` is the product matrix
+                          // [NO][HD + E] (hi | lo), `b2` the merged bias, `res` null - the shortcut is the RAW `x`, so xcoef must be set
+    const float* xcoef;   // optional GroupNorm affine [B][2][E] (GNParams::coef): x is the raw tensor, HW tokens per image
+    int HW;
+    float* ystats;        // optional statistics of the stored output, one set per token tile (GNParams::cpartial)
+    int ystats_ld;
+    const GNTail* tail;   // optional GroupNorm tail (gn_tail.h; split storage only)
+};
+
+// Streaming attention of the autoencoder's AttnBlock (ae_attn.hip, ae_attn_split.hip): o = softmax(scale q k^T) v + bv for nz images of T tokens
+struct AeFlashCall {
+    const void* q; const void* k;   // [nz][T][ldq / ldk], C features
+    const void* vt;                 // [nz][C][T]
+    const float* bv;                // [C] or null
+    void* o;                        // [nz][T][ldo]
+    int ldq, ldk, ldo, nz, T, C;
+    float scale;
 };

@@ -442,8 +442,11 @@ int rs_unet_forward(rs_engine* e, const float* x, const int* t_host, const float
     return e->run(st, [&](Exec& ex) {
         View feat; const View* fp = nullptr;
         if (!e->fe_convs.empty()) { feat = e->g.feature_extract(ex, lq, mask, B, Hl, Wl, prec); fp = &feat; }
-        if (!mixed) e->g.unet_body(ex, x, 1.0f, fp, lq, mask, Hl, Wl, out, B, H, W, prec, rows[0]);
-        else e->g.unet_body(ex, x, 1.0f, fp, lq, mask, Hl, Wl, out, B, H, W, prec, e->g.film_table(ex, rows.data(), B), e->film_total);
+        Graphs::UNetCall u{};
+        u.x = x; u.xscale = 1.0f; u.lq_feat = fp; u.lq_nchw = lq; u.mask_nchw = mask; u.out = out; u.B = B; u.H = H; u.W = W; u.dt = prec;
+        u.film = mixed ? e->g.film_table(ex, rows.data(), B) : rows[0];
+        u.film_ld = mixed ? e->film_total : 0;
+        e->g.unet_body(ex, u);
     });
 }
 
@@ -462,7 +465,7 @@ int rs_vq_decode(rs_engine* e, const float* z, float* img, int32_t* idx_out, int
                  void* stream) {
     if (!e || !e->cfg.has_ae) return fail("engine has no autoencoder");
     hipStream_t st = (hipStream_t)stream;
-    return e->run(st, [&](Exec& ex) { e->g.decode_body(ex, z, 1.0f, img, idx_out, B, h, w, force_not_quantize, prec); });
+    return e->run(st, [&](Exec& ex) { e->g.decode_body(ex, Graphs::DecodeCall{z, 1.0f, img, idx_out, B, h, w, force_not_quantize, prec}); });
 }
 
 int rs_bicubic(rs_engine* e, const float* y, float* out, int B, int C, int H, int W, int sf, void* stream) {
@@ -557,11 +560,15 @@ static int sample_impl(rs_engine* e, const rs_sample_args* a, const rs_noise_key
             }
         e->g.sample_prologue(ex, a, z_y, xt, a->noise, keys, kd);
         std::vector<int> tb(B);
+        Graphs::StepCall sc{};
+        sc.xt = xt; sc.pred = pred; sc.y = a->y; sc.mask = a->mask; sc.B = B; sc.hz = hz; sc.wz = wz; sc.t = tb.data(); sc.a = a; sc.films = films.data();
+        sc.keys = keys; sc.keys_dev = kd;
         for (int i = a->steps - 1, k = 1; i >= 0; --i, ++k) {
-            const int pr = a->prec_unet[i];
             std::fill(tb.begin(), tb.end(), i);
-            e->g.sample_step(ex, xt, pred, e->fe_convs.empty() ? nullptr : &feat[pr], a->y, a->mask, a->h, a->w, B, hz, wz, pr, tb.data(), a, films.data(),
-                           keys ? nullptr : a->noise + (long long)k * zcount, keys, kd);
+            sc.prec = a->prec_unet[i];
+            sc.feat = e->fe_convs.empty() ? nullptr : &feat[sc.prec];
+            sc.noise = keys ? nullptr : a->noise + (long long)k * zcount;
+            e->g.sample_step(ex, sc);
         }
         e->g.sample_epilogue(ex, a, xt);
     });
@@ -637,7 +644,10 @@ static int sample_step_impl(rs_engine* e, const rs_step_args* s, const rs_noise_
         // (feature-extractor configs: the conditioning features of this batch, per call)
         View feat; const View* fp = nullptr;
         if (!e->fe_convs.empty()) { feat = e->g.feature_extract(ex, s->y, s->mask, B, a->h, a->w, s->prec); fp = &feat; }
-        e->g.sample_step(ex, s->x, pred, fp, s->y, s->mask, a->h, a->w, B, hz, wz, s->prec, s->t, a, films.data(), keys ? nullptr : s->noise, keys, kd);
+        Graphs::StepCall sc{};
+        sc.xt = s->x; sc.pred = pred; sc.feat = fp; sc.y = s->y; sc.mask = s->mask; sc.B = B; sc.hz = hz; sc.wz = wz; sc.prec = s->prec; sc.t = s->t;
+        sc.a = a; sc.films = films.data(); sc.noise = keys ? nullptr : s->noise; sc.keys = keys; sc.keys_dev = kd;
+        e->g.sample_step(ex, sc);
     });
 }
 

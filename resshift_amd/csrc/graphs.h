@@ -15,6 +15,9 @@
 //     decoder path writes into the lower slice (pixel stride = total channels).
 //   * FiLM vectors (time_embed + every ResBlock's emb_layers) depend only on t: computed once per
 //     distinct t on device and cached (rs_engine::film_row).
+//   * A conv of a graph is a ConvCall, built by name at its call site (Graphs::k3 / k1 + setters) and consumed whole by everything that
+//     plans, asks about or launches it; the other kernel families and the bodies take one parameter block each (common.h, Graphs::*Call).
+//   * Debug-trace names nest through Exec::Scope: a block's inner records under "<block>.", its output under the enclosing prefix.
 #pragma once
 #include "model.h"
 #include <algorithm>
@@ -35,6 +38,7 @@ struct View {
     // rest (column 0 of an st2 row = channel st_n0).  st2 == nullptr: `st` covers all C channels.
     float* st2 = nullptr; int st2S = 0, st2ld = 0, st_n0 = 0;
     bool stats_complete() const { return st != nullptr; }
+    void drop_stats() { st = nullptr; st2 = nullptr; st_prod = -1; }
     long long pixels() const { return (long long)B * H * W; }
     View slice(int c0, int c) const {
         View v = *this; v.p = (char*)p + (size_t)c0 * rs_dtype_chan_bytes(dt); v.C = c;
@@ -131,6 +135,14 @@ struct Exec {
     std::vector<TraceRec>* trace = nullptr;
     char* cap_base = nullptr; size_t cap_off = 0; long long trace_copies = 0;
     std::string prefix;
+    // a block's records go under "<enclosing prefix><name>."; the enclosing prefix comes back when the scope ends, so scopes nest
+    struct Scope {
+        Exec& ex; size_t keep;
+        Scope(Exec& e, const std::string& name) : ex(e), keep(e.prefix.size()) { ex.prefix += name + "."; }
+        Scope(const Scope&) = delete;
+        ~Scope() { ex.prefix.resize(keep); }
+    };
+    Scope scope(const std::string& name) { return Scope(*this, name); }
     void reset(size_t m) { arena->off = m; }
     void tr(const std::string& name, const View& v) {
         if (!tracing) return;
@@ -141,12 +153,16 @@ struct Exec {
         trace->push_back(TraceRec{prefix + name, v.B, v.C, v.H, v.W, o});
         ++trace_copies;
         const int rc = rs_nhwc_to_nchw_launch(v.p, v.dt, (float*)(cap_base + o), v.B, v.C, v.H * v.W, v.ld, 0, st);
-        if (rc != 0 && err == 0) fail(rc, "launch failed: debug trace copy of " + prefix + name);
+        if (rc != 0) fail(rc, "launch failed: debug trace copy of " + prefix + name);
     }
-    void fail(int rc, const std::string& text) { err = rc; rs_set_last_error(text.c_str(), rc); }
+    // the first error of a pass wins: its code and its text
+    void fail(int rc, const std::string& text) {
+        if (err) return;
+        err = rc; rs_set_last_error(text.c_str(), rc);
+    }
     void check(int rc, const char* what) {
         ++launches;
-        if (rc != 0 && err == 0) fail(rc, std::string("launch failed: ") + what);
+        if (rc != 0) fail(rc, std::string("launch failed: ") + what);
     }
     // MFMA implicit-GEMM launches are the roofline-relevant kernel family: count their algorithmic FLOPs
     // (2*M*N*K per batch entry, K = taps*Cin as in the usual conv FLOP count) and, when profiling is on, bracket
@@ -205,11 +221,12 @@ struct Exec {
         check(launch(), what);
         if (e1) (void)hipEventRecord(e1, st);
     }
-    // ... of the MFMA family: books `flops` under the input precision (slot 0 fp16, 1 fp32, 2 split), `fam_fl` + the shape tag under family f, the bytes
-    template <class L> void mfma(int slot, int f, double flops, double fam_fl, double bytes, long long M, int N, int K, int nz, const char* what, L launch) {
-        igemm_flops[slot] += flops;
-        fam_note(f, fam_fl, M, N, K, nz);
-        igemm_bytes += bytes;
+    // ... of the MFMA family: books `flops` under the input precision (slot 0 fp16, 1 fp32, 2 split), `fam_flops` + the shape tag under family `fam`, the bytes
+    struct MfmaNote { int slot, fam; double flops, fam_flops, bytes; long long M; int N, K, nz; };
+    template <class L> void mfma(const MfmaNote& n, const char* what, L launch) {
+        igemm_flops[n.slot] += n.flops;
+        fam_note(n.fam, n.fam_flops, n.M, n.N, n.K, n.nz);
+        igemm_bytes += n.bytes;
         ++igemm_launches;
         bracketed(prof, what, launch);
     }
@@ -222,7 +239,7 @@ struct Exec {
         const double isz = in_dt == RS_F16 ? 2.0 : 4.0, osz = out_dt == RS_F16 ? 2.0 : 4.0;
         const double src = (double)p.B * p.Hs * p.Ws * (double)(p.C0 + p.C1 + p.sC) * isz;
         const double out = (double)p.M * p.Cout * osz;
-        mfma(in_dt == RS_F16 ? 0 : (in_dt == RS_F16S ? 2 : 1), f, fl, fl, (double)nz * (src + (double)p.Cout * Kall * isz + out + (p.res ? out : 0.0)), p.M, p.Cout, Kall, nz,
+        mfma({in_dt == RS_F16 ? 0 : (in_dt == RS_F16S ? 2 : 1), f, fl, fl, (double)nz * (src + (double)p.Cout * Kall * isz + out + (p.res ? out : 0.0)), p.M, p.Cout, Kall, nz},
              what, [&] { return rs_conv_launch(&p, in_dt, out_dt, nz, &pl, st); });
         if (pl.splitk > 1) ++launches;   // (the slices' reduce kernel)
     }
@@ -231,198 +248,231 @@ struct Exec {
         const double M = (double)p.B * p.H * p.W;
         const int sp = dt == RS_F16S;
         const double fl = 2.0 * M * (p.wproj ? 4.0 : 3.0) * E * E;
-        mfma(sp ? 2 : 0, sp ? F_WINATTN_S : F_WINATTN, fl, 2.0 * M * (p.wproj ? 4.0 : 3.0) * E * E + 2.0 * 2.0 * M * 64.0 * E,   // + QK^T and PV of the 64-token windows
-             (sp ? 4.0 : 2.0) * (M * E * (p.res ? 3.0 : 2.0) + (p.wproj ? 4.0 : 3.0) * E * E), (long long)M, E, E, 1, sp ? "win_attn_qkv_split" : "win_attn_qkv",
+        mfma({sp ? 2 : 0, sp ? F_WINATTN_S : F_WINATTN, fl, 2.0 * M * (p.wproj ? 4.0 : 3.0) * E * E + 2.0 * 2.0 * M * 64.0 * E,   // + QK^T and PV of the 64-token windows
+              (sp ? 4.0 : 2.0) * (M * E * (p.res ? 3.0 : 2.0) + (p.wproj ? 4.0 : 3.0) * E * E), (long long)M, E, E, 1}, sp ? "win_attn_qkv_split" : "win_attn_qkv",
              [&] { return sp ? rs_win_attn_qkv_split_launch(&p, st) : rs_win_attn_qkv_launch(&p, st); });
     }
     // streaming AE attention (ae_attn.hip): QK^T and PV of nz images, q / k / v^T read once, o written once
-    void ae_flash(const void* q, int ldq, const void* k, int ldk, const void* vt, const float* bv, void* o, int ldo, int nz, int T, int C, float scale,
-                  int dt = RS_F16) {
+    void ae_flash(const AeFlashCall& c, int dt) {
         const int sp = dt == RS_F16S;
-        const double fl = 4.0 * (double)nz * (double)T * (double)T * (double)C;
-        mfma(sp ? 2 : 0, sp ? F_AEFLASH_S : F_AEFLASH, fl, fl, (sp ? 4.0 : 2.0) * 4.0 * (double)nz * T * C, T, T, C, nz, sp ? "ae_flash_attn_split" : "ae_flash_attn", [&] {
-            return sp ? rs_ae_flash_split_launch(q, ldq, k, ldk, vt, bv, o, ldo, nz, T, C, scale, st) : rs_ae_flash_launch(q, ldq, k, ldk, vt, bv, o, ldo, nz, T, C, scale, st);
-        });
+        const double fl = 4.0 * (double)c.nz * (double)c.T * (double)c.T * (double)c.C;
+        mfma({sp ? 2 : 0, sp ? F_AEFLASH_S : F_AEFLASH, fl, fl, (sp ? 4.0 : 2.0) * 4.0 * (double)c.nz * c.T * c.C, c.T, c.T, c.C, c.nz},
+             sp ? "ae_flash_attn_split" : "ae_flash_attn", [&] { return sp ? rs_ae_flash_split_launch(&c, st) : rs_ae_flash_launch(&c, st); });
     }
     // the fused Swin MLP belongs to the same MFMA family for the roofline bookkeeping: both GEMMs' FLOPs, compulsory bytes
-    void swin_mlp(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* res, void* y, int M, int ldx,
-                  int ldres, int ldy, int E, int HD, const float* xcoef = nullptr, int HW = 0, int dt = RS_F16, float* ystats = nullptr,
-                  int ystats_ld = 0, const GNTail* tail = nullptr, int NO = 0) {
-        const int sp = dt == RS_F16S;
-        if (NO <= 0) NO = E;   // (NO != E: patch_unembed folded in - fc1, then the product matrix over [h ; x])
+    void swin_mlp(const SwinMlpCall& c, int dt) {
+        const int sp = dt == RS_F16S, M = c.M, E = c.E, HD = c.HD;
+        const int NO = c.NO <= 0 ? E : c.NO;   // (NO != E: patch_unembed folded in - fc1, then the product matrix over [h ; x])
         const double fl = 2.0 * (double)M * ((double)E * HD + (double)NO * (NO != E ? HD + E : HD));
-        mfma(sp ? 2 : 0, sp ? F_SWINMLP_S : F_SWINMLP, fl, fl,
-             (sp ? 4.0 : 2.0) * ((double)M * (E * ((res || NO != E) ? 2.0 : 1.0) + NO) + (double)E * HD + (double)NO * (NO != E ? HD + E : HD)), M, NO, HD, 1,
-             sp ? "swin_mlp_split" : "swin_mlp", [&] {
-                 return sp ? rs_swin_mlp_split_launch_n(x, w1, b1, w2, b2, res, y, M, ldx, ldres, ldy, E, HD, NO, xcoef, HW, ystats, ystats_ld, tail, st)
-                           : rs_swin_mlp_launch(x, w1, b1, w2, b2, res, y, M, ldx, ldres, ldy, E, HD, xcoef, HW, ystats, ystats_ld, st);
-             });
+        mfma({sp ? 2 : 0, sp ? F_SWINMLP_S : F_SWINMLP, fl, fl,
+              (sp ? 4.0 : 2.0) * ((double)M * (E * ((c.res || NO != E) ? 2.0 : 1.0) + NO) + (double)E * HD + (double)NO * (NO != E ? HD + E : HD)), M, NO, HD, 1},
+             sp ? "swin_mlp_split" : "swin_mlp", [&] { return sp ? rs_swin_mlp_split_launch(&c, st) : rs_swin_mlp_launch(&c, st); });
+    }
+};
+
+// One convolution of the graph, one value from plan to launch: the layer's weights, its views, the geometry, what the launch fuses in, and the
+// ConvPlan made from exactly these fields (rs_conv_plan: the kernel, its split-K factor, the statistics it can leave).  Every field that feeds
+// the plan is private and changes only through a setter that drops the plan; plan() makes it again on demand, so want_stats(), fuses_gn(),
+// Graphs::skip_fold(), Graphs::gn_silu_conv3() and launch() all see the one plan of the arguments that are launched, made once.  The dry and
+// the real pass get the same plan: it depends on the layout only.
+class ConvCall {
+    const ConvW* w_;
+    bool big_;                            // |w| >= 30 (Model::big): no 2^11 scaling of the hi fragment - the generic split kernel takes it
+    View x_, y_, x1_, res_, skx_;         // (x1_ / res_ / skx_ count only with two_ / has_res_ / skw_: a dry pass's pointers are all null)
+    bool two_ = false, has_res_ = false;
+    const ConvW* skw_ = nullptr;          // folded 1x1 shortcut (IGemmParams::sx) over the block input skx_
+    int stride_ = 1, pad_t_, pad_l_, up_ = 1, act_ = 0;
+    int osc_ = 0, ooy_ = 0, oox_ = 0;     // the scattered rows of the sub-pixel form (IGemmParams::osc)
+    // what only the launch reads: no part of the plan, free to set at any time
+    float out_scale_ = 1.f;
+    const float* xcoef_ = nullptr; int xact_ = RS_ACT_NONE;
+    mutable ConvPlan plan_{}; mutable bool planned_ = false;
+    ConvCall& replan() { planned_ = false; return *this; }
+    int rows() const { return osc_ == 2 ? y_.H / 2 : y_.H; }   // the grid a launch computes: the low-resolution one of the sub-pixel form
+    int cols() const { return osc_ == 2 ? y_.W / 2 : y_.W; }
+
+public:
+    // the layer's KH x KW taps at stride 1 with `pad` zeros on every side (Graphs::k3 / k1)
+    ConvCall(const ConvW& w, bool big, const View& x, const View& y, int pad) : w_(&w), big_(big), x_(x), y_(y), pad_t_(pad), pad_l_(pad) {}
+    // stride s with `pad` zeros above and to the left (below / right: whatever the output size implies - F.pad(x,(0,1,0,1)) + pad 0 is pad = 0)
+    ConvCall& strided(int s, int pad) { stride_ = s; pad_t_ = pad_l_ = pad; return replan(); }
+    ConvCall& upsampled() { up_ = 2; return replan(); }   // nearest x2 folded into the conv's addressing
+    ConvCall& act(int a) { act_ = a; return replan(); }
+    ConvCall& source(const View& x) { x_ = x; two_ = false; return replan(); }
+    ConvCall& second_source(const View& x1) { x1_ = x1; two_ = true; return replan(); }   // channels concatenated after x
+    ConvCall& residual(const View& r) { res_ = r; has_res_ = true; return replan(); }
+    ConvCall& shortcut(const ConvW& skw, const View& skx) { skw_ = &skw; skx_ = skx; return replan(); }
+    ConvCall& no_shortcut() { skw_ = nullptr; return replan(); }
+    // class (py, px) of the sub-pixel form of "nearest x2 + conv3x3": a 2x2 conv over the low-resolution grid whose rows go to the pixels of that parity
+    ConvCall& subpixel(int py, int px) { osc_ = 2; ooy_ = py; oox_ = px; pad_t_ = 1 - py; pad_l_ = 1 - px; return replan(); }
+    // ... and another class of the same form: its weights and parity, and THIS call's plan - the four launches have one shape
+    ConvCall sibling(const ConvW& w, int py, int px) const {
+        (void)plan();
+        ConvCall c = *this;
+        c.w_ = &w; c.ooy_ = py; c.oox_ = px; c.pad_t_ = 1 - py; c.pad_l_ = 1 - px;
+        return c;
+    }
+    ConvCall& out_scale(float s) { out_scale_ = s; return *this; }
+    // act(x * coef[b][0][c] + coef[b][1][c]) is what the conv sees (halo and Winograd kernels: fuses_gn())
+    ConvCall& input_transform(const float* coef, int act) { xcoef_ = coef; xact_ = act; return *this; }
+
+    const View& x() const { return x_; }
+    const View& y() const { return y_; }   // (after want_stats(): with the statistics buffer the launch fills)
+    const View& shortcut_x() const { return skx_; }
+    bool has_shortcut() const { return skw_ != nullptr; }
+
+    // THE place that turns the call into the parameter block of an implicit-GEMM launch, for the planner and for launch() (which adds the
+    // split-K slabs, the statistics and the tail: state of the pass, not of the call)
+    IGemmParams params() const {
+        const ConvW& w = *w_;
+        const int C1 = two_ ? x1_.C : 0;
+        IGemmParams p{};
+        p.x0 = x_.p; p.x1 = two_ ? x1_.p : nullptr; p.w = w.w_for(x_.dt); p.bias = w.bias;
+        p.res = has_res_ ? res_.p : nullptr; p.y = y_.p;
+        p.C0 = x_.C; p.C1 = C1; p.ld0 = x_.ld; p.ld1 = two_ ? x1_.ld : 0;
+        p.B = x_.B; p.Hs = x_.H; p.Ws = x_.W; p.up = up_; p.Ho = rows(); p.Wo = cols(); p.KH = w.KH; p.KW = w.KW;
+        p.stride = stride_; p.pad_t = pad_t_; p.pad_l = pad_l_; p.Cout = w.Cout; p.ldy = y_.ld; p.ldres = has_res_ ? res_.ld : 0;
+        p.M = y_.B * rows() * cols(); p.Ktot = w.KH * w.KW * (x_.C + C1); p.act = act_; p.out_scale = out_scale_;
+        p.splitk = 1;
+        p.ww = (x_.dt == RS_F16S && !two_) ? w.ww : nullptr;
+        p.unscaled_w = (x_.dt == RS_F16S && big_) ? 1 : 0;
+        p.xcoef = xcoef_; p.xact = xact_;
+        if (skw_) { p.sx = skx_.p; p.sw = skw_->w_for(x_.dt); p.sbias = skw_->bias; p.sC = skx_.C; p.sld = skx_.ld; }
+        p.osc = osc_; p.ooy = ooy_; p.oox = oox_;
+        return p;
+    }
+    const ConvPlan& plan() const {
+        if (planned_) return plan_;
+        plan_ = ConvPlan{};   // (CK_NONE: the direct kernel, or a launch that launch() refuses)
+        planned_ = true;
+        if (w_->direct || x_.C + (two_ ? x1_.C : 0) != w_->CinP) return plan_;
+        const IGemmParams p = params();
+        (void)rs_conv_plan(&p, x_.dt, y_.dt, 1, &plan_);
+        return plan_;
+    }
+    // the conv can apply a GroupNorm affine + SiLU to its input while the tile sits in LDS
+    bool fuses_gn() const { const int k = plan().kernel; return k == CK_WINO || k == CK_HALO || k == CK_HALO_SEG; }
+    // Attach a statistics buffer to the output IF the planned kernel can leave them: the halo kernel (one partial set per 256- or 128-pixel
+    // tile of one image), the generic split-storage kernel (RS_GN_GEN_STATS, default on: one set per 128- / 64-pixel tile), or - split-K
+    // launches of either - the reduce kernel (slabs of 256 pixels / the whole small image).  The sub-pixel form: the generic split kernel
+    // only, one slab per low-resolution pixel tile and parity class.  The buffer lives in the coefficient pool (reset per network body), so
+    // a block's output may carry it to whoever consumes it later (the next block, the decoder's concatenation).
+    void want_stats(Exec& ex) {
+        const ConvPlan& pl = plan();
+        const bool sub = osc_ == 2;
+        const int HW = rows() * cols(), spx = pl.stats_px;
+        y_.drop_stats();
+        if (!rs_knob_gn_epi_stats() || (pl.kernel == CK_SPLIT && !rs_knob_gn_gen_stats()) || (sub && pl.kernel != CK_SPLIT) || spx <= 0 || (HW % spx)) return;
+        ex.attach_stats(y_, (sub ? 4 : 1) * (HW / spx), y_.C);
+    }
+    // `shared`: the tail of a group of launches that fill ONE statistics buffer (the sub-pixel form); null: this launch draws its own
+    void launch(Exec& ex, const GNTail* shared = nullptr) const {
+        const ConvW& w = *w_;
+        const int C1 = two_ ? x1_.C : 0;
+        // split storage has no two-source implicit GEMM: gather the channel concatenation once (only the first conv of the
+        // feature-extractor configs, unet.py:882)
+        if (!w.direct && two_ && x_.dt == RS_F16S) {
+            View xcat = ex.T(x_.B, x_.H, x_.W, x_.C + C1, x_.dt);
+            if (!ex.dry) {
+                ex.check(rs_copy_channels_launch(x_.p, x_.ld, xcat.p, xcat.ld, x_.C, x_.pixels(), x_.dt, ex.st), "concat copy");
+                ex.check(rs_copy_channels_launch(x1_.p, x1_.ld, xcat.slice(x_.C, C1).p, xcat.ld, C1, x_.pixels(), x_.dt, ex.st), "concat copy");
+            }
+            // the gathered tensor is another layout with another plan: what was decided on the two-source plan does not carry over (statistics
+            // that the new plan cannot serve are refused by the launch itself)
+            if (xcoef_ || skw_) { ex.fail(-3, "two-source conv in split storage cannot take an input transform or a folded shortcut"); return; }
+            ConvCall(*this).source(xcat).launch(ex, shared);
+            return;
+        }
+        const ConvPlan& pl = plan();
+        // split-K for launches that cannot fill the chip (8x8 / 16x16 UNet levels): fp32 slabs live in the arena
+        float* const partial = pl.splitk > 1 ? (float*)ex.raw((size_t)pl.splitk * y_.B * y_.H * y_.W * w.Cout * sizeof(float)) : nullptr;
+        if (ex.dry) return;
+        if (x_.C + C1 != w.CinP) { ex.fail(-3, "conv input channels do not match the packed weights"); return; }
+        if (w.direct) {
+            DirectConvParams p{};
+            p.x0 = x_.p; p.x1 = two_ ? x1_.p : nullptr; p.w = w.wd; p.bias = w.bias; p.y = y_.p;
+            p.C0 = x_.C; p.C1 = C1; p.ld0 = x_.ld; p.ld1 = two_ ? x1_.ld : 0;
+            p.B = x_.B; p.Hs = x_.H; p.Ws = x_.W; p.up = up_; p.Ho = y_.H; p.Wo = y_.W; p.KH = w.KH; p.KW = w.KW;
+            p.stride = stride_; p.pad_t = pad_t_; p.pad_l = pad_l_; p.Cout = w.Cout; p.ldy = y_.ld; p.act = act_;
+            if (has_res_) { ex.fail(-3, "direct conv has no residual path"); return; }
+            ex.check(rs_direct_conv_launch(&p, x_.dt, y_.dt, ex.st), "direct_conv");
+            return;
+        }
+        IGemmParams p = params();
+        p.partial = partial;
+        if (y_.st) {   // statistics for the consuming GroupNorm: the kernel's epilogue or its split-K reduce (want_stats() asked the same plan)
+            if (!pl.stats_px) { ex.fail(-3, "output statistics requested from a conv whose kernel cannot produce them"); return; }
+            p.ystats = y_.st; p.ystats_ld = y_.stld;
+            if (shared) p.tail = *shared;
+            else (void)ex.fill_tail(y_.st_prod, y_.B, p.tail);   // ... and that GroupNorm's coefficients too (gn_tail.h)
+        }
+        if (!p.w) { ex.fail(-3, "weights for this precision were not packed (enable_f16/enable_f32/enable_split)"); return; }
+        ex.igemm(p, pl, x_.dt, y_.dt, 1, "igemm");
     }
 };
 
 // The graphs themselves: they read the model and drive an Exec, nothing else
 struct Graphs {
     const Model& m;
+    // ---------------------------------------------------------------- ops
+    ConvCall k3(const ConvW& w, const View& x, const View& y) const { return ConvCall(w, m.big(w), x, y, 1); }   // 3x3 (any KH x KW), pad 1
+    ConvCall k1(const ConvW& w, const View& x, const View& y) const { return ConvCall(w, m.big(w), x, y, 0); }   // 1x1 / linear, pad 0
+    // a conv whose epilogue also leaves the statistics (+ coefficients) for the GroupNorm that consumes its output: the output view, with them
+    View conv_for_gn(Exec& ex, ConvCall c, bool stats = true) {
+        if (stats) c.want_stats(ex);
+        c.launch(ex);
+        return c.y();
+    }
     // the four launches of the sub-pixel form: x [B,H,W,C] -> y [B,2H,2W,C].  Taken when the low-resolution grid alone fills the chip
     // (the 8 x 8 -> 16 x 16 and 16 x 16 -> 32 x 32 steps at batch 32 do not: they keep the folded-address form).
-    bool upfold_ok(const Exec& ex, const ConvW (&upf)[4], const View& x, const View& y) const {
+    bool upfold_ok(const ConvW (&upf)[4], const View& x, const View& y) const {
         if (x.dt != y.dt || (x.dt != RS_F16 && x.dt != RS_F16S) || y.H != 2 * x.H || y.W != 2 * x.W || x.C != upf[0].CinP) return false;
         if (!upf[0].w_for(x.dt) || (x.ld % 8) || (y.ld % 8)) return false;   // (the scattered-row launches' alignment preconditions)
         // (measured, profiles/r5_upfold_ab.txt: with the 16 -> 32 and 8 -> 16 steps as well - 8192 / 2048 low-resolution pixels at batch 32, four
         // launches that cannot fill the chip each - the pass is 0.9 ms slower than with the 32 -> 64 step alone)
         return (long long)x.B * x.H * x.W >= 16384;
     }
-    // the plan of each of the four launches (same shape, scattered rows: osc)
-    ConvPlan upfold_plan(const ConvW (&upf)[4], const View& x, const View& y) const {
-        View yl = y; yl.H = x.H; yl.W = x.W;   // a launch computes the low-resolution grid; its rows are scattered into y
-        IGemmParams p = conv_params(upf[0], x, nullptr, yl, 1, 1, 1, 1, 0, nullptr, 1.f);
-        p.osc = 2;
-        ConvPlan pl{};
-        (void)rs_conv_plan(&p, x.dt, y.dt, 1, &pl);
-        return pl;
-    }
-    // statistics of y for the consuming GroupNorm from the four launches' epilogues (split storage): one slab per low-resolution pixel tile
-    // and parity class
-    void upfold_want_stats(Exec& ex, const ConvPlan& pl, const View& x, View& y) {
-        y.st = nullptr; y.st2 = nullptr; y.st_prod = -1;
-        const int spx = pl.stats_px;
-        if (!rs_knob_gn_epi_stats() || !rs_knob_gn_gen_stats() || pl.kernel != CK_SPLIT || spx <= 0 || ((x.H * x.W) % spx)) return;
-        ex.attach_stats(y, 4 * (x.H * x.W / spx), y.C);
-    }
-    void upfold_conv(Exec& ex, const ConvPlan& pl, const ConvW (&upf)[4], const View& x, const View& y) {
-        if (ex.dry) return;
+    // ... as four calls that share class 0's plan, ONE statistics buffer and ONE tail (one ticket per image); returns y (with the statistics)
+    View upfold(Exec& ex, const ConvW (&upf)[4], const View& x, const View& y, bool stats) {
+        ConvCall c0 = k3(upf[0], x, y).subpixel(0, 0);
+        if (stats) c0.want_stats(ex);
+        if (ex.dry) return c0.y();
         GNTail tl{};
-        if (y.st) (void)ex.fill_tail(y.st_prod, y.B, tl);   // ONE tail (one ticket per image) for the four launches
-        for (int q = 0; q < 4; ++q) {
-            const int py = q >> 1, px = q & 1;
-            View yl = y; yl.H = x.H; yl.W = x.W;
-            IGemmParams p = conv_params(upf[q], x, nullptr, yl, 1, 1 - py, 1 - px, 1, 0, nullptr, 1.f);
-            p.osc = 2; p.ooy = py; p.oox = px;
-            if (y.st) { p.ystats = y.st; p.ystats_ld = y.stld; p.tail = tl; }
-            if (!p.w) { ex.fail(-3, "weights for this precision were not packed (enable_f16/enable_f32/enable_split)"); return; }
-            ex.igemm(p, pl, x.dt, y.dt, 1, "igemm");
-        }
-    }
-    // ---------------------------------------------------------------- ops
-    // parameter block of one implicit-GEMM conv launch: the layout and the planning inputs (plan_conv()); conv() adds what only the launch needs
-    IGemmParams conv_params(const ConvW& w, const View& x, const View* x1, const View& y, int stride, int pad_t, int pad_l, int up,
-                            int act, const View* res, float out_scale) const {
-        const int C1 = x1 ? x1->C : 0;
-        IGemmParams p{};
-        p.x0 = x.p; p.x1 = x1 ? x1->p : nullptr; p.w = w.w_for(x.dt); p.bias = w.bias;
-        p.res = res ? res->p : nullptr; p.y = y.p;
-        p.C0 = x.C; p.C1 = C1; p.ld0 = x.ld; p.ld1 = x1 ? x1->ld : 0;
-        p.B = x.B; p.Hs = x.H; p.Ws = x.W; p.up = up; p.Ho = y.H; p.Wo = y.W; p.KH = w.KH; p.KW = w.KW;
-        p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l; p.Cout = w.Cout; p.ldy = y.ld; p.ldres = res ? res->ld : 0;
-        p.M = y.B * y.H * y.W; p.Ktot = w.KH * w.KW * (x.C + C1); p.act = act; p.out_scale = out_scale;
-        p.splitk = 1;
-        p.ww = (x.dt == RS_F16S && !x1) ? w.ww : nullptr;
-        p.unscaled_w = (x.dt == RS_F16S && m.big(w)) ? 1 : 0;   // |w| >= 30: no 2^11 scaling of the hi fragment - the generic split kernel takes it
-        return p;
-    }
-    // The plan of the launch conv() makes for these arguments (rs_conv_plan: the kernel, its split-K factor, the statistics it can leave).
-    // A conv is planned ONCE: by its call site, which hands the plan to want_stats() / skip_fold() / gn_silu_conv3() / conv(), or by conv()
-    // itself.  The dry and the real pass get the same plan: it depends on the layout only.  On the halo and Winograd kernels the conv can
-    // apply a GroupNorm affine + SiLU to its input while the tile sits in LDS (fuses_gn()); `skx`: the block input of a folded 1x1 shortcut.
-    ConvPlan plan_conv(const ConvW& w, const View& x, const View* x1, const View& y, int stride, int pad_t, int pad_l, int up, int act,
-                       const View* res, const View* skx = nullptr) const {
-        ConvPlan pl{};   // (CK_NONE: the direct kernel, or a launch that conv() refuses)
-        if (w.direct || x.C + (x1 ? x1->C : 0) != w.CinP) return pl;
-        IGemmParams p = conv_params(w, x, x1, y, stride, pad_t, pad_l, up, act, res, 1.f);
-        if (skx) { p.sC = skx->C; p.sld = skx->ld; }
-        (void)rs_conv_plan(&p, x.dt, y.dt, 1, &pl);
-        return pl;
-    }
-    ConvPlan plan3(const ConvW& w, const View& x, const View& y, const View* res, const View* skx = nullptr) const { return plan_conv(w, x, nullptr, y, 1, 1, 1, 1, 0, res, skx); }
-    static bool fuses_gn(const ConvPlan& pl) { return pl.kernel == CK_WINO || pl.kernel == CK_HALO || pl.kernel == CK_HALO_SEG; }
-    void conv(Exec& ex, const ConvW& w, const View& x, const View* x1, const View& y, int stride, int pad_t, int pad_l, int up,
-              int act, const View* res, float out_scale = 1.f, const float* xcoef = nullptr, int xact = RS_ACT_NONE,
-              const ConvW* skw = nullptr, const View* skx = nullptr, const ConvPlan* plan = nullptr) {
-        const int C1 = x1 ? x1->C : 0;
-        // split storage has no two-source implicit GEMM: gather the channel concatenation once (only the first conv of the
-        // feature-extractor configs, unet.py:882)
-        if (!w.direct && x1 && x.dt == RS_F16S) {
-            View xcat = ex.T(x.B, x.H, x.W, x.C + C1, x.dt);
-            if (!ex.dry) {
-                ex.check(rs_copy_channels_launch(x.p, x.ld, xcat.p, xcat.ld, x.C, x.pixels(), x.dt, ex.st), "concat copy");
-                ex.check(rs_copy_channels_launch(x1->p, x1->ld, xcat.slice(x.C, C1).p, xcat.ld, C1, x.pixels(), x.dt, ex.st), "concat copy");
-            }
-            conv(ex, w, xcat, nullptr, y, stride, pad_t, pad_l, up, act, res, out_scale);
-            return;
-        }
-        const ConvPlan pl = plan ? *plan : plan_conv(w, x, x1, y, stride, pad_t, pad_l, up, act, res, skw ? skx : nullptr);
-        // split-K for launches that cannot fill the chip (8x8 / 16x16 UNet levels): fp32 slabs live in the arena
-        float* const partial = pl.splitk > 1 ? (float*)ex.raw((size_t)pl.splitk * y.B * y.H * y.W * w.Cout * sizeof(float)) : nullptr;
-        if (ex.dry) return;
-        if (x.C + C1 != w.CinP) { if (!ex.err) { ex.fail(-3, "conv input channels do not match the packed weights"); } return; }
-        if (w.direct) {
-            DirectConvParams p{};
-            p.x0 = x.p; p.x1 = x1 ? x1->p : nullptr; p.w = w.wd; p.bias = w.bias; p.y = y.p;
-            p.C0 = x.C; p.C1 = C1; p.ld0 = x.ld; p.ld1 = x1 ? x1->ld : 0;
-            p.B = x.B; p.Hs = x.H; p.Ws = x.W; p.up = up; p.Ho = y.H; p.Wo = y.W; p.KH = w.KH; p.KW = w.KW;
-            p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l; p.Cout = w.Cout; p.ldy = y.ld; p.act = act;
-            if (res) { ex.fail(-3, "direct conv has no residual path"); return; }
-            ex.check(rs_direct_conv_launch(&p, x.dt, y.dt, ex.st), "direct_conv");
-        } else {
-            IGemmParams p = conv_params(w, x, x1, y, stride, pad_t, pad_l, up, act, res, out_scale);
-            p.partial = partial;
-            p.xcoef = xcoef; p.xact = xact;
-            if (skw) { p.sx = skx->p; p.sw = skw->w_for(x.dt); p.sbias = skw->bias; p.sC = skx->C; p.sld = skx->ld; }   // folded 1x1 shortcut (skip_fold()): the halo kernel's
-            if (y.st) {   // statistics for the consuming GroupNorm: the kernel's epilogue or its split-K reduce (want_stats() asked the same plan)
-                if (!pl.stats_px) { ex.fail(-3, "output statistics requested from a conv whose kernel cannot produce them"); return; }
-                p.ystats = y.st; p.ystats_ld = y.stld;
-                (void)ex.fill_tail(y.st_prod, y.B, p.tail);   // ... and that GroupNorm's coefficients too (gn_tail.h)
-            }
-            if (!p.w) { ex.fail(-3, "weights for this precision were not packed (enable_f16/enable_f32/enable_split)"); return; }
-            ex.igemm(p, pl, x.dt, y.dt, 1, "igemm");
-        }
+        if (c0.y().st) (void)ex.fill_tail(c0.y().st_prod, y.B, tl);
+        for (int q = 0; q < 4; ++q) c0.sibling(upf[q], q >> 1, q & 1).launch(ex, &tl);
+        return c0.y();
     }
     void zero(Exec& ex, const View& v) {
         if (ex.dry) return;
         const hipError_t e = hipMemsetAsync(v.p, 0, (size_t)v.B * v.H * v.W * v.ld * rs_dtype_size(v.dt), ex.st);
         ex.check(e == hipSuccess ? 0 : -1, "memset");
     }
-    void conv3(Exec& ex, const ConvW& w, const View& x, const View& y, const View* res = nullptr, int act = 0, const float* xcoef = nullptr,
-               int xact = RS_ACT_NONE, const ConvW* skw = nullptr, const View* skx = nullptr, const ConvPlan* plan = nullptr) {
-        conv(ex, w, x, nullptr, y, 1, 1, 1, 1, act, res, 1.f, xcoef, xact, skw, skx, plan);
-    }
     // A ResBlock's 1x1 shortcut (models/unet.py:178-183,205-206; ldm/modules/diffusionmodules/model.py:121-127,148-149) as extra K columns
     // of its second 3x3 conv (IGemmParams::sx) instead of a GEMM launch + a tensor + a residual read: split storage on the halo kernel's
     // 8-wave big-plane tiles, whole 32-channel chunks of the block input, no weight that needs the unscaled path.  RS_SKIP_FOLD=0: off.
-    // `pl`: conv2's plan WITH the shortcut folded in (plan3(r.c2, h1, Y, nullptr, &X)).
-    bool skip_fold(const ResBlockW& r, const View& X, const View& Y, const ConvPlan& pl) const {
+    // `c2`: conv2 WITH the shortcut in it.
+    bool skip_fold(const ResBlockW& r, const ConvCall& c2) const {
         static const bool on = rs_env_on("RS_SKIP_FOLD");
         static const bool on16 = rs_env_on("RS_SKIP_FOLD_F16");   // (fp16 storage: the decoder's nin_shortcuts, the fp16 policy's UNet)
+        const View &X = c2.shortcut_x(), &Y = c2.y();
         if (!on || !rs_knob_gn_conv_fold() || !r.has_skip || (X.dt != RS_F16S && !(X.dt == RS_F16 && on16)) || Y.dt != X.dt) return false;
         if (X.dt == RS_F16S && (m.big(r.skip) || m.big(r.c2))) return false;
         if (!r.skip.w_for(X.dt) || r.skip.KH != 1 || X.C != r.skip.CinP || (X.C % 32) || (X.ld % 8) || X.H != Y.H || X.W != Y.W) return false;
-        return pl.kernel == CK_HALO;   // (the HALO kernel's big-plane tiles, no split-K: the fold - a GEMM launch saved - beats the Winograd kernel's 10 %)
-    }
-    // Attach a statistics buffer to a tensor that is about to be produced by the conv planned as `pl` IF its kernel can leave them: the halo
-    // kernel (one partial set per 256- or 128-pixel tile of one image), the generic split-storage kernel (RS_GN_GEN_STATS, default on: one
-    // set per 128- / 64-pixel tile), or - split-K launches of either - the reduce kernel (slabs of 256 pixels / the whole small image).
-    // The buffer lives in the coefficient pool (reset per network body), so a block's output may carry it to whoever consumes it later
-    // (the next block, the decoder's concatenation).
-    void want_stats(Exec& ex, const ConvPlan& pl, View& y) {
-        const int HW = y.H * y.W, spx = pl.stats_px;
-        y.st = nullptr; y.st2 = nullptr; y.st_prod = -1;
-        if (!rs_knob_gn_epi_stats() || (pl.kernel == CK_SPLIT && !rs_knob_gn_gen_stats()) || spx <= 0 || (HW % spx)) return;
-        ex.attach_stats(y, HW / spx, y.C);
+        return c2.plan().kernel == CK_HALO;   // (the HALO kernel's big-plane tiles, no split-K: the fold - a GEMM launch saved - beats the Winograd kernel's 10 %)
     }
     // GroupNorm (+FiLM) + SiLU + 3x3 conv (models/unet.py:128-147,198-203; ldm/modules/diffusionmodules/model.py:129-147): on the
     // halo kernel the GroupNorm only produces per-(image, channel) affine coefficients and the conv applies them to the RAW tensor
     // in LDS (bit-identical to normalising first); otherwise normalise into a scratch tensor and convolve that
-    void gn_silu_conv3(Exec& ex, const ConvPlan& pl, const GNW& g, const ConvW& w, const View& X, const View& Y, float eps, const float* film,
-                       const View* res, const ConvW* skw = nullptr, const View* skx = nullptr) {
-        if (rs_knob_gn_conv_fold() && fuses_gn(pl)) {
-            const float* coef = gn_coef(ex, g, X, eps, film);
-            conv3(ex, w, X, Y, res, 0, coef, RS_ACT_SILU, skw, skx, &pl);
+    void gn_silu_conv3(Exec& ex, ConvCall& c, const GNW& g, float eps, const float* film) {
+        if (rs_knob_gn_conv_fold() && c.fuses_gn()) {
+            c.input_transform(gn_coef(ex, g, c.x(), eps, film), RS_ACT_SILU).launch(ex);
             return;
         }
-        if (skw) { if (!ex.err) { ex.fail(-3, "folded shortcut planned for a conv that does not run on the halo kernel"); } return; }
+        if (c.has_shortcut()) { ex.fail(-3, "folded shortcut planned for a conv that does not run on the halo kernel"); return; }
+        const View X = c.x();
         View t = ex.T(X.B, X.H, X.W, X.C, X.dt);
         gn(ex, g, X, t, eps, RS_ACT_SILU, film);
-        conv3(ex, w, t, Y, res);   // (another launch - the dense scratch tensor is its input: conv() plans it)
+        c.source(t).launch(ex);   // (another launch - the dense scratch tensor is its input: planned again)
     }
     // GroupNorm + SiLU + conv3x3 to <= 4 channels (the UNet's `out`, Encoder / Decoder norm_out + conv_out) -> fp32 NHWC `o`: one fused pass
     // (gn_silu_head_conv_kernel) over the raw tensor with the GroupNorm as coefficients; RS_HEAD_FUSED=0: normalise, then
@@ -437,17 +487,8 @@ struct Graphs {
         const size_t mk = ex.mark();
         View t = ex.T(X.B, X.H, X.W, X.C, X.dt);
         gn(ex, g, X, t, eps, RS_ACT_SILU);
-        conv(ex, w, t, nullptr, o, 1, 1, 1, 1, 0, nullptr);
+        k3(w, t, o).launch(ex);
         ex.reset(mk);
-    }
-    // a conv whose epilogue also leaves the statistics (+ coefficients) for the GroupNorm that consumes y: one plan for want_stats() and conv()
-    void conv_st(Exec& ex, const ConvW& w, const View& x, View& y, int stride, int pad, int up, const View* res = nullptr, bool stats = true) {
-        const ConvPlan pl = plan_conv(w, x, nullptr, y, stride, pad, pad, up, 0, res);
-        if (stats) want_stats(ex, pl, y);
-        conv(ex, w, x, nullptr, y, stride, pad, pad, up, 0, res, 1.f, nullptr, RS_ACT_NONE, nullptr, nullptr, &pl);
-    }
-    void conv1(Exec& ex, const ConvW& w, const View& x, const View& y, const View* res = nullptr, int act = 0) {
-        conv(ex, w, x, nullptr, y, 1, 0, 0, 1, act, res);
     }
     // The per-(image, channel) affine [B][2][C] of a GroupNorm whose consumer applies it while loading x (halo conv, fused Swin kernels).
     // Three ways to get it, cheapest first: the launch that produced x's statistics wrote it already (tail, planned by the dry pass);
@@ -513,25 +554,23 @@ struct Graphs {
     void resblock(Exec& ex, const ResBlockW& r, const View& X, View& Y, const float* film_row, bool out_stats = true, float eps = 1e-5f) {
         const size_t mk = ex.mark();
         View h1 = ex.T(X.B, X.H, X.W, r.Cout, X.dt);
-        const ConvPlan p1 = plan3(r.c1, X, h1, nullptr);
-        want_stats(ex, p1, h1);   // conv1's epilogue leaves the statistics norm2 needs
-        gn_silu_conv3(ex, p1, r.n1, r.c1, X, h1, eps, nullptr, nullptr);
+        ConvCall c1 = k3(r.c1, X, h1);
+        c1.want_stats(ex);   // conv1's epilogue leaves the statistics norm2 needs
+        gn_silu_conv3(ex, c1, r.n1, eps, nullptr);
+        h1 = c1.y();
         ex.tr("conv1", h1);
         const float* film = film_row ? film_row + r.film_off : nullptr;
         // the shortcut: folded into conv2 (skip_fold()), a 1x1 conv whose output conv2 adds, or the block input itself
-        const View* res = &X;
-        View sk;
-        ConvPlan p2 = r.has_skip ? plan3(r.c2, h1, Y, nullptr, &X) : ConvPlan{};
-        const bool folded = r.has_skip && skip_fold(r, X, Y, p2);
-        if (folded) res = nullptr;
-        else if (r.has_skip) {
-            sk = ex.T(X.B, X.H, X.W, r.Cout, X.dt);
-            conv1(ex, r.skip, X, sk);
-            res = &sk;
+        ConvCall c2 = k3(r.c2, h1, Y);
+        if (!r.has_skip) c2.residual(X);
+        else if (!skip_fold(r, c2.shortcut(r.skip, X))) {
+            View sk = ex.T(X.B, X.H, X.W, r.Cout, X.dt);
+            k1(r.skip, X, sk).launch(ex);
+            c2.no_shortcut().residual(sk);
         }
-        if (!folded) p2 = plan3(r.c2, h1, Y, res);
-        if (out_stats) want_stats(ex, p2, Y);
-        gn_silu_conv3(ex, p2, r.n2, r.c2, h1, Y, eps, film, res, folded ? &r.skip : nullptr, folded ? &X : nullptr);
+        if (out_stats) c2.want_stats(ex);
+        gn_silu_conv3(ex, c2, r.n2, eps, film);
+        Y = c2.y();
         ex.reset(mk);
     }
     // ldm/modules/diffusionmodules/model.py:129-149 (temb=None), GroupNorm eps 1e-6 (model.py:46-47)
@@ -541,7 +580,7 @@ struct Graphs {
         const size_t mk = ex.mark();
         const int E = b.E, heads = m.cfg.unet.num_heads;
         View e = ex.T(X.B, X.H, X.W, E, X.dt);
-        conv_st(ex, b.embed, X, e, 1, 0, 1);   // patch_embed's epilogue: statistics (+ coefficients) for the first block's norm1
+        e = conv_for_gn(ex, k1(b.embed, X, e));   // patch_embed's epilogue: statistics (+ coefficients) for the first block's norm1
         ex.tr("embed", e);
         int bi = 0;
         for (const SwinBlockW& s : b.blocks) {
@@ -564,7 +603,7 @@ struct Graphs {
             View qkv;
             if (!fuse_qkv) {
                 qkv = ex.T(X.B, X.H, X.W, 3 * E, X.dt);
-                conv1(ex, s.qkv, n, qkv);
+                k1(s.qkv, n, qkv).launch(ex);
                 ex.tr(bp + "qkv", qkv);
             }
             const bool fuse_proj = fuse_qkv && (X.dt == RS_F16S || (attn_fused >= 2 && s.proj.wh_frag));   // ... and the output projection + shortcut as well
@@ -578,6 +617,15 @@ struct Graphs {
             const bool fuse_mlp = mlp_fused && !big_mlp && (X.dt == RS_F16 || (X.dt == RS_F16S && (mlp_fused & 2))) && rs_swin_mlp_supported(E, s.fc1.Cout) &&
                                   s.fc2.Cout == E && Mtok >= mlp_minm && s.fc1.w_for(X.dt) && s.fc2.w_for(X.dt);
             const bool fold2 = fuse_mlp && gn_fold && HWt % 128 == 0;
+            // the fused MLP over input `in` into `out`, with out's statistics (+ tail) if it carries any (real pass); the caller adds fc2's side
+            GNTail mlp_tail{};
+            auto mlp_call = [&](const View& in, const View& out) {
+                SwinMlpCall c{};
+                c.x = in.p; c.ldx = in.ld; c.w1 = s.fc1.w_for(X.dt); c.b1 = s.fc1.bias; c.y = out.p; c.ldy = out.ld;
+                c.M = Mtok; c.E = E; c.HD = s.fc1.Cout; c.HW = HWt; c.ystats = out.st; c.ystats_ld = out.stld;
+                if (out.st && ex.fill_tail(out.st_prod, X.B, mlp_tail)) c.tail = &mlp_tail;
+                return c;
+            };
             // The fused kernels' epilogues leave the statistics of their outputs for the GroupNorm that reads them (attention -> norm2: one
             // partial set per window; MLP -> the next block's norm1: one per 128-token tile) and - round 4 - the launch that completes an
             // image's statistics writes that GroupNorm's coefficients (tail): no pass over those tensors, no coefficient launch.
@@ -609,7 +657,7 @@ struct Graphs {
             if (!fuse_proj) {
                 ex.tr(bp + "attn", a);
                 e2 = ex.T(X.B, X.H, X.W, E, X.dt);
-                conv1(ex, s.proj, a, e2, &e);
+                k1(s.proj, a, e2).residual(e).launch(ex);
             }
             ex.tr(bp + "proj", e2);
             View e3;
@@ -624,13 +672,12 @@ struct Graphs {
                                 !m.big(b.unfold) && Y.dt == RS_F16S && Y.C == b.C && rs_swin_mlp_split_unembed_supported(E, s.fc1.Cout, b.C) &&
                                 (Y.ld % 8) == 0 && (e2.ld % 8) == 0;   // (the launcher's alignment preconditions: an unaligned view falls back to the separate 1x1 conv instead of failing the pass - ADVICE r5)
             if (unfold) {
-                Y.st = nullptr; Y.st2 = nullptr; Y.st_prod = -1;
+                Y.drop_stats();
                 if (out_stats && sstats && HWt % 128 == 0 && Mtok % 128 == 0) ex.attach_stats(Y, HWt / 128, Y.C);   // statistics (+ tail) for the GroupNorm that consumes the layer's output
                 if (!ex.dry) {
-                    GNTail tl{};
-                    const GNTail* tlp = (Y.st && ex.fill_tail(Y.st_prod, X.B, tl)) ? &tl : nullptr;
-                    ex.swin_mlp(e2.p, s.fc1.w_for(X.dt), s.fc1.bias, b.unfold.ws, b.unfold.bias, nullptr, Y.p, Mtok, e2.ld, 0, Y.ld, E, s.fc1.Cout, coef2, HWt,
-                                X.dt, Y.st, Y.stld, tlp, b.C);
+                    SwinMlpCall c = mlp_call(e2, Y);
+                    c.w2 = b.unfold.ws; c.b2 = b.unfold.bias; c.NO = b.C; c.xcoef = coef2;
+                    ex.swin_mlp(c, X.dt);
                 }
                 ex.reset(mk);
                 return;
@@ -640,29 +687,25 @@ struct Graphs {
                 const bool is_last = &s == &b.blocks.back();   // (the last block's output feeds patch_unembed, not a GroupNorm)
                 if (sstats && !is_last && HWt % 128 == 0 && Mtok % 128 == 0) ex.attach_stats(e3, HWt / 128, E);
                 if (!ex.dry) {
-                    const void* w1 = s.fc1.w_for(X.dt); const void* w2 = s.fc2.w_for(X.dt);
-                    GNTail tl{};
-                    const GNTail* tlp = (e3.st && ex.fill_tail(e3.st_prod, X.B, tl)) ? &tl : nullptr;
-                    if (fold2) ex.swin_mlp(e2.p, w1, s.fc1.bias, w2, s.fc2.bias, e2.p, e3.p, Mtok, e2.ld, e2.ld, e3.ld, E, s.fc1.Cout, coef2, HWt, X.dt, e3.st, e3.stld, tlp);
-                    else ex.swin_mlp(n2.p, w1, s.fc1.bias, w2, s.fc2.bias, e2.p, e3.p, Mtok, n2.ld, e2.ld, e3.ld, E, s.fc1.Cout, nullptr, HWt, X.dt, e3.st, e3.stld, tlp);
+                    SwinMlpCall c = mlp_call(fold2 ? e2 : n2, e3);   // (norm2 folded: the raw tensor and its coefficients)
+                    c.w2 = s.fc2.w_for(X.dt); c.b2 = s.fc2.bias; c.res = e2.p; c.ldres = e2.ld; c.xcoef = fold2 ? coef2 : nullptr;
+                    ex.swin_mlp(c, X.dt);
                 }
             } else {
                 View f = ex.T(X.B, X.H, X.W, s.fc1.Cout, X.dt);
-                conv1(ex, s.fc1, n2, f, nullptr, RS_ACT_GELU);
+                k1(s.fc1, n2, f).act(RS_ACT_GELU).launch(ex);
                 e3 = ex.T(X.B, X.H, X.W, E, X.dt);
-                conv1(ex, s.fc2, f, e3, &e2);
+                k1(s.fc2, f, e3).residual(e2).launch(ex);
             }
             ex.tr(bp + "out", e3);
             e = e3;
         }
-        conv_st(ex, b.unembed, e, Y, 1, 0, 1, nullptr, out_stats);
+        Y = conv_for_gn(ex, k1(b.unembed, e, Y), out_stats);
         ex.reset(mk);
     }
-    // ... under its debug-trace name: inner records under the block's prefix, then the block's output
-    void traced_resnet(Exec& ex, const std::string& nm, const ResBlockW& r, const View& x, View& y) {
-        ex.prefix = nm + ".";
-        resnet(ex, r, x, y);
-        ex.prefix.clear();
+    // a block under its debug-trace name: the records `body` makes go under "<name>.", then the block's output `y` under the name itself
+    template <class F> void traced(Exec& ex, const std::string& nm, const View& y, F body) {
+        { const Exec::Scope sc = ex.scope(nm); body(); }
         ex.tr(nm, y);
     }
     // model.py:179-203: x + proj_out(softmax(q k^T / sqrt(C)) v); S is materialised in fp32 per image chunk
@@ -672,8 +715,8 @@ struct Graphs {
         View n = ex.T(X.B, X.H, X.W, C, dt);
         gn(ex, a.norm, X, n, 1e-6f, RS_ACT_NONE);
         View q = ex.T(X.B, X.H, X.W, C, dt), k = ex.T(X.B, X.H, X.W, C, dt);
-        conv1(ex, a.q, n, q);
-        conv1(ex, a.k, n, k);
+        k1(a.q, n, q).launch(ex);
+        k1(a.k, n, k).launch(ex);
         ex.tr("norm", n); ex.tr("q", q); ex.tr("k", k);
         View o = ex.T(X.B, X.H, X.W, C, dt);
         // fp16 storage: streaming attention (ae_attn.hip) - S never reaches HBM; RS_AE_FLASH=0 keeps the row-block path below (A/B runs),
@@ -686,11 +729,14 @@ struct Graphs {
             char* vTa = (char*)ex.raw((size_t)X.B * C * T * rs_dtype_size(dt));
             if (!ex.dry) {
                 // vT[z][c][t] = sum_k Wv[c][k] n[z][t][k]   (bias added to the attention output: softmax rows sum to 1)
-                gemm_nt(ex, a.v.w_for(dt), 0, n.p, (long long)T * C, nullptr, vTa, (long long)C * T, X.B, C, T, C, 1.f, dt, dt);
-                ex.ae_flash(q.p, q.ld, k.p, k.ld, vTa, a.v.bias, o.p, o.ld, X.B, T, C, 1.0f / std::sqrt((float)C), dt);
+                gemm_nt(ex, {a.v.w_for(dt), 0}, {n.p, (long long)T * C}, nullptr, vTa, (long long)C * T, {X.B, C, T, C, 1.f, dt, dt});
+                AeFlashCall c{};
+                c.q = q.p; c.ldq = q.ld; c.k = k.p; c.ldk = k.ld; c.vt = vTa; c.bv = a.v.bias; c.o = o.p; c.ldo = o.ld;
+                c.nz = X.B; c.T = T; c.C = C; c.scale = 1.0f / std::sqrt((float)C);
+                ex.ae_flash(c, dt);
             }
             ex.tr("o", o);
-            conv_st(ex, a.proj, o, Y, 1, 0, 1, &X);
+            Y = conv_for_gn(ex, k1(a.proj, o, Y).residual(X));
             ex.reset(mk);
             return;
         }
@@ -715,32 +761,33 @@ struct Graphs {
                 const int nz = std::min(chunk, X.B - b0);
                 const size_t boff = (size_t)b0 * T * C * es;
                 // vT[z][c][t] = sum_k Wv[c][k] n[z][t][k]   (bias folded into the PV epilogue: softmax rows sum to 1)
-                gemm_nt(ex, a.v.w_for(dt), 0, (char*)n.p + boff, (long long)T * C, nullptr, vT, (long long)C * T, nz, C, T, C, 1.f, dt, dt);
+                gemm_nt(ex, {a.v.w_for(dt), 0}, {(char*)n.p + boff, (long long)T * C}, nullptr, vT, (long long)C * T, {nz, C, T, C, 1.f, dt, dt});
                 for (int r0 = 0; r0 < T; r0 += rows) {
                     const int nr = std::min(rows, T - r0);   // (rows == T unless a single image is processed in row blocks)
                     const size_t roff = boff + (size_t)r0 * C * es;
-                    gemm_nt(ex, (char*)q.p + roff, (long long)T * C, (char*)k.p + boff, (long long)T * C, nullptr, S, (long long)nr * T, nz, nr, T, C,
-                            1.0f / std::sqrt((float)C), dt, RS_F32);
+                    gemm_nt(ex, {(char*)q.p + roff, (long long)T * C}, {(char*)k.p + boff, (long long)T * C}, nullptr, S, (long long)nr * T,
+                            {nz, nr, T, C, 1.0f / std::sqrt((float)C), dt, RS_F32});
                     ex.check(rs_softmax_rows_launch(S, P, dt, (long long)nz * nr, T, T, T, ex.st), "softmax");
-                    gemm_nt(ex, P, (long long)nr * T, vT, (long long)C * T, a.v.bias, (char*)o.p + roff, (long long)T * C, nz, nr, C, T, 1.f, dt, dt);
+                    gemm_nt(ex, {P, (long long)nr * T}, {vT, (long long)C * T}, a.v.bias, (char*)o.p + roff, (long long)T * C, {nz, nr, C, T, 1.f, dt, dt});
                 }
             }
         }
         ex.tr("o", o);
-        conv_st(ex, a.proj, o, Y, 1, 0, 1, &X);
+        Y = conv_for_gn(ex, k1(a.proj, o, Y).residual(X));
         ex.reset(mk);
     }
-    // y[z][m][n] = scale * sum_k A[z][m][k] B[z][n][k] (+bias[n])
-    void gemm_nt(Exec& ex, const void* A, long long bsA, const void* Bm, long long bsB, const float* bias, void* y, long long bsY, int nz,
-                 int M, int N, int K, float scale, int in_dt, int out_dt) {
-        if (!A || !Bm) { if (!ex.err) { ex.fail(-3, "gemm operand missing (precision not packed?)"); } return; }
+    // y[z][m][n] = scale * sum_k A[z][m][k] B[z][n][k] (+bias[n]): nz dense matrices each, `bs` elements apart (0: one shared by all z)
+    struct Mat { const void* p; long long bs; };
+    struct GemmShape { int nz, M, N, K; float scale; int in_dt, out_dt; };
+    void gemm_nt(Exec& ex, Mat A, Mat Bm, const float* bias, void* y, long long bsY, const GemmShape& g) {
+        if (!A.p || !Bm.p) { ex.fail(-3, "gemm operand missing (precision not packed?)"); return; }
         IGemmParams p{};
-        p.x0 = A; p.w = Bm; p.bias = bias; p.y = y; p.C0 = K; p.ld0 = K; p.B = 1; p.Hs = M; p.Ws = 1; p.up = 1; p.Ho = M; p.Wo = 1;
-        p.KH = 1; p.KW = 1; p.stride = 1; p.Cout = N; p.ldy = N; p.M = M; p.Ktot = K; p.out_scale = scale;
-        p.bs_x0 = bsA; p.bs_w = bsB; p.bs_y = bsY;
+        p.x0 = A.p; p.w = Bm.p; p.bias = bias; p.y = y; p.C0 = g.K; p.ld0 = g.K; p.B = 1; p.Hs = g.M; p.Ws = 1; p.up = 1; p.Ho = g.M; p.Wo = 1;
+        p.KH = 1; p.KW = 1; p.stride = 1; p.Cout = g.N; p.ldy = g.N; p.M = g.M; p.Ktot = g.K; p.out_scale = g.scale;
+        p.bs_x0 = A.bs; p.bs_w = Bm.bs; p.bs_y = bsY;
         ConvPlan pl{};
-        (void)rs_conv_plan(&p, in_dt, out_dt, nz, &pl);
-        ex.igemm(p, pl, in_dt, out_dt, nz, "gemm_nt");
+        (void)rs_conv_plan(&p, g.in_dt, g.out_dt, g.nz, &pl);
+        ex.igemm(p, pl, g.in_dt, g.out_dt, g.nz, "gemm_nt");
     }
     // per-image FiLM table [B][film_total] for a batch whose images are at different timesteps: ONE gather launch from the cached rows
     // (rows[b] = film_row(t_b)), so that every image sees exactly the values the shared row of a homogeneous batch would give it.  Lives in
@@ -752,12 +799,21 @@ struct Graphs {
         return tab;
     }
     // ---------------------------------------------------------------- UNet forward
-    // x: NCHW fp32 [B,Cz,H,W] (already scaled by _scale_input when called through the drop-in API);
-    // lq_feat: optional NHWC view of the (feature-extracted) conditioning; out: NCHW fp32.
-    void unet_body(Exec& ex, const float* x, float xscale, const View* lq_feat, const float* lq_nchw, const float* mask_nchw, int Hl, int Wl,
-                   float* out, int B, int H, int W, int dt, const float* film, int film_ld = 0, const float* xscale_rows = nullptr) {
+    struct UNetCall {
+        const float* x;             // NCHW fp32 [B,Cz,H,W] (already scaled by _scale_input when called through the drop-in API) ...
+        float xscale;               // ... times this factor,
+        const float* xscale_rows;   // or (non-null) times one factor per image
+        const View* lq_feat;        // optional NHWC view of the (feature-extracted) conditioning
+        const float* lq_nchw; const float* mask_nchw;
+        float* out;                 // NCHW fp32
+        int B, H, W, dt;
+        const float* film; int film_ld;   // the FiLM row of the batch's timestep, or (film_ld > 0) a per-image table [B][film_ld], film_table()
+    };
+    void unet_body(Exec& ex, const UNetCall& c) {
+        const float* const x = c.x; const float* const film = c.film; const View* const lq_feat = c.lq_feat;
+        const int B = c.B, H = c.H, W = c.W, dt = c.dt;
         ex.enter_part("unet");
-        ex.film_base = film; ex.film_ld = film_ld;   // (film_ld > 0: `film` is a per-image table [B][film_ld], film_table())
+        ex.film_base = film; ex.film_ld = c.film_ld;
         const rs_unet_config& u = m.cfg.unet;
         const int n_in = (int)m.in_blocks.size(), n_out = (int)m.out_blocks.size();
         const size_t mk0 = ex.mark();
@@ -788,8 +844,8 @@ struct Graphs {
         // ---- input conv (unet.py:876-886): cat[x, lq(,mask)]
         const int Cz = u.in_channels;
         auto x_to_nhwc = [&](const View& v) {   // x (times _scale_input: one factor, or one per image) into channels [0, Cz) of v
-            if (xscale_rows) ex.check(rs_nchw_to_nhwc_rows_launch(x, v.p, dt, B, Cz, H * W, v.ld, 0, xscale_rows, ex.st), "x->nhwc (per image)");
-            else ex.check(rs_nchw_to_nhwc_launch(x, v.p, dt, B, Cz, H * W, v.ld, 0, xscale, ex.st), "x->nhwc");
+            if (c.xscale_rows) ex.check(rs_nchw_to_nhwc_rows_launch(x, v.p, dt, B, Cz, H * W, v.ld, 0, c.xscale_rows, ex.st), "x->nhwc (per image)");
+            else ex.check(rs_nchw_to_nhwc_launch(x, v.p, dt, B, Cz, H * W, v.ld, 0, c.xscale, ex.st), "x->nhwc");
         };
         View h;
         {
@@ -802,15 +858,17 @@ struct Graphs {
                 if (!ex.dry) {
                     zero(ex, in0);
                     x_to_nhwc(in0);
-                    if (cl) ex.check(rs_nchw_to_nhwc_launch(lq_nchw, in0.p, dt, B, 3, H * W, in0.ld, Cz, 1.f, ex.st), "lq->nhwc");
-                    if (cl == 4) ex.check(rs_nchw_to_nhwc_launch(mask_nchw, in0.p, dt, B, 1, H * W, in0.ld, Cz + 3, 1.f, ex.st), "mask->nhwc");
+                    if (cl) ex.check(rs_nchw_to_nhwc_launch(c.lq_nchw, in0.p, dt, B, 3, H * W, in0.ld, Cz, 1.f, ex.st), "lq->nhwc");
+                    if (cl == 4) ex.check(rs_nchw_to_nhwc_launch(c.mask_nchw, in0.p, dt, B, 1, H * W, in0.ld, Cz + 3, 1.f, ex.st), "mask->nhwc");
                 }
-                conv_st(ex, m.in_blocks[0].conv, in0, y0, 1, 1, 1);
+                y0 = conv_for_gn(ex, k3(m.in_blocks[0].conv, in0, y0));
             } else {
                 // conditioning goes through the strided-conv feature extractor (unet.py:693-702); lq_feat precomputed
                 View xin = ex.T(B, H, W, Cz, dt);
                 if (!ex.dry) x_to_nhwc(xin);
-                conv(ex, m.in_blocks[0].conv, xin, lq_feat, y0, 1, 1, 1, 1, 0, nullptr);
+                ConvCall c0 = k3(m.in_blocks[0].conv, xin, y0);
+                if (lq_feat) c0.second_source(*lq_feat);
+                c0.launch(ex);
             }
             ex.reset(mk);
             h = y0;
@@ -822,25 +880,19 @@ struct Graphs {
             const UBlock& b = m.in_blocks[i];
             const size_t mk = ex.mark();
             View y = skip_view(i);
+            const std::string nm = "in." + std::to_string(i);
             if (b.has_down) {
-                conv_st(ex, b.conv, h, y, 2, 1, 1);
-                ex.tr("in." + std::to_string(i), y);
+                y = conv_for_gn(ex, k3(b.conv, h, y).strided(2, 1));
             } else if (b.has_swin) {
                 View r = ex.T(B, h.H, h.W, b.out_ch, dt);
-                ex.prefix = "in." + std::to_string(i) + ".res.";
-                resblock(ex, b.res, h, r, film, /*out_stats=*/false);   // (r feeds patch_embed, not a GroupNorm)
-                ex.prefix.clear();
-                ex.tr("in." + std::to_string(i) + ".res", r);
-                ex.prefix = "in." + std::to_string(i) + ".swin.";
+                traced(ex, nm + ".res", r, [&] { resblock(ex, b.res, h, r, film, /*out_stats=*/false); });   // (r feeds patch_embed, not a GroupNorm)
+                const Exec::Scope sc = ex.scope(nm + ".swin");
                 basiclayer(ex, b.swin, r, y);
-                ex.prefix.clear();
-                ex.tr("in." + std::to_string(i), y);
             } else {
-                ex.prefix = "in." + std::to_string(i) + ".res.";
+                const Exec::Scope sc = ex.scope(nm + ".res");
                 resblock(ex, b.res, h, y, film);
-                ex.prefix.clear();
-                ex.tr("in." + std::to_string(i), y);
             }
+            ex.tr(nm, y);
             ex.reset(mk);
             h = y;
             note(cat_hi[n_in - 1 - i], y);
@@ -849,20 +901,11 @@ struct Graphs {
         {
             const size_t mk = ex.mark();
             View r1 = ex.T(B, h.H, h.W, h.C, dt), r2 = ex.T(B, h.H, h.W, h.C, dt);
-            ex.prefix = "mid.res1.";
-            resblock(ex, m.mid_res1, h, r1, film, /*out_stats=*/false);
-            ex.prefix.clear();
-            ex.tr("mid.res1", r1);
-            ex.prefix = "mid.swin.";
-            basiclayer(ex, m.mid_swin, r1, r2);
-            ex.prefix.clear();
-            ex.tr("mid.swin", r2);
+            traced(ex, "mid.res1", r1, [&] { resblock(ex, m.mid_res1, h, r1, film, /*out_stats=*/false); });
+            traced(ex, "mid.swin", r2, [&] { basiclayer(ex, m.mid_swin, r1, r2); });
             View y = cat[0].slice(0, m.h_ch[0]);
-            ex.prefix = "mid.res2.";
-            resblock(ex, m.mid_res2, r2, y, film);
-            ex.prefix.clear();
+            traced(ex, "mid.res2", y, [&] { resblock(ex, m.mid_res2, r2, y, film); });
             note(cat_lo[0], y);
-            ex.tr("mid.res2", y);
             ex.reset(mk);
         }
         // ---- output blocks (unet.py:890-892)
@@ -879,36 +922,23 @@ struct Graphs {
             }
             const size_t mk = ex.mark();
             const std::string nm = "out." + std::to_string(j);
-            ex.prefix = nm + ".res.";
             if (!b.has_swin && !b.has_up) {
+                const Exec::Scope sc = ex.scope(nm + ".res");
                 resblock(ex, b.res, X, y, film);
-                ex.prefix.clear();
             } else {
                 View cur = ex.T(B, X.H, X.W, b.out_ch, dt);
-                resblock(ex, b.res, X, cur, film, /*out_stats=*/false);   // (feeds patch_embed or the upsampling conv)
-                ex.prefix.clear();
-                ex.tr(nm + ".res", cur);
-                if (b.has_swin) {
-                    ex.prefix = nm + ".swin.";
-                    if (b.has_up) {
-                        View r2 = ex.T(B, X.H, X.W, b.out_ch, dt);
-                        basiclayer(ex, b.swin, cur, r2, /*out_stats=*/false);
-                        cur = r2;
-                        ex.prefix.clear();
-                        ex.tr(nm + ".swin", cur);
-                    } else {
-                        basiclayer(ex, b.swin, cur, y);
-                        ex.prefix.clear();
-                    }
+                traced(ex, nm + ".res", cur, [&] { resblock(ex, b.res, X, cur, film, /*out_stats=*/false); });   // (feeds patch_embed or the upsampling conv)
+                if (b.has_swin && b.has_up) {
+                    View r2 = ex.T(B, X.H, X.W, b.out_ch, dt);
+                    traced(ex, nm + ".swin", r2, [&] { basiclayer(ex, b.swin, cur, r2, /*out_stats=*/false); });
+                    cur = r2;
+                } else if (b.has_swin) {
+                    const Exec::Scope sc = ex.scope(nm + ".swin");
+                    basiclayer(ex, b.swin, cur, y);
                 }
                 if (b.has_up) {
-                    if (b.has_upf && upfold_ok(ex, b.upf, cur, y)) {
-                        const ConvPlan pl = upfold_plan(b.upf, cur, y);
-                        upfold_want_stats(ex, pl, cur, y);
-                        upfold_conv(ex, pl, b.upf, cur, y);
-                    } else {
-                        conv_st(ex, b.conv, cur, y, 1, 1, 2);  // nearest x2 folded into the conv's addressing
-                    }
+                    if (b.has_upf && upfold_ok(b.upf, cur, y)) y = upfold(ex, b.upf, cur, y, /*stats=*/true);
+                    else y = conv_for_gn(ex, k3(b.conv, cur, y).upsampled());
                 }
             }
             if (j + 1 < n_out) note(cat_lo[j + 1], y); else last = y;
@@ -919,7 +949,7 @@ struct Graphs {
         {
             View o = ex.T(B, H, W, u.out_channels, RS_F32);
             head(ex, m.out_norm, m.out_conv, last, o, 1e-5f);
-            if (!ex.dry) ex.check(rs_nhwc_to_nchw_launch(o.p, RS_F32, out, B, u.out_channels, H * W, o.ld, 0, ex.st), "out->nchw");
+            if (!ex.dry) ex.check(rs_nhwc_to_nchw_launch(o.p, RS_F32, c.out, B, u.out_channels, H * W, o.ld, 0, ex.st), "out->nchw");
         }
         ex.reset(mk0);
     }
@@ -934,9 +964,9 @@ struct Graphs {
         }
         for (size_t s = 0; s < m.fe_convs.size(); ++s) {
             View a = ex.T(B, cur.H, cur.W, m.fe_convs[s].Cout, dt);
-            conv(ex, m.fe_convs[s], cur, nullptr, a, 1, 1, 1, 1, RS_ACT_SILU, nullptr);
+            k3(m.fe_convs[s], cur, a).act(RS_ACT_SILU).launch(ex);
             View d = ex.T(B, cur.H / 2, cur.W / 2, m.fe_downs[s].Cout, dt);
-            conv(ex, m.fe_downs[s], a, nullptr, d, 2, 1, 1, 1, 0, nullptr);
+            k3(m.fe_downs[s], a, d).strided(2, 1).launch(ex);
             cur = d;
         }
         return cur;
@@ -951,7 +981,7 @@ struct Graphs {
         ex.pool_off = 0;
         const int B = in_nhwc.B;
         View h = ex.T(B, in_nhwc.H, in_nhwc.W, a.ch, dt);
-        conv_st(ex, m.enc_in, in_nhwc, h, 1, 1, 1);
+        h = conv_for_gn(ex, k3(m.enc_in, in_nhwc, h));
         // debug-trace names: the blocks of oracle.resshift_oracle.ae_encode_plan, inner records under their block's prefix
         ex.tr("enc.in", h);
         for (int l = 0; l < a.n_levels; ++l) {
@@ -960,62 +990,57 @@ struct Graphs {
             int bi = 0;
             for (const ResBlockW& r : L.blocks) {
                 View y = ex.T(B, h.H, h.W, r.Cout, dt);
-                traced_resnet(ex, lv + ".block." + std::to_string(bi++), r, h, y);
+                traced(ex, lv + ".block." + std::to_string(bi++), y, [&] { resnet(ex, r, h, y); });
                 h = y;
             }
             if (L.has_resample) {
                 // F.pad(x,(0,1,0,1)) + conv stride 2 pad 0 (model.py:80-84)
                 View y = ex.T(B, h.H / 2, h.W / 2, h.C, dt);
-                conv_st(ex, L.resample, h, y, 2, 0, 1);
+                y = conv_for_gn(ex, k3(L.resample, h, y).strided(2, 0));
                 ex.tr(lv + ".ds", y);
                 h = y;
             }
         }
-        View m1 = ex.T(B, h.H, h.W, h.C, dt); traced_resnet(ex, "enc.mid.block_1", m.enc_mid1, h, m1);
-        View m2 = ex.T(B, h.H, h.W, h.C, dt);
-        ex.prefix = "enc.mid.attn.";
-        attnblock(ex, m.enc_attn, m1, m2);
-        ex.prefix.clear();
-        ex.tr("enc.mid.attn", m2);
-        View m3 = ex.T(B, h.H, h.W, h.C, dt); traced_resnet(ex, "enc.mid.block_2", m.enc_mid2, m2, m3);
+        View m1 = ex.T(B, h.H, h.W, h.C, dt); traced(ex, "enc.mid.block_1", m1, [&] { resnet(ex, m.enc_mid1, h, m1); });
+        View m2 = ex.T(B, h.H, h.W, h.C, dt); traced(ex, "enc.mid.attn", m2, [&] { attnblock(ex, m.enc_attn, m1, m2); });
+        View m3 = ex.T(B, h.H, h.W, h.C, dt); traced(ex, "enc.mid.block_2", m3, [&] { resnet(ex, m.enc_mid2, m2, m3); });
         View zc = ex.T(B, h.H, h.W, a.z_channels, RS_F32);
         head(ex, m.enc_norm, m.enc_out, m3, zc, 1e-6f);
         ex.tr("enc.out", zc);   // (enc.z, the quant_conv, is the call's output)
         View zq = ex.T(B, h.H, h.W, a.embed_dim, RS_F32);
-        conv(ex, m.quant_conv, zc, nullptr, zq, 1, 0, 0, 1, 0, nullptr);
+        k1(m.quant_conv, zc, zq).launch(ex);
         if (!ex.dry) ex.check(rs_nhwc_to_nchw_launch(zq.p, RS_F32, z_nchw, B, a.embed_dim, h.H * h.W, zq.ld, 0, ex.st), "z->nchw");
         ex.reset(mk0);
     }
-    // z NCHW fp32 [B,embed,h,w] -> img NCHW fp32
-    void decode_body(Exec& ex, const float* z_nchw, float zscale, float* img, int32_t* idx_out, int B, int h_, int w_, int force_nq, int dt) {
+    // z NCHW fp32 [B,embed,h,w] (times zscale) -> img NCHW fp32; idx_out: the VQ codes, unless force_nq skips the quantiser
+    struct DecodeCall { const float* z; float zscale; float* img; int32_t* idx_out; int B, h, w, force_nq, dt; };
+    void decode_body(Exec& ex, const DecodeCall& c) {
+        const float* const z_nchw = c.z; float* const img = c.img;
+        const int B = c.B, h_ = c.h, w_ = c.w, dt = c.dt;
         ex.enter_part("decoder");
         const rs_ae_config& a = m.cfg.ae;
         const size_t mk0 = ex.mark();
         ex.pool_off = 0;
         View z = ex.T(B, h_, w_, a.embed_dim, RS_F32);
-        if (!ex.dry) ex.check(rs_nchw_to_nhwc_launch(z_nchw, z.p, RS_F32, B, a.embed_dim, h_ * w_, z.ld, 0, zscale, ex.st), "z->nhwc");
+        if (!ex.dry) ex.check(rs_nchw_to_nhwc_launch(z_nchw, z.p, RS_F32, B, a.embed_dim, h_ * w_, z.ld, 0, c.zscale, ex.st), "z->nhwc");
         View q = z;
-        if (!force_nq) {
+        if (!c.force_nq) {
             q = ex.T(B, h_, w_, a.embed_dim, RS_F32);
-            if (!ex.dry) ex.check(rs_vq_launch((const float*)z.p, m.codebook, (float*)q.p, idx_out, (long long)B * h_ * w_, a.n_embed, a.embed_dim, ex.st), "vq");
+            if (!ex.dry) ex.check(rs_vq_launch((const float*)z.p, m.codebook, (float*)q.p, c.idx_out, (long long)B * h_ * w_, a.n_embed, a.embed_dim, ex.st), "vq");
             // debug-trace names: the blocks of oracle.resshift_oracle.ae_decode_plan, inner records under their block's prefix
             ex.tr("dec.zq.z", z);   // (the latents the argmin saw: the call's input times zscale)
             ex.tr("dec.zq", q);
         }
         View pq = ex.T(B, h_, w_, m.dec_in.CinP, dt);  // z_channels zero-padded to the decoder conv_in's chunk size
         zero(ex, pq);
-        conv(ex, m.post_quant_conv, q, nullptr, pq.slice(0, a.z_channels), 1, 0, 0, 1, 0, nullptr);
+        k1(m.post_quant_conv, q, pq.slice(0, a.z_channels)).launch(ex);
         ex.tr("dec.pq", pq.slice(0, a.z_channels));
         View h = ex.T(B, h_, w_, m.dec_in.Cout, dt);
-        conv(ex, m.dec_in, pq, nullptr, h, 1, 1, 1, 1, 0, nullptr);
+        k3(m.dec_in, pq, h).launch(ex);
         ex.tr("dec.in", h);
-        View m1 = ex.T(B, h.H, h.W, h.C, dt); traced_resnet(ex, "dec.mid.block_1", m.dec_mid1, h, m1);
-        View m2 = ex.T(B, h.H, h.W, h.C, dt);
-        ex.prefix = "dec.mid.attn.";
-        attnblock(ex, m.dec_attn, m1, m2);
-        ex.prefix.clear();
-        ex.tr("dec.mid.attn", m2);
-        View m3 = ex.T(B, h.H, h.W, h.C, dt); traced_resnet(ex, "dec.mid.block_2", m.dec_mid2, m2, m3);
+        View m1 = ex.T(B, h.H, h.W, h.C, dt); traced(ex, "dec.mid.block_1", m1, [&] { resnet(ex, m.dec_mid1, h, m1); });
+        View m2 = ex.T(B, h.H, h.W, h.C, dt); traced(ex, "dec.mid.attn", m2, [&] { attnblock(ex, m.dec_attn, m1, m2); });
+        View m3 = ex.T(B, h.H, h.W, h.C, dt); traced(ex, "dec.mid.block_2", m3, [&] { resnet(ex, m.dec_mid2, m2, m3); });
         h = m3;
         for (int l = a.n_levels - 1; l >= 0; --l) {
             const AELevel& L = m.dec_levels[l];
@@ -1023,13 +1048,13 @@ struct Graphs {
             int bi = 0;
             for (const ResBlockW& r : L.blocks) {
                 View y = ex.T(B, h.H, h.W, r.Cout, dt);
-                traced_resnet(ex, lv + ".block." + std::to_string(bi++), r, h, y);
+                traced(ex, lv + ".block." + std::to_string(bi++), y, [&] { resnet(ex, r, h, y); });
                 h = y;
             }
             if (L.has_resample) {
                 View y = ex.T(B, h.H * 2, h.W * 2, h.C, dt);
-                if (L.has_upf && upfold_ok(ex, L.upf, h, y)) upfold_conv(ex, upfold_plan(L.upf, h, y), L.upf, h, y);
-                else conv(ex, L.resample, h, nullptr, y, 1, 1, 1, 2, 0, nullptr);
+                if (L.has_upf && upfold_ok(L.upf, h, y)) upfold(ex, L.upf, h, y, /*stats=*/false);
+                else k3(L.resample, h, y).upsampled().launch(ex);
                 ex.tr(lv + ".us", y);
                 h = y;
             }
@@ -1080,9 +1105,20 @@ struct Graphs {
     // x_{t-1} = coef1 x_t + coef2 pred + [t > 0] sigma noise, in place.  Equal indices: exactly the scalar launches of rs_sample.  Otherwise
     // the per-image FiLM table (+ one gather launch), _scale_input per image inside the UNet's input conversion and the per-image
     // elementwise kernel: every image gets bit for bit what it would get in a homogeneous batch of the same size.  films[i]: cached FiLM row of step index i (rows not used may be null).
-    void sample_step(Exec& ex, float* xt, float* pred, const View* feat, const float* y, const float* mask, int h, int w, int B, int hz, int wz,
-                     int prec, const int* t, const rs_sample_args* a, const float* const* films, const float* noise, const rs_noise_key* keys = nullptr,
-                     const rs_noise_key* keys_dev = nullptr) {
+    struct StepCall {
+        float* xt; float* pred;                                        // [B,Cz,hz,wz] NCHW fp32: x_t (updated in place), the UNet's prediction
+        const View* feat; const float* y; const float* mask;           // the UNet's conditioning (UNetCall::lq_feat / lq_nchw / mask_nchw)
+        int B, hz, wz, prec;
+        const int* t;                                                  // [B] step indices
+        const rs_sample_args* a; const float* const* films;
+        const float* noise;                                            // the step's noise, or (seeded calls) ...
+        const rs_noise_key* keys; const rs_noise_key* keys_dev;        // ... the images' keys (keys_dev: sample_prologue())
+    };
+    void sample_step(Exec& ex, const StepCall& c) {
+        float* const xt = c.xt; float* const pred = c.pred; const int* const t = c.t; const rs_sample_args* const a = c.a; const rs_noise_key* const keys = c.keys;
+        const int B = c.B, hz = c.hz, wz = c.wz;
+        UNetCall u{};
+        u.x = xt; u.lq_feat = c.feat; u.lq_nchw = c.y; u.mask_nchw = c.mask; u.out = pred; u.B = B; u.H = hz; u.W = wz; u.dt = c.prec;
         bool mixed = false;
         for (int b = 1; b < B; ++b) mixed |= t[b] != t[0];
         const long long zcount = (long long)B * m.cfg.unet.in_channels * hz * wz, per = zcount / B;
@@ -1095,25 +1131,27 @@ struct Graphs {
         };
         if (!mixed) {
             const int i = t[0];
-            unet_body(ex, xt, a->inv_std[i], feat, y, mask, h, w, pred, B, hz, wz, prec, films[i]);
+            u.xscale = a->inv_std[i]; u.film = c.films[i];
+            unet_body(ex, u);
             if (ex.dry) return;
             if (keys) {
                 posterior(B > RS_MAX_ROWS ? 1 : B);
-                ex.check(rs_axpbypcz_seeded_launch(xt, pred, xt, ca, cb, cc, keys, keys_dev, dr, per, B, ex.st), "posterior step (seeded)");
+                ex.check(rs_axpbypcz_seeded_launch(xt, pred, xt, ca, cb, cc, keys, c.keys_dev, dr, per, B, ex.st), "posterior step (seeded)");
             } else
-                ex.check(rs_axpbypcz_launch(xt, pred, i > 0 ? noise : nullptr, xt, a->coef1[i], a->coef2[i], a->sigma[i], zcount, ex.st), "posterior step");
+                ex.check(rs_axpbypcz_launch(xt, pred, i > 0 ? c.noise : nullptr, xt, a->coef1[i], a->coef2[i], a->sigma[i], zcount, ex.st), "posterior step");
             return;
         }
         const size_t mk = ex.mark();
         const float* rows[RS_MAX_ROWS];
-        for (int b = 0; b < B; ++b) rows[b] = films[t[b]];
+        for (int b = 0; b < B; ++b) rows[b] = c.films[t[b]];
         const float* tab = film_table(ex, rows, B);
         for (int b = 0; b < B; ++b) ca[b] = a->inv_std[t[b]];   // _scale_input per image (:598-609)
-        unet_body(ex, xt, 1.0f, feat, y, mask, h, w, pred, B, hz, wz, prec, tab, m.film_total, ca);
+        u.xscale = 1.0f; u.xscale_rows = ca; u.film = tab; u.film_ld = m.film_total;
+        unet_body(ex, u);
         if (!ex.dry) {
             posterior(B);
             if (keys) ex.check(rs_axpbypcz_seeded_launch(xt, pred, xt, ca, cb, cc, keys, nullptr, dr, per, B, ex.st), "posterior step (per image, seeded)");
-            else ex.check(rs_axpbypcz_rows_launch(xt, pred, noise, xt, ca, cb, cc, per, B, ex.st), "posterior step (per image)");
+            else ex.check(rs_axpbypcz_rows_launch(xt, pred, c.noise, xt, ca, cb, cc, per, B, ex.st), "posterior step (per image)");
         }
         ex.reset(mk);
     }
@@ -1122,7 +1160,7 @@ struct Graphs {
         const int f = latent_div(), hz = a->h * a->sf / f, wz = a->w * a->sf / f;
         const long long zcount = (long long)a->B * m.cfg.ae.embed_dim * hz * wz;
         if (a->z_out && !ex.dry) (void)hipMemcpyAsync(a->z_out, xt, zcount * 4, hipMemcpyDeviceToDevice, ex.st);
-        decode_body(ex, xt, 1.0f / a->scale_factor, a->out, a->idx_out, a->B, hz, wz, 0, a->prec_decode);
+        decode_body(ex, DecodeCall{xt, 1.0f / a->scale_factor, a->out, a->idx_out, a->B, hz, wz, 0, a->prec_decode});
     }
 };
 

@@ -46,20 +46,13 @@ int rs_win_attn_qkv_supported(int heads, int E);
 int rs_win_attn_qkv_launch(const WinAttnParams* p, hipStream_t st);
 int rs_win_attn_qkv_split_launch(const WinAttnParams* p, hipStream_t st);
 int rs_ae_flash_supported(int C, int T);
-int rs_ae_flash_launch(const void* q, int ldq, const void* k, int ldk, const void* vt, const float* bv, void* o, int ldo, int nz, int T, int C,
-                       float scale, hipStream_t st);
+int rs_ae_flash_launch(const AeFlashCall* c, hipStream_t st);
 int rs_ae_flash_split_supported(int C, int T);
-int rs_ae_flash_split_launch(const void* q, int ldq, const void* k, int ldk, const void* vt, const float* bv, void* o, int ldo, int nz, int T, int C,
-                             float scale, hipStream_t st);
+int rs_ae_flash_split_launch(const AeFlashCall* c, hipStream_t st);
 int rs_swin_mlp_supported(int E, int HD);
-int rs_swin_mlp_split_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* res, void* y, int M, int ldx,
-                             int ldres, int ldy, int E, int HD, const float* xcoef, int HW, float* ystats, int ystats_ld, const GNTail* tail, hipStream_t st);
-int rs_swin_mlp_split_launch_n(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* res, void* y, int M, int ldx,
-                               int ldres, int ldy, int E, int HD, int NO, const float* xcoef, int HW, float* ystats, int ystats_ld, const GNTail* tail,
-                               hipStream_t st);
+int rs_swin_mlp_launch(const SwinMlpCall* c, hipStream_t st);
 int rs_swin_mlp_split_unembed_supported(int E, int HD, int NO);
-int rs_swin_mlp_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* res, void* y, int M, int ldx,
-                       int ldres, int ldy, int E, int HD, const float* xcoef, int HW, float* ystats, int ystats_ld, hipStream_t st);
+int rs_swin_mlp_split_launch(const SwinMlpCall* c, hipStream_t st);   // (c->NO != E: + patch_unembed)
 int rs_small_linear_launch(const float* x, const float* w, const float* bias, float* y, int R, int K, int N, int silu_in, int silu_out, hipStream_t st);
 int rs_bicubic_launch(const float* in, void* out, int out_dt, int B, int C, int H, int W, int sf, int ldo, hipStream_t st);
 int rs_interp_launch(const float* in, float* out, long long planes, int H, int W, int Ho, int Wo, double step_h, double step_w, int mode, int clamp,

@@ -69,7 +69,7 @@ struct Model {
     // ... and a layer whose weights reach |w| >= 30 is not a reason to refuse the policy: only the kernels that scale the hi fragment by
     // 2^11 (the halo conv, the fused split Swin kernels) cannot take it, the generic split kernel (igemm_split.hip: two accumulators, no
     // scaling) can.  One flag byte per conv / linear in build order, written into the blob by the packing rank (it travels with the
-    // broadcast) and read back by rs_weights_ready; plan_conv() (IGemmParams::unscaled_w) / basiclayer() route a flagged layer to the generic kernels.
+    // broadcast) and read back by rs_weights_ready; ConvCall (IGemmParams::unscaled_w) / basiclayer() route a flagged layer to the generic kernels.
     std::vector<unsigned char> big_w;
     int conv_count = 0;
     unsigned char* big_w_dev = nullptr;

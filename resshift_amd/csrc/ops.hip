@@ -328,34 +328,53 @@ int rs_op_window_attention_qkv_split(const void* x, const void* wqkv_dev, const 
     return op_window_attention_qkv(true, x, wqkv_dev, bqkv_dev, wproj_dev, bproj_dev, res, out, table_host, xcoef_dev, B, H, W, heads, shift, (hipStream_t)stream);
 }
 
+// the dense call block of the op-level attention entries: rows of C features
+static AeFlashCall op_ae_flash_call(const void* q, const void* k, const void* vt, const float* bv_dev, void* o, int nz, int T, int C) {
+    AeFlashCall c{};
+    c.q = q; c.k = k; c.vt = vt; c.bv = bv_dev; c.o = o; c.ldq = c.ldk = c.ldo = C; c.nz = nz; c.T = T; c.C = C; c.scale = 1.0f / std::sqrt((float)C);
+    return c;
+}
 int rs_op_ae_flash_attention(const void* q, const void* k, const void* vt, const float* bv_dev, void* o, int nz, int T, int C, void* stream) {
-    const int rc = rs_ae_flash_launch(q, C, k, C, vt, bv_dev, o, C, nz, T, C, 1.0f / std::sqrt((float)C), (hipStream_t)stream);
+    const AeFlashCall c = op_ae_flash_call(q, k, vt, bv_dev, o, nz, T, C);
+    const int rc = rs_ae_flash_launch(&c, (hipStream_t)stream);
     if (rc) rs_set_last_error("streaming AE attention launch rejected the shape (fp16, C in {128, 256, 512}, T a multiple of 128)", -1);
     return rc;
 }
 
 int rs_op_ae_flash_attention_split(const void* q, const void* k, const void* vt, const float* bv_dev, void* o, int nz, int T, int C, void* stream) {
-    const int rc = rs_ae_flash_split_launch(q, C, k, C, vt, bv_dev, o, C, nz, T, C, 1.0f / std::sqrt((float)C), (hipStream_t)stream);
+    const AeFlashCall c = op_ae_flash_call(q, k, vt, bv_dev, o, nz, T, C);
+    const int rc = rs_ae_flash_split_launch(&c, (hipStream_t)stream);
     if (rc) rs_set_last_error("split-storage streaming AE attention launch rejected the shape (C = 512, T a multiple of 64)", -1);
     return rc;
 }
 
+// the dense call block of the op-level MLP entries: rows of E features in, NO (0: E) out, no shortcut yet
+static SwinMlpCall op_swin_mlp_call(const void* x, const void* w1_dev, const float* b1_dev, const void* w2_dev, const float* b2_dev, void* y, int M, int E) {
+    SwinMlpCall c{};
+    c.x = x; c.w1 = w1_dev; c.b1 = b1_dev; c.w2 = w2_dev; c.b2 = b2_dev; c.y = y; c.M = M; c.ldx = c.ldy = c.E = E;
+    return c;
+}
 int rs_op_swin_mlp(const void* x, const void* w1_dev, const float* b1_dev, const void* w2_dev, const float* b2_dev, const void* res, void* y,
                    int M, int E, int HD, void* stream) {
-    const int rc = rs_swin_mlp_launch(x, w1_dev, b1_dev, w2_dev, b2_dev, res, y, M, E, E, E, E, HD, nullptr, 0, nullptr, 0, (hipStream_t)stream);
+    SwinMlpCall c = op_swin_mlp_call(x, w1_dev, b1_dev, w2_dev, b2_dev, y, M, E);
+    c.HD = HD; c.res = res; c.ldres = E;
+    const int rc = rs_swin_mlp_launch(&c, (hipStream_t)stream);
     if (rc) rs_set_last_error("swin_mlp launch rejected the shape (fp16, E = 192, HD = 768 only)", -1);
     return rc;
 }
 int rs_op_swin_mlp_split(const void* x, const void* w1_dev, const float* b1_dev, const void* w2_dev, const float* b2_dev, const void* res, void* y,
                          int M, int E, int HD, void* stream) {
-    const int rc = rs_swin_mlp_split_launch(x, w1_dev, b1_dev, w2_dev, b2_dev, res, y, M, E, E, E, E, HD, nullptr, 0, nullptr, 0, nullptr, (hipStream_t)stream);
+    SwinMlpCall c = op_swin_mlp_call(x, w1_dev, b1_dev, w2_dev, b2_dev, y, M, E);
+    c.HD = HD; c.res = res; c.ldres = E;
+    const int rc = rs_swin_mlp_split_launch(&c, (hipStream_t)stream);
     if (rc) rs_set_last_error("swin_mlp_split launch rejected the shape (split storage, E = 192, HD = 768 only)", -1);
     return rc;
 }
 int rs_op_swin_mlp_split_unembed(const void* x, const float* xcoef_dev, const void* w1_dev, const float* b1_dev, const void* w2cat_dev, const float* bcat_dev,
                                  void* y, int M, int HW, int E, int HD, int NO, void* stream) {
-    const int rc = rs_swin_mlp_split_launch_n(x, w1_dev, b1_dev, w2cat_dev, bcat_dev, nullptr, y, M, E, 0, NO, E, HD, NO, xcoef_dev, HW, nullptr, 0, nullptr,
-                                              (hipStream_t)stream);
+    SwinMlpCall c = op_swin_mlp_call(x, w1_dev, b1_dev, w2cat_dev, bcat_dev, y, M, E);
+    c.HD = HD; c.NO = c.ldy = NO; c.xcoef = xcoef_dev; c.HW = HW;
+    const int rc = rs_swin_mlp_split_launch(&c, (hipStream_t)stream);
     if (rc) rs_set_last_error("swin_mlp_split (+ patch_unembed) launch rejected the shape (split storage, E = 192, HD = 768, NO = 160, HW % 128 == 0 only)", -1);
     return rc;
 }

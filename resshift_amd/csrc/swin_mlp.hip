@@ -261,15 +261,15 @@ __global__ __launch_bounds__(512, 2) void swin_mlp_kernel(MlpParams p) {
 // Launch conditions (checked by the caller as well): fp16 storage, E = 192, HD = 768, 16-byte aligned rows.
 extern "C" int rs_swin_mlp_supported(int E, int HD) { return E == 192 && HD == 768; }
 
-extern "C" int rs_swin_mlp_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* res, void* y,
-                                  int M, int ldx, int ldres, int ldy, int E, int HD, const float* xcoef, int HW, float* ystats, int ystats_ld,
-                                  hipStream_t st) {
-    if (ystats && (HW <= 0 || (HW & 31) || (M & 31))) return -2;
-    if (!rs_swin_mlp_supported(E, HD) || (ldx & 7) || (ldy & 7) || (res && (ldres & 3)) || M <= 0) return -2;
-    if (xcoef && (HW <= 0 || HW % 128)) return -2;
+extern "C" int rs_swin_mlp_launch(const SwinMlpCall* c, hipStream_t st) {
+    const int M = c->M, HW = c->HW;
+    if (c->tail || (c->NO > 0 && c->NO != c->E)) return -2;   // (split storage only)
+    if (c->ystats && (HW <= 0 || (HW & 31) || (M & 31))) return -2;
+    if (!rs_swin_mlp_supported(c->E, c->HD) || (c->ldx & 7) || (c->ldy & 7) || (c->res && (c->ldres & 3)) || M <= 0) return -2;
+    if (c->xcoef && (HW <= 0 || HW % 128)) return -2;
     MlpParams p{};
-    p.x = (const f16*)x; p.w1 = (const f16*)w1; p.b1 = b1; p.w2 = (const f16*)w2; p.b2 = b2; p.res = (const f16*)res; p.y = (f16*)y;
-    p.M = M; p.ldx = ldx; p.ldres = ldres; p.ldy = ldy; p.xcoef = xcoef; p.HW = HW; p.ystats = ystats; p.ystats_ld = ystats_ld;
+    p.x = (const f16*)c->x; p.w1 = (const f16*)c->w1; p.b1 = c->b1; p.w2 = (const f16*)c->w2; p.b2 = c->b2; p.res = (const f16*)c->res; p.y = (f16*)c->y;
+    p.M = M; p.ldx = c->ldx; p.ldres = c->ldres; p.ldy = c->ldy; p.xcoef = c->xcoef; p.HW = HW; p.ystats = c->ystats; p.ystats_ld = c->ystats_ld;
     constexpr int LDS = 160 * 1024;
     static RsAttrFlags attr_flags;
     if (attr_flags.need()) {
@@ -597,25 +597,22 @@ extern "C" int rs_mlp_phase_cycles(int nwg, double* out6) {
 // patch_unembed folded into the layer's last fused MLP (the kernel's NO != E form): the output widths this build instantiates
 extern "C" int rs_swin_mlp_split_unembed_supported(int E, int HD, int NO) { return E == 192 && HD == 768 && NO == 160; }
 
-// `NO` = 0 (or E): the block alone, y = x' + fc2(gelu(fc1(norm2(x)))) with `res` = x'.  NO != E: + patch_unembed - `w2` is the product matrix
-// [NO][HD + E] (hi | lo), `b2` the merged bias (NO floats), `res` must be null (the shortcut is the RAW `x`, which therefore has to be the
-// block's own input: xcoef set), y has NO channels.
-extern "C" int rs_swin_mlp_split_launch_n(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* res, void* y,
-                                          int M, int ldx, int ldres, int ldy, int E, int HD, int NO, const float* xcoef, int HW, float* ystats,
-                                          int ystats_ld, const GNTail* tail, hipStream_t st) {
-    if (NO <= 0) NO = E;
-    if (ystats && (HW <= 0 || (HW & 127) || (M & 127))) return -2;   // one statistics set per 128-token tile of one image
-    if (tail && tail->coef && !ystats) return -2;
-    if (!rs_swin_mlp_supported(E, HD) || (ldx & 7) || (ldy & 7) || (res && (ldres & 3)) || M <= 0) return -2;
-    if (NO != E && (!rs_swin_mlp_split_unembed_supported(E, HD, NO) || res || !xcoef)) return -2;
-    if (xcoef && (HW <= 0 || HW % 128)) return -2;
+// SwinMlpCall::NO = 0 (or E): the block alone, y = x' + fc2(gelu(fc1(norm2(x)))) with `res` = x'.  NO != E: + patch_unembed (common.h), y has NO channels.
+extern "C" int rs_swin_mlp_split_launch(const SwinMlpCall* c, hipStream_t st) {
+    const int M = c->M, HW = c->HW, E = c->E, NO = c->NO <= 0 ? E : c->NO;
+    const GNTail* tail = c->tail;
+    if (c->ystats && (HW <= 0 || (HW & 127) || (M & 127))) return -2;   // one statistics set per 128-token tile of one image
+    if (tail && tail->coef && !c->ystats) return -2;
+    if (!rs_swin_mlp_supported(E, c->HD) || (c->ldx & 7) || (c->ldy & 7) || (c->res && (c->ldres & 3)) || M <= 0) return -2;
+    if (NO != E && (!rs_swin_mlp_split_unembed_supported(E, c->HD, NO) || c->res || !c->xcoef)) return -2;
+    if (c->xcoef && (HW <= 0 || HW % 128)) return -2;
     MlpSplitParams p{};
-    p.x = (const f16*)x; p.w1 = (const f16*)w1; p.b1 = b1; p.w2 = (const f16*)w2; p.b2 = b2; p.res = (const f16*)res; p.y = (f16*)y;
-    p.M = M; p.ldx = ldx; p.ldres = ldres; p.ldy = ldy; p.xcoef = xcoef; p.HW = HW; p.ystats = ystats; p.ystats_ld = ystats_ld;
+    p.x = (const f16*)c->x; p.w1 = (const f16*)c->w1; p.b1 = c->b1; p.w2 = (const f16*)c->w2; p.b2 = c->b2; p.res = (const f16*)c->res; p.y = (f16*)c->y;
+    p.M = M; p.ldx = c->ldx; p.ldres = c->ldres; p.ldy = c->ldy; p.xcoef = c->xcoef; p.HW = HW; p.ystats = c->ystats; p.ystats_ld = c->ystats_ld;
     if (tail && tail->coef) {   // GroupNorm tail: this launch's statistics are segment 0; every 128-token tile of an image arrives once
         p.tail = *tail;
         p.tail.expected = HW / 128;
-        p.tail.st0 = ystats; p.tail.S0 = HW / 128; p.tail.ld0 = ystats_ld; p.tail.n0 = NO;
+        p.tail.st0 = c->ystats; p.tail.S0 = HW / 128; p.tail.ld0 = c->ystats_ld; p.tail.n0 = NO;
     }
     constexpr int LDS = 2 * 6 * 32 * 128 + 2 * 192 * 128 + 128 * 128;   // 114688 (NO = 160: 8 KB less; one size keeps it simple)
     static RsAttrFlags attr_flags;
@@ -626,10 +623,4 @@ extern "C" int rs_swin_mlp_split_launch_n(const void* x, const void* w1, const f
     if (NO == 160) hipLaunchKernelGGL((swin_mlp_split_kernel<192, 768, 160>), dim3((M + 127) / 128), dim3(512), LDS, st, p);
     else hipLaunchKernelGGL((swin_mlp_split_kernel<192, 768>), dim3((M + 127) / 128), dim3(512), LDS, st, p);
     return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-extern "C" int rs_swin_mlp_split_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* res, void* y,
-                                        int M, int ldx, int ldres, int ldy, int E, int HD, const float* xcoef, int HW, float* ystats, int ystats_ld,
-                                        const GNTail* tail, hipStream_t st) {
-    return rs_swin_mlp_split_launch_n(x, w1, b1, w2, b2, res, y, M, ldx, ldres, ldy, E, HD, E, xcoef, HW, ystats, ystats_ld, tail, st);
 }
