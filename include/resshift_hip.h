@@ -422,6 +422,39 @@ int rs_jpeg_codec(const float* in, float* out, const int* quality, int B, int C,
 int rs_blur_resize(const float* in, const float* kernels, float* out, int B, int C, int H, int W, int Ho, int Wo, int k, int Bk, int clamp,
                    void* stream);
 
+/* ---- JPEG files: libjpeg's baseline encoder on the device -------------------------------------------------------------
+ * rs_jpeg_encode: uint8 RGB images -> finished baseline JPEG FILES in device memory, byte for byte what libjpeg writes for them at 4:2:0 with
+ *   its default tables - PIL.Image.save(format="JPEG", quality=q, subsampling=2) - so that only compressed bytes cross PCIe.  The forward
+ *   path is rs_jpeg_codec's above (one definition, csrc/jpeg_common.h), from the 8-bit pixels on; this call adds the entropy stage the codec
+ *   never materialises.  tests/_jpeg_enc_ref.py is the definition in numpy, equal to Pillow's libjpeg-turbo on every byte.  Same conventions
+ *   as the block above: stateless, inputs only read, a batch is byte for byte its B = 1 calls, argument errors -2 with rs_last_error()
+ *   starting "rs_jpeg_encode: " before any launch.  Several launches on `stream`; no kernel waits for another workgroup.
+ *   in: uint8 [B,H,W,3] on the device (what rs_output_to_u8 / rs_unit_to_u8 write); C must be 3; 8 <= H, W <= 65535 and at most about 55
+ *   megapixels (the two-level prefix sum of the stuffing pass); every image of a call has the same size and its own quality, a HOST array of
+ *   integers 1 .. 100 (by value to the kernels, B <= RS_MAX_ROWS).  out: B rows of out_pitch >= rs_jpeg_encode_bound(H, W) bytes on the
+ *   device; image b's file is out[b * out_pitch .. + nbytes[b]) and NO byte at or beyond nbytes[b] of a row is written.  nbytes: int [B] on
+ *   the device.  workspace: rs_jpeg_encode_workspace(B, H, W) bytes on the device, 16-byte aligned, contents irrelevant before and after.
+ *   in, out, nbytes and workspace must not overlap.
+ *   Blocks.  Quantised coefficients in zigzag order, in scan order: per MCU (16 x 16 pixels) Y00, Y01, Y10, Y11, Cb, Cr, MCUs row-major.
+ *   libjpeg transforms only ceil(H/8) x ceil(W/8) Y blocks; an MCU's Y positions beyond them are DUMMY blocks (jccoefct.c compress_data): all
+ *   63 AC coefficients zero, the DC that of the preceding block of the MCU, which may be a dummy itself.  Chroma is never a dummy.
+ *   Codes.  Per block the DC difference against the previous block of the same component in scan order (0 before the first; dummies take part),
+ *   as its magnitude category n (Annex K.3 DC table of the component) and n extra bits; then run / category symbols (Annex K.3 AC table)
+ *   with n extra bits, ZRL (0xF0) for every 16 zeros of a longer run, EOB (0x00) unless coefficient 63 is non-zero.  Extra bits of v < 0 are
+ *   v + 2^n - 1.  Bits fill bytes MSB first; the last byte is padded with 1-bits; every 0xFF byte of the scan is followed by 0x00.
+ *   File.  SOI, APP0 (JFIF 1.01, units 0, density 1 x 1), DQT luminance, DQT chrominance (8-bit, zigzag order), SOF0 (8-bit, H, W, components
+ *   1 / 2 / 3 sampled 0x22 / 0x11 / 0x11 with tables 0 / 1 / 1), DHT DC0, AC0, DC1, AC1, SOS (one interleaved scan), the scan from offset 623,
+ *   EOI.  Only the DQT payloads depend on the quality, only SOF0 on the size.
+ *   Bound.  The longest code of a block: the longest DC code with its extra bits (chrominance category 11: 11 + 11 bits) and 63 coefficients
+ *   of the longest AC code with its extra bits (16 + 10, so no EOB): 22 + 63 * 26 = 1660 bits, derived from the code tables at compile time.
+ *   rs_jpeg_encode_bound(H, W) = 623 + 2 * ceil(6 * ceil(H/16) * ceil(W/16) * 1660 / 8) + 2: every byte of the scan stuffed, plus EOI.  The
+ *   coder clamps categories to 11 (DC) and 10 (AC) - beyond what 8-bit samples reach - so no input overruns it.  Both size queries return 0
+ *   for sizes rs_jpeg_encode refuses. */
+size_t rs_jpeg_encode_bound(int H, int W);
+size_t rs_jpeg_encode_workspace(int B, int H, int W);
+int rs_jpeg_encode(const void* in_u8_nhwc, void* out, int* nbytes, const int* quality, void* workspace, int B, int C, int H, int W,
+                   size_t out_pitch, void* stream);
+
 /* uint8 pre / post processing on the device.
  * rs_u8_to_input:  interleaved uint8 [B,H,W,C] -> planar fp32 [B,C,H,W] in [-1,1]  ((v/255 - 0.5)/0.5; replaces
  *                  datapipe/datasets.py:59-63 ToTensor + Normalize on the host)

@@ -150,6 +150,9 @@ SIGNATURES = {
     "rs_unit_to_u8": (_I, [_P, _P] + [_I] * 4 + [_P]),
     "rs_jpeg_codec": (_I, [_P, _P, C.POINTER(C.c_int)] + [_I] * 4 + [_P]),
     "rs_blur_resize": (_I, [_P, _P, _P] + [_I] * 9 + [_P]),
+    "rs_jpeg_encode_bound": (_SZ, [_I, _I]),
+    "rs_jpeg_encode_workspace": (_SZ, [_I, _I, _I]),
+    "rs_jpeg_encode": (_I, [_P, _P, _P, C.POINTER(C.c_int), _P] + [_I] * 4 + [_SZ, _P]),
     "rs_u8_to_input": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "rs_output_to_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rs_arena_bytes": (_SZ, [_P]),

@@ -1,5 +1,6 @@
 // rs_jpeg_codec: libjpeg's baseline JPEG round trip (include/resshift_hip.h "face degradation") - 4:2:0, the "islow" integer
-// DCT pair, the default tables, "fancy" chroma up-sampling - in ONE launch, the entropy stage (lossless) never materialised.  Between the
+// DCT pair, the default tables, "fancy" chroma up-sampling - in ONE launch, the entropy stage (lossless) never materialised (jpeg_encode.hip
+// materialises it; the forward half both share is jpeg_common.h).  Between the
 // rounding of the input and the division of the output everything is 32-bit integer arithmetic, so the result is a function of the image
 // and the quality alone, whatever the mapping, the batch or the position in it.
 //
@@ -12,7 +13,7 @@
 //      dequantise, inverse DCT, with no transposes and no barriers in between.  The tile has 128 Y blocks and, with the ring, 120
 //      chroma blocks: 248 of the 256 threads, so the ring costs no time of its own.
 //   3. pixels: a thread per output pixel, lanes along a row: triangle up-sampling from the chroma planes, YCbCr -> RGB, / 255.
-#include "image_common.h"
+#include "jpeg_common.h"
 
 constexpr int JC_TX = 8, JC_TY = 4;                          // MCUs of a tile
 constexpr int JC_THREADS = 256;
@@ -22,54 +23,6 @@ constexpr int JC_CW = (JC_TX + 2) * 8, JC_CH = (JC_TY + 2) * 8;   // a chroma pl
 constexpr int JC_YBLOCKS = 4 * JC_TX * JC_TY, JC_CBLOCKS = (JC_TX + 2) * (JC_TY + 2);
 static_assert(JC_YBLOCKS + 2 * JC_CBLOCKS <= JC_THREADS, "a thread per block");
 static_assert(JC_YW * 2 == JC_THREADS, "phase 3 maps a thread to a column of every other row");
-
-constexpr int jc_fix16(double c) { return (int)(c * 65536 + .5); }
-constexpr int jc_fix13(double c) { return (int)(c * 8192 + .5); }
-constexpr int JC_0_298 = jc_fix13(0.298631336), JC_0_390 = jc_fix13(0.390180644), JC_0_541 = jc_fix13(0.541196100), JC_0_765 = jc_fix13(0.765366865),
-              JC_0_899 = jc_fix13(0.899976223), JC_1_175 = jc_fix13(1.175875602), JC_1_501 = jc_fix13(1.501321110), JC_1_847 = jc_fix13(1.847759065),
-              JC_1_961 = jc_fix13(1.961570560), JC_2_053 = jc_fix13(2.053119869), JC_2_562 = jc_fix13(2.562915447), JC_3_072 = jc_fix13(3.072711026);
-
-// Annex K in natural order, [vertical frequency][horizontal]: luminance, chrominance
-__constant__ int JC_BASE[2][64] = {
-    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
-     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
-    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99},
-};
-
-struct JcQuality { int q[RS_MAX_ROWS]; };
-
-__device__ __forceinline__ int jc_descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-
-// the odd part both transforms share, on (t0, t1, t2, t3) = forward (t4, t5, t6, t7) / inverse (i7, i5, i3, i1)
-__device__ __forceinline__ void jc_odd(int& t0, int& t1, int& t2, int& t3) {
-    int z1 = t0 + t3, z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
-    const int z5 = (z3 + z4) * JC_1_175;
-    t0 *= JC_0_298; t1 *= JC_2_053; t2 *= JC_3_072; t3 *= JC_1_501;
-    z1 *= -JC_0_899; z2 *= -JC_2_562;
-    z3 = z3 * -JC_1_961 + z5;
-    z4 = z4 * -JC_0_390 + z5;
-    t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
-}
-
-// one 8-point pass of jfdctint.c on d[0], d[S], .. d[7 S]; ROWS: the first (row) pass
-template <bool ROWS, int S>
-__device__ __forceinline__ void jc_fdct8(int* d) {
-    const int t0 = d[0] + d[7 * S], t1 = d[S] + d[6 * S], t2 = d[2 * S] + d[5 * S], t3 = d[3 * S] + d[4 * S];
-    int t7 = d[0] - d[7 * S], t6 = d[S] - d[6 * S], t5 = d[2 * S] - d[5 * S], t4 = d[3 * S] - d[4 * S];
-    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    constexpr int n = ROWS ? 11 : 15;
-    d[0] = ROWS ? (t10 + t11) << 2 : jc_descale(t10 + t11, 2);
-    d[4 * S] = ROWS ? (t10 - t11) << 2 : jc_descale(t10 - t11, 2);
-    const int z1 = (t12 + t13) * JC_0_541;
-    d[2 * S] = jc_descale(z1 + t13 * JC_0_765, n);
-    d[6 * S] = jc_descale(z1 - t12 * JC_1_847, n);
-    jc_odd(t4, t5, t6, t7);
-    d[7 * S] = jc_descale(t4, n);
-    d[5 * S] = jc_descale(t5, n);
-    d[3 * S] = jc_descale(t6, n);
-    d[S] = jc_descale(t7, n);
-}
 
 // one 8-point pass of jidctint.c; COLS: the first (column) pass
 template <bool COLS, int S>
@@ -94,30 +47,9 @@ __device__ __forceinline__ void jc_idct8(int* d) {
 // an 8 x 8 block of samples at p (pitch bytes per row, 8-byte aligned), coded in place
 __device__ __forceinline__ void jc_code_block(unsigned char* p, int pitch, const int* tab, const float* rcp) {
     int d[64];
+    jc_forward_block(p, pitch, tab, rcp, d);
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const uint2 v = *reinterpret_cast<const uint2*>(p + r * pitch);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            d[r * 8 + j] = (int)((v.x >> (8 * j)) & 255u) - 128;
-            d[r * 8 + 4 + j] = (int)((v.y >> (8 * j)) & 255u) - 128;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) jc_fdct8<true, 1>(d + r * 8);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) jc_fdct8<false, 8>(d + c);
-    // q = sign(c) ((|c| + (8 t >> 1)) / (8 t)), then q t.  The quotient comes from the fp32 reciprocal and is put right by its remainder:
-    // the numerator is below 2^17, so the fp32 estimate is off by one at the most.
-#pragma unroll
-    for (int i = 0; i < 64; ++i) {
-        const int t = tab[i], dv = t << 3;
-        const int n = abs(d[i]) + (dv >> 1);
-        int q = (int)((float)n * rcp[i]);
-        const int rem = n - q * dv;
-        q += (rem >= dv ? 1 : 0) - (rem < 0 ? 1 : 0);
-        d[i] = (d[i] < 0 ? -q : q) * t;
-    }
+    for (int i = 0; i < 64; ++i) d[i] *= tab[i];              // dequantise
 #pragma unroll
     for (int c = 0; c < 8; ++c) jc_idct8<true, 8>(d + c);
 #pragma unroll
@@ -153,44 +85,17 @@ __global__ __launch_bounds__(JC_THREADS) void jpeg_codec_kernel(const float* __r
         const int mx0 = tx * JC_TX, my0 = ty * JC_TY;        // the tile's first MCU
         const float* inp = in + img * 3 * HW;
         float* outp = out + img * 3 * HW;
-        if (tid < 128) {   // jpeg_set_quality(q, force_baseline) of Annex K
-            const int q = qual.q[img], s = q < 50 ? 5000 / q : 200 - 2 * q;
-            const int t = min(max((JC_BASE[tid >> 6][tid & 63] * s + 50) / 100, 1), 255);
-            tab[tid >> 6][tid & 63] = t;
-            rcp[tid >> 6][tid & 63] = 1.0f / (float)(t << 3);
-        }
-        // 1. colour.  Quad (qy, qx) of tile + ring is the chroma sample (cy, cx) of the image's padded planes.  libjpeg replicates pixels on
-        // the right at full resolution, at the bottom at full resolution up to an even row count only, and from there the DOWN-SAMPLED chroma
-        // rows and the Y rows: chroma row cy >= CHr is row CHr - 1, Y row y >= H is row H - 1.
+        jc_stage_tables(qual.q[img], tid, tab, rcp);
+        // 1. colour.  Quad (qy, qx) of tile + ring is the chroma sample (cy, cx) of the image's padded planes (jc_quad has libjpeg's edge rules)
+        const auto px = [&](long long o, int& r, int& g, int& b) { r = jc_u8(inp[o]); g = jc_u8(inp[HW + o]); b = jc_u8(inp[2 * HW + o]); };
         for (int i = tid; i < JC_CH * JC_CW; i += JC_THREADS) {
             const int qy = i / JC_CW, qx = i - qy * JC_CW;
             const int my = my0 - 1 + (qy >> 3), mx = mx0 - 1 + (qx >> 3);
             if (my < 0 || my >= mcus_y || mx < 0 || mx >= mcus_x) continue;   // (no such MCU: its samples are never read)
-            const int cy = my * 8 + (qy & 7), cx = mx * 8 + (qx & 7);
-            const int cyc = min(cy, CHr - 1);
-            const int r0 = min(2 * cyc, H - 1), r1 = min(2 * cyc + 1, H - 1), c0 = min(2 * cx, W - 1), c1 = min(2 * cx + 1, W - 1);
-            int yv[2][2], cb = 0, cr = 0;
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx) {
-                    const long long o = (long long)(dy ? r1 : r0) * W + (dx ? c1 : c0);
-                    const int r = jc_u8(inp[o]), g = jc_u8(inp[HW + o]), b = jc_u8(inp[2 * HW + o]);
-                    yv[dy][dx] = (jc_fix16(.299) * r + jc_fix16(.587) * g + jc_fix16(.114) * b + 32768) >> 16;
-                    cb += (-jc_fix16(.16874) * r - jc_fix16(.33126) * g + jc_fix16(.5) * b + (128 << 16) + 32767) >> 16;
-                    cr += (jc_fix16(.5) * r - jc_fix16(.41869) * g - jc_fix16(.08131) * b + (128 << 16) + 32767) >> 16;
-                }
-            const int bias = 1 + (cx & 1);
-            Cp[0][i] = (unsigned char)((cb + bias) >> 2);
-            Cp[1][i] = (unsigned char)((cr + bias) >> 2);
-            if (qy >= 8 && qy < JC_CH - 8 && qx >= 8 && qx < JC_CW - 8) {
-                const bool below = cy > cyc;                  // Y rows past the image: the last row (r1) twice
-                unsigned char* yp = Yp + (qy - 8) * 2 * JC_YP + (qx - 8) * 2;
-                yp[0] = (unsigned char)(below ? yv[1][0] : yv[0][0]);
-                yp[1] = (unsigned char)(below ? yv[1][1] : yv[0][1]);
-                yp[JC_YP] = (unsigned char)yv[1][0];
-                yp[JC_YP + 1] = (unsigned char)yv[1][1];
-            }
+            const JcQuad qd = jc_quad(px, my * 8 + (qy & 7), mx * 8 + (qx & 7), H, W);
+            Cp[0][i] = (unsigned char)qd.cb;
+            Cp[1][i] = (unsigned char)qd.cr;
+            if (qy >= 8 && qy < JC_CH - 8 && qx >= 8 && qx < JC_CW - 8) jc_quad_store_y(qd, Yp + (qy - 8) * 2 * JC_YP + (qx - 8) * 2, JC_YP);
         }
         __syncthreads();
         // 2. blocks

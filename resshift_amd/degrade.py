@@ -500,17 +500,39 @@ def list_images(path) -> list:
     return [p for e in IMAGE_EXTS for p in sorted(path.glob(f"**/*.{e}"))]
 
 
-def write_plans(lq_dir, plans) -> None:
-    """lq_dir/plans.json: {stem: plan as a dict}, sorted by stem"""
+FILES_KEY = "_files"   # plans.json: how the LQ files were written, where that is not the default PNG
+
+
+def write_plans(lq_dir, plans, ext="png", quality=None) -> None:
+    """lq_dir/plans.json: {stem: plan as a dict}, sorted by stem; for JPEG files also {"_files": {"ext": "jpg", "quality": q}}"""
+    table = {k: p.to_dict() for k, p in sorted(plans.items())}
+    if ext != "png":
+        table[FILES_KEY] = {"ext": ext, "quality": quality}
     with open(Path(lq_dir) / "plans.json", "w") as fh:
-        json.dump({k: p.to_dict() for k, p in sorted(plans.items())}, fh, indent=1)
+        json.dump(table, fh, indent=1)
 
 
-def _make_set(gt_dir, lq_dir, size_error, plan_for, run_u8, device, seed, positions) -> dict:
+def _file_format(ext, quality):
+    """(ext, quality) of the LQ files: "png", or "jpg" with an integer quality 1 .. 100 (default 95)"""
+    if ext not in ("png", "jpg"):
+        raise ValueError(f"ext must be 'png' or 'jpg', not {ext!r}")
+    if ext == "png":
+        if quality is not None:
+            raise ValueError("quality belongs to ext='jpg'")
+        return ext, None
+    quality = 95 if quality is None else quality
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError(f"quality must be an integer in 1 .. 100, not {quality!r}")
+    return ext, quality
+
+
+def _make_set(gt_dir, lq_dir, size_error, plan_for, run_u8, device, seed, positions, ext="png", quality=None) -> dict:
     """what `make_testset` and `make_face_testset` share.  size_error(h, w): None, or why the recipe does not take an image of that size;
-    plan_for(h, w, seed): the image's plan; run_u8(degrader, uint8 [1,H,W,3], plan): its LQ image, uint8 [1,h,w,3] on the device."""
+    plan_for(h, w, seed): the image's plan; run_u8(degrader, uint8 [1,H,W,3], plan): its LQ image, uint8 [1,h,w,3] on the device.
+    ext="jpg": the LQ image is written as a real JPEG at `quality`, coded on the device (ImageOps.jpeg_encode)."""
     from PIL import Image
 
+    ext, quality = _file_format(ext, quality)
     files = list_images(gt_dir)
     todo = list(range(len(files))) if positions is None else list(positions)
     sizes = {}
@@ -528,23 +550,28 @@ def _make_set(gt_dir, lq_dir, size_error, plan_for, run_u8, device, seed, positi
     for i in todo:
         plan = plan_for(*sizes[i], request_seed(seed, i))
         gt = torch.from_numpy(np.asarray(Image.open(files[i]).convert("RGB"), dtype=np.uint8).copy()).unsqueeze(0)
-        lq = run_u8(dg, gt, plan)[0].cpu().numpy()
-        Image.fromarray(lq).save(lq_dir / f"{files[i].stem}.png")
+        lq = run_u8(dg, gt, plan)
+        if ext == "png":
+            Image.fromarray(lq[0].cpu().numpy()).save(lq_dir / f"{files[i].stem}.png")
+        else:
+            (lq_dir / f"{files[i].stem}.jpg").write_bytes(dg.ops.jpeg_encode(lq, quality)[0])
         plans[files[i].stem] = plan
     if positions is None:
-        write_plans(lq_dir, plans)
+        write_plans(lq_dir, plans, ext, quality)
     return plans
 
 
-def make_testset(gt_dir, lq_dir, sf=4, opts: DegradeOptions = REALESRGAN_TESTING, seed=10000, device=None, positions=None) -> dict:
+def make_testset(gt_dir, lq_dir, sf=4, opts: DegradeOptions = REALESRGAN_TESTING, seed=10000, device=None, positions=None, ext="png",
+                 quality=None) -> dict:
     """A folder of ground-truth images -> lq_dir/<stem>.png, degraded on the device, plus lq_dir/plans.json {stem: plan}.  The image at
     position i of the sorted listing gets one plan with B = 1 from the seed continuous.request_seed(seed, i): a file's LQ image depends
     on its position and the seed only.  Every side of every image must be a multiple of `sf` (ValueError naming the file, before
     anything is written).  `device`: a device or an Engine.  `positions` (of the listing; default: all of it): the files this call
-    degrades - the caller then writes plans.json itself (`write_plans`) from what its ranks return.  Returns {stem: DegradePlan}."""
+    degrades - the caller then writes plans.json itself (`write_plans`) from what its ranks return.  `ext="jpg"`: lq_dir/<stem>.jpg
+    instead, real JPEG files at `quality` (1 .. 100, default 95) coded on the device; plans.json records both.  Returns {stem: DegradePlan}."""
     opts = dataclasses.replace(opts, sf=int(sf))
     return _make_set(gt_dir, lq_dir, lambda h, w: f"is no multiple of sf = {opts.sf}" if h % opts.sf or w % opts.sf else None,
-                     lambda h, w, s: draw_plan(opts, 1, h, w, s), lambda dg, gt, plan: dg.run_u8(gt, plan), device, seed, positions)
+                     lambda h, w, s: draw_plan(opts, 1, h, w, s), lambda dg, gt, plan: dg.run_u8(gt, plan), device, seed, positions, ext, quality)
 
 
 def make_face_testset(gt_dir, lq_dir, opts: FaceOptions = FACE_TESTING, seed=10000, device=None, positions=None) -> dict:
@@ -565,11 +592,16 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=10000)
     ap.add_argument("--recipe", choices=("realesrgan", "face"), default="realesrgan",
                     help="face: datapipe/face_degradation_testing.py (the LQ images keep the ground truth's size; --sf is not used)")
+    ap.add_argument("--ext", choices=("png", "jpg"), default="png", help="jpg (realesrgan recipe): the LQ files are JPEGs coded on the device")
+    ap.add_argument("--quality", type=int, default=None, help="the JPEG quality of --ext jpg, 1 .. 100 (default 95)")
     a = ap.parse_args(argv)
     if a.recipe == "face":
+        if a.ext != "png" or a.quality is not None:
+            ap.error("--ext / --quality belong to the realesrgan recipe")
         plans = make_face_testset(a.gt_dir, a.lq_dir, seed=a.seed)
     else:
-        plans = make_testset(a.gt_dir, a.lq_dir, sf=a.sf, seed=a.seed)
+        fmt = {} if a.ext == "png" and a.quality is None else dict(ext=a.ext, quality=a.quality)
+        plans = make_testset(a.gt_dir, a.lq_dir, sf=a.sf, seed=a.seed, **fmt)
     print(f"{len(plans)} images -> {a.lq_dir} (plans.json)")
 
 

@@ -1,4 +1,4 @@
-"""The image operators around the sampler (include/resshift_hip.h "colour correction" .. "face degradation"): the argument
+"""The image operators around the sampler (include/resshift_hip.h "colour correction" .. "JPEG files"): the argument
 checks and the ctypes call of each as a module function on contiguous device tensors, and `ImageOps`, the same on a device for callers
 that hand over any float tensor - `Engine` inherits it, `degrade.Degrader` builds one when it has no engine.  `_lib.<name>` still finds
 every public name of this module."""
@@ -14,6 +14,7 @@ from ._lib import COLOR_FIX_MODES, RS_MAX_ROWS, check, current_stream_ptr, load,
 
 __all__ = ["ImageOps", "color_fix", "RESIZE_SCALES", "resize_len", "resize", "FILTER_KMAX", "INTERP_MODES", "filter2d", "interp_size", "interpolate",
            "jpeg", "add_noise", "unit_to_u8", "BLUR_RESIZE_KMAX", "BLUR_RESIZE_SCALES", "JPEG_CODEC_MIN", "jpeg_codec", "blur_resize",
+           "JPEG_ENCODE_MAX", "jpeg_encode_bound", "jpeg_encode",
            "METRICS_TAPS", "metrics", "rgb_to_y"]
 
 
@@ -164,6 +165,14 @@ def _per_image(values, B, who, what):
     return vals
 
 
+def _qualities(who, quality, B):
+    """one integer quality 1 .. 100 per image, from one for all or a sequence of B"""
+    q = [quality] * B if isinstance(quality, bool) else _per_image(quality, B, who, "qualities")
+    if not all(isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= 100 for v in q):
+        raise ValueError(f"{who}: every quality must be an integer in 1 .. 100, not {q}")
+    return q
+
+
 def jpeg(x, quality):
     """rs_jpeg: the reference's DiffJPEG(differentiable=False) on x [B,3,H,W] (a contiguous fp32 device tensor in [0,1] - the caller clamps),
     `quality` one number per image (or one for all) in (0, 100) exclusive.  Batches above RS_MAX_ROWS go in chunks (the qualities travel by
@@ -228,9 +237,7 @@ def jpeg_codec(x, quality):
         raise ValueError(f"jpeg_codec: C must be 3 (RGB), not {Cc}")
     if H < JPEG_CODEC_MIN or W < JPEG_CODEC_MIN:
         raise ValueError(f"jpeg_codec: H and W must be at least {JPEG_CODEC_MIN}, not {H} x {W}")
-    q = [quality] * B if isinstance(quality, bool) else _per_image(quality, B, "jpeg_codec", "qualities")
-    if not all(isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= 100 for v in q):
-        raise ValueError(f"jpeg_codec: every quality must be an integer in 1 .. 100, not {q}")
+    q = _qualities("jpeg_codec", quality, B)
     out = torch.empty_like(x)
     lib = load()
     for s in _row_chunks(B):
@@ -252,6 +259,54 @@ def blur_resize(x, kernels, size, clamp=False):
     check(load().rs_blur_resize(x.data_ptr(), kernels.data_ptr() if kernels is not None else None, out.data_ptr(), B, Cc, H, W, Ho, Wo, k, Bk,
                                 1 if clamp else 0, current_stream_ptr()), "rs_blur_resize")
     return out
+
+
+# ---- JPEG files (include/resshift_hip.h "JPEG files") --------------------------------------------------------------------
+JPEG_ENCODE_MAX = 65535   # rs_jpeg_encode: the largest height and width (the SOF0 fields)
+
+
+def jpeg_encode_bound(H, W) -> int:
+    """rs_jpeg_encode_bound: the bytes a JPEG file of an H x W image can reach - the header, every block at its longest code with every
+    byte of the scan stuffed, EOI"""
+    return int(load().rs_jpeg_encode_bound(int(H), int(W)))
+
+
+def jpeg_encode(x, quality):
+    """rs_jpeg_encode: the images x -> their baseline JPEG files, one `bytes` per image, each byte for byte what
+    PIL.Image.save(format="JPEG", quality=q, subsampling=2) writes.  x is a contiguous device tensor, uint8 [B,H,W,3] in RGB order (what
+    `output_to_u8` / `unit_to_u8` return) or float32 [B,3,H,W] in [0,1], which `unit_to_u8` rounds first - rint(clip(x, 0, 1) * 255), the
+    input step of `jpeg_codec`; 8 <= H, W <= 65535; `quality` one integer per image (or one for all) in 1 .. 100.  Batches above
+    RS_MAX_ROWS go in chunks.  The files are coded on the device; per chunk one device-to-host copy of the lengths and one of the used
+    bytes of the rows - never the rows' bound."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.is_contiguous() and x.dim() == 4 and x.dtype in (torch.uint8, torch.float32)):
+        raise ValueError("jpeg_encode: x must be a contiguous device tensor, uint8 [B,H,W,3] or float32 [B,3,H,W] in [0,1]")
+    B = int(x.shape[0])
+    Cc, H, W = (int(x.shape[3]), int(x.shape[1]), int(x.shape[2])) if x.dtype == torch.uint8 else (int(v) for v in x.shape[1:])
+    if Cc != 3:
+        raise ValueError(f"jpeg_encode: C must be 3 (RGB), not {Cc}")
+    if B < 1:
+        raise ValueError("jpeg_encode: an empty batch")
+    if not (JPEG_CODEC_MIN <= H <= JPEG_ENCODE_MAX and JPEG_CODEC_MIN <= W <= JPEG_ENCODE_MAX):
+        raise ValueError(f"jpeg_encode: H and W must lie in {JPEG_CODEC_MIN} .. {JPEG_ENCODE_MAX}, not {H} x {W}")
+    q = _qualities("jpeg_encode", quality, B)
+    lib = load()
+    u8 = x if x.dtype == torch.uint8 else unit_to_u8(x)
+    pitch = (int(lib.rs_jpeg_encode_bound(H, W)) + 255) // 256 * 256
+    files = []
+    for s in _row_chunks(B):
+        n = s.stop - s.start
+        need = int(lib.rs_jpeg_encode_workspace(n, H, W))
+        if need == 0:
+            raise ValueError(f"jpeg_encode: {H} x {W} is too large (rs_jpeg_encode takes about 55 megapixels)")
+        out = torch.empty((n, pitch), device=x.device, dtype=torch.uint8)
+        work = torch.empty(need, device=x.device, dtype=torch.uint8)
+        nbytes = torch.empty(n, device=x.device, dtype=torch.int32)
+        check(lib.rs_jpeg_encode(u8[s].data_ptr(), out.data_ptr(), nbytes.data_ptr(), (C.c_int * n)(*q[s]), work.data_ptr(), n, 3, H, W, pitch,
+                                 current_stream_ptr()), "rs_jpeg_encode")
+        lens = nbytes.cpu().tolist()
+        host = out[:, :max(lens)].cpu().numpy()       # (the columns any file of the chunk uses)
+        files += [host[i, :lens[i]].tobytes() for i in range(n)]
+    return files
 
 
 METRICS_TAPS = 11   # the SSIM window: the cropped image must be at least 11 x 11
@@ -375,6 +430,13 @@ class ImageOps:
         """bilinear(filter2d(x, kernels), size) in one launch with kernels of up to 41 taps; kernels=None: the resize alone (rs_blur_resize)."""
         with torch.cuda.device(self.device):
             return blur_resize(self._f32c(x), None if kernels is None else self._f32c(kernels), size, clamp=clamp)
+
+    # JPEG files (DESIGN.md 7j)
+    def jpeg_encode(self, x, quality):
+        """x - uint8 [B,H,W,3] RGB, or a float tensor [B,3,H,W] in [0,1] - as baseline JPEG files coded on the device, one `bytes` per image
+        and one integer quality 1 .. 100 per image: byte for byte PIL's save(format="JPEG", quality=q, subsampling=2) (rs_jpeg_encode)."""
+        with torch.cuda.device(self.device):
+            return jpeg_encode(x.detach().contiguous() if x.dtype == torch.uint8 else self._f32c(x), quality)
 
     def metrics(self, sr, gt, border=0, ycbcr=True):
         """PSNR / SSIM of the batch `sr` against the ground truth `gt` on uint8 pixels, as the reference's calculate_psnr / calculate_ssim

@@ -309,7 +309,7 @@ class ResShiftSampler(BaseSampler):
         return rows
 
     def inference(self, in_path, out_path, mask_path=None, mask_back=True, bs=1, noise_repeat=False, pool=False, seeded=False, gt_path=None,
-                  metric_border=0, metric_ycbcr=True):
+                  metric_border=0, metric_ycbcr=True, out_ext="png", jpeg_quality=95):
         """sampler.py:167-308: batches of `bs` images are sharded over the ranks exactly like sampler.py:273-277; every
         rank writes its own PNGs.  uint8 -> [-1,1] (datapipe/datasets.py:59-63), the inpainting blend (sampler.py:218-222)
         and the final clamp / round to uint8 (utils/util_image.py:245-269) run on the device (rs_u8_to_input /
@@ -326,9 +326,23 @@ class ResShiftSampler(BaseSampler):
         the inpainting blend, the colour fix and `out_scale`): PSNR and SSIM as the reference's calculate_psnr / calculate_ssim compute
         them (Engine.metrics), `metric_border` pixels cropped, on MATLAB's Y channel when `metric_ycbcr`.  Returns
         {stem: (psnr, ssim)} for the whole input on every rank; rank 0 writes out_path/metrics.csv.  A missing ground-truth file raises
-        FileNotFoundError before anything is sampled, one of another size than the output ValueError."""
+        FileNotFoundError before anything is sampled, one of another size than the output ValueError.
+        `out_ext`: "png" (the default: the PNGs above, not a launch or a byte changed) or "jpg": every image is written as
+        out_path/{stem}.jpg, a baseline JPEG at `jpeg_quality` (an integer 1 .. 100) coded on the device from the same uint8 tensor
+        (Engine.jpeg_encode, DESIGN.md 7j: the bytes of PIL's save(quality=jpeg_quality, subsampling=2)), on the batch, the tiled and the
+        `pool` route alike - only compressed bytes cross PCIe.  With `gt_path` the scores remain those of that uint8 tensor, the image
+        BEFORE the JPEG coding; the file on disk is its JPEG.  A one-channel output has no JPEG here: ValueError before anything is
+        sampled or written, like any other `out_ext` and a `jpeg_quality` outside 1 .. 100."""
         if seeded and noise_repeat:
             raise ValueError("seeded=True names every draw by (seed, stream): it excludes noise_repeat")
+        if out_ext not in ("png", "jpg"):
+            raise ValueError(f"out_ext must be 'png' or 'jpg', not {out_ext!r}")
+        if out_ext == "jpg":
+            if isinstance(jpeg_quality, bool) or not isinstance(jpeg_quality, int) or not 1 <= jpeg_quality <= 100:
+                raise ValueError(f"jpeg_quality must be an integer in 1 .. 100, not {jpeg_quality!r}")
+            out_ch = int(self.configs["autoencoder"]["params"]["ddconfig"]["out_ch"])
+            if out_ch != 3:
+                raise ValueError(f"out_ext='jpg' needs a three-channel (RGB) output; this model's has {out_ch}")
         finish = Finish.of(self)   # (the options are checked before anything is touched; sample_tiled and the TilePool build their own)
         if mask_path is not None:
             finish.reject_mask("inference")
@@ -353,7 +367,10 @@ class ResShiftSampler(BaseSampler):
             rows = {}
         score = (lambda u8, fs: rows.update(self._score(u8, fs, gt_path, single, metric_border, metric_ycbcr))) if rows is not None else None
         load = lambda fs: self._load(fs, mask_path, single)
-        write = lambda sr, lq, mask, fs: self._write_pngs(sr, lq, mask, mask_back, fs, out_path, score)
+        if out_ext == "png":
+            write = lambda sr, lq, mask, fs: self._write_pngs(sr, lq, mask, mask_back, fs, out_path, score)
+        else:
+            write = lambda sr, lq, mask, fs: self._write_jpgs(sr, lq, mask, mask_back, fs, out_path, jpeg_quality, score)
         if pool:
             self._inference_pool(self._shares(files, bs), load, write, noise_repeat, seeded)
         else:
@@ -411,17 +428,26 @@ class ResShiftSampler(BaseSampler):
         mpaths = [Path(mask_path)] if single else [Path(mask_path) / p.name for p in files]
         return lq, self.engine.u8_to_input(torch.stack([self._read_image_u8(m, gray=True) for m in mpaths]).to(self.device))
 
-    def _write_pngs(self, sr, lq, mask, mask_back, files, out_path, score=None):
-        """the finished batch sr [n,C,H,W] of `files` -> their PNGs: the inpainting blend and the rounding on the device, `score(u8, files)`
-        on the very uint8 device tensor that is then written"""
-        from PIL import Image
-
+    def _output_u8(self, sr, lq, mask, mask_back, files, score=None):
+        """the finished batch sr [n,C,H,W] of `files` -> uint8 [n,H,W,C] on the device: the inpainting blend and the rounding there,
+        `score(u8, files)` on the very tensor that is then written"""
         blend = mask is not None and mask_back
         out_u8 = self.engine.output_to_u8(sr, lq=lq if blend else None, mask=mask if blend else None)
         if score is not None:
             score(out_u8, files)
-        for p, im in zip(files, out_u8.cpu().numpy()):
+        return out_u8
+
+    def _write_pngs(self, sr, lq, mask, mask_back, files, out_path, score=None):
+        """the finished batch of `files` -> their PNGs: the uint8 pixels cross PCIe, Pillow encodes on the host"""
+        from PIL import Image
+
+        for p, im in zip(files, self._output_u8(sr, lq, mask, mask_back, files, score).cpu().numpy()):
             Image.fromarray(im if im.shape[2] != 1 else im[:, :, 0]).save(out_path / f"{p.stem}.png")
+
+    def _write_jpgs(self, sr, lq, mask, mask_back, files, out_path, quality, score=None):
+        """`_write_pngs` for out_ext="jpg": the same uint8 device tensor, coded to JPEG files on the device - only their bytes cross PCIe"""
+        for p, data in zip(files, self.engine.jpeg_encode(self._output_u8(sr, lq, mask, mask_back, files, score), quality)):
+            (out_path / f"{p.stem}.jpg").write_bytes(data)
 
     def _inference_pool(self, shares, load, write, noise_repeat, seeded):
         """the files of `shares`, one by one, through ONE TilePool: submitted ahead while fewer than POOL_LOOKAHEAD tiles wait; an image
