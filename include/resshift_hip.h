@@ -12,8 +12,14 @@
  *     Tensor.data_ptr()); the engine never frees caller memory;
  *   - user-facing image / latent tensors are NCHW fp32 like the reference's; the NHWC fp16/fp32
  *     working layout is internal;
- *   - work is enqueued on the caller's hipStream_t (pass torch's current stream); one engine per
- *     device, not thread-safe;
+ *   - work is enqueued on the caller's hipStream_t (pass torch's current stream) - every launch, memset and copy of a call, on any
+ *     stream, non-blocking ones included: nothing relies on the null stream's legacy ordering (tests/test_streams_gpu.py runs every
+ *     entry on a side stream behind a producer that is still running).  After one warm-up call of the same shapes (the scratch arena
+ *     grows and a timestep's FiLM row is built behind a stream synchronise, on first use) the network, sampling, tile and image calls
+ *     return without waiting for the stream; rs_jpeg_encode's host wrapper, the debug trace and the rs_op_* test entries may wait;
+ *   - one engine per device, not thread-safe.  An engine's scratch (arena, GroupNorm pools, tickets, FiLM rows, key staging) is shared
+ *     by its calls, so the caller orders the calls of ONE engine across streams (event / stream wait); calls of different engines, and
+ *     the stateless rs_tile_* / image operators, need no ordering among themselves: there is no device-global scratch;
  *   - precision: RS_PREC_F16 = fp16 storage / fp32 accumulate MFMA, RS_PREC_F32 = fp32 storage /
  *     exact fp32 MFMA, RS_PREC_SPLIT = (hi, lo) fp16 pair storage (x = hi + lo * 2^-11, 4 bytes per
  *     element) / three fp16 MFMAs per product, fp32 accumulate: fp32-class results at 1/3 of the
@@ -127,8 +133,9 @@ int rs_bind_weight_blob(rs_engine* e, void* dev, size_t bytes);
 int rs_pack_weights(rs_engine* e);
 /* broadcast the bound blob from rank `root` over the HOST's RCCL communicator (`rccl_comm`: an ncclComm_t; one ncclBroadcast of
  * rs_weight_bytes() bytes, in place, on `stream`): what replaces the reference's per-rank checkpoint load (sampler.py:66-77, utils/util_net.py
- * reload_model) for a host without torch.distributed.  RCCL is dlopen'ed at call time - no link dependency.  Every rank calls rs_weights_ready()
- * afterwards. */
+ * reload_model) for a host without torch.distributed.  RCCL is dlopen'ed at call time - no link dependency.  The call synchronises `stream`
+ * before it returns, so the received bytes are there: every rank calls rs_weights_ready() afterwards, which reads the blob's header and
+ * per-layer flags back with plain copies, and needs no synchronisation of the caller's in between. */
 int rs_bcast_weights(rs_engine* e, void* rccl_comm, int root, void* stream);
 /* tell the engine the blob content is valid (after pack or after a broadcast) */
 int rs_weights_ready(rs_engine* e);

@@ -48,18 +48,33 @@ struct rs_engine : Model {
     bool debug = false;
     std::vector<TraceRec> trace;                        // records of the last traced call (Exec::tr)
     // per-request seeds (philox.h): the keys of a seeded batch of more than RS_MAX_ROWS images, copied to the device once per call
-    rs_noise_key* keys_dev = nullptr; size_t keys_cap = 0;
+    // The copy does not wait for the stream (a blocking copy would hold the host until everything queued before the call has run): the
+    // keys go through a pinned staging array, and an event says when the previous call's copy has read it.
+    rs_noise_key* keys_dev = nullptr; rs_noise_key* keys_pin = nullptr; size_t keys_cap = 0;
+    hipEvent_t keys_ev = nullptr; bool keys_ev_set = false;
+    void free_keys() {
+        if (keys_dev) (void)hipFree(keys_dev);
+        if (keys_pin) (void)hipHostFree(keys_pin);
+        if (keys_ev) (void)hipEventDestroy(keys_ev);
+        keys_dev = keys_pin = nullptr; keys_cap = 0; keys_ev = nullptr; keys_ev_set = false;
+    }
     const rs_noise_key* stage_keys(const rs_noise_key* keys, int B, hipStream_t st) {
         if (rs_fake_device()) return (const rs_noise_key*)(uintptr_t)4096;   // (never dereferenced: every launch fails there)
+        const size_t bytes = (size_t)B * sizeof(rs_noise_key);
         if ((size_t)B > keys_cap) {
             (void)hipStreamSynchronize(st);
-            if (keys_dev) (void)hipFree(keys_dev);
-            keys_dev = nullptr; keys_cap = 0;
-            if (hipMalloc((void**)&keys_dev, (size_t)B * sizeof(rs_noise_key)) != hipSuccess) return nullptr;
+            if (keys_ev_set) (void)hipEventSynchronize(keys_ev);
+            free_keys();
+            if (hipMalloc((void**)&keys_dev, bytes) != hipSuccess || hipHostMalloc((void**)&keys_pin, bytes, hipHostMallocDefault) != hipSuccess ||
+                hipEventCreateWithFlags(&keys_ev, hipEventDisableTiming) != hipSuccess) { free_keys(); return nullptr; }
             keys_cap = (size_t)B;
         }
-        // (stream-ordered and complete on return: the caller's host array may go away, and an earlier call's kernels no longer read the buffer)
-        if (hipMemcpyWithStream(keys_dev, keys, (size_t)B * sizeof(rs_noise_key), hipMemcpyHostToDevice, st) != hipSuccess) return nullptr;
+        if (keys_ev_set) (void)hipEventSynchronize(keys_ev);   // the previous call's copy has left the staging array (long done in a serial caller)
+        memcpy(keys_pin, keys, bytes);                          // (the caller's host array may go away on return)
+        // stream-ordered: an earlier call's kernels on this stream no longer read the device buffer when the copy lands
+        if (hipMemcpyAsync(keys_dev, keys_pin, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return nullptr;
+        keys_ev_set = hipEventRecord(keys_ev, st) == hipSuccess;
+        if (!keys_ev_set) (void)hipStreamSynchronize(st);
         return keys_dev;
     }
     char* cap_base = nullptr; size_t cap_bytes = 0; bool cap_host = false;   // their capture region (run(); freed by rs_debug_enable(0))
@@ -261,7 +276,7 @@ void rs_destroy(rs_engine* e) {
     if (!rs_fake_device()) {
         for (auto& kv : e->film_cache) (void)hipFree(kv.second);
         if (e->arena.base) (void)hipFree(e->arena.base);
-        if (e->keys_dev) (void)hipFree(e->keys_dev);
+        e->free_keys();
     }
     e->free_capture();
     delete e;
@@ -307,6 +322,9 @@ int rs_bcast_weights(rs_engine* e, void* rccl_comm, int root, void* stream) {
     const int rc = fn(e->blob.base, e->blob.base, e->blob_bytes, /* ncclUint8 */ 1, root, rccl_comm, (hipStream_t)stream);
     if (rc != 0) return fail("rs_bcast_weights: ncclBroadcast failed (ncclResult_t " + std::to_string(rc) + ")");
     e->ready = false;   // (the receiving ranks' flags are read back by rs_weights_ready)
+    // rs_weights_ready reads the blob header and the per-layer flags with copies that wait for no caller stream: the received bytes must be
+    // there when this call returns (once per process; a non-blocking stream would otherwise leave a window for a stale read)
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return fail("rs_bcast_weights: the broadcast did not complete on its stream");
     return 0;
 }
 

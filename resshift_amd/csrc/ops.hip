@@ -18,9 +18,10 @@ static void* dev_copy(const void* host, size_t bytes) {
     return d;
 }
 // fragment-major copy (weight_pack.h) of a row-major DEVICE operand: rows of `ld` halfs, lo plane at +lo_off halfs (< 0: fp16 only) -> device copy
-static void* frag_major_from_device_rows(const void* wdev, int N, int K, int ld, int lo_off) {
+// (the operand is the caller's, possibly still being written on the caller's stream `st`: the read-back waits for that stream first)
+static void* frag_major_from_device_rows(const void* wdev, int N, int K, int ld, int lo_off, hipStream_t st) {
     std::vector<f16> rows((size_t)N * ld), out((size_t)N * K * (lo_off >= 0 ? 2 : 1));
-    if (hipMemcpy(rows.data(), wdev, rows.size() * sizeof(f16), hipMemcpyDeviceToHost) != hipSuccess) return nullptr;
+    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(rows.data(), wdev, rows.size() * sizeof(f16), hipMemcpyDeviceToHost) != hipSuccess) return nullptr;
     frag_major_fill(N, K, out.data(), lo_off >= 0, [&](int n, int k) { return rows[(size_t)n * ld + k]; },
                     [&](int n, int k) { return rows[(size_t)n * ld + (lo_off >= 0 ? lo_off : 0) + k]; });
     return dev_copy(out.data(), out.size() * sizeof(f16));
@@ -202,7 +203,7 @@ int rs_op_conv3x3_wino(const void* x, const float* coef_dev, int act_in, const f
     const int ntile = rs_wino_tiles(&p);
     p.dbg = 64;   // (an op-level entry: no fill-the-chip threshold)
     p.dbg |= (int)rs_env_int("RS_WINO_ABL", 0);   // (-DRS_WINO_PHASES builds: timing ablations, wino.hip)
-    if (rs_env_set("RS_WINO_STAMPS")) { (void)hipMalloc((void**)&stamps, (size_t)ntile * 16 * sizeof(float)); (void)hipMemset(stamps, 0, (size_t)ntile * 16 * sizeof(float)); p.partial = stamps; }
+    if (rs_env_set("RS_WINO_STAMPS")) { (void)hipMalloc((void**)&stamps, (size_t)ntile * 16 * sizeof(float)); (void)hipMemsetAsync(stamps, 0, (size_t)ntile * 16 * sizeof(float), st); p.partial = stamps; }
     ConvPlan pl{};
     (void)rs_conv_plan(&p, RS_F16S, RS_F16S, 1, &pl);
     if (pl.kernel != CK_WINO) rc = rs_set_last_error("shape is not eligible for the wino kernel", -1);
@@ -307,8 +308,8 @@ static int op_window_attention_qkv(bool split, const void* x, const void* wqkv_d
     WinAttnParams p{};
     p.bias_n = dn; p.bias_c = dc; p.out = out; p.B = B; p.H = H; p.W = W; p.heads = heads; p.shift = shift; p.ldo = heads * 32; p.scale = 1.0f / std::sqrt(32.0f);
     const int E = heads * 32, ld = split ? 2 * E : E, lo_off = split ? E : -1;
-    void* wq_f = frag_major_from_device_rows(wqkv_dev, 3 * E, E, ld, lo_off);
-    void* wp_f = wproj_dev ? frag_major_from_device_rows(wproj_dev, E, E, ld, lo_off) : nullptr;
+    void* wq_f = frag_major_from_device_rows(wqkv_dev, 3 * E, E, ld, lo_off, st);
+    void* wp_f = wproj_dev ? frag_major_from_device_rows(wproj_dev, E, E, ld, lo_off, st) : nullptr;
     p.x = x; p.wqkv = wq_f; p.bqkv = bqkv_dev; p.ldx = heads * 32; p.xcoef = xcoef_dev;
     p.wproj = wp_f; p.bproj = bproj_dev; p.res = res; p.ldres = heads * 32;
     const int rc = !(wq_f && (wp_f || !wproj_dev)) ? -1 : (split ? rs_win_attn_qkv_split_launch(&p, st) : rs_win_attn_qkv_launch(&p, st));
