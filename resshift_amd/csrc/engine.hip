@@ -259,11 +259,19 @@ rs_engine* rs_create(const rs_config* cfg) {
     if (!cfg->has_unet && !cfg->has_ae) { g_err = "config has neither a UNet nor an autoencoder"; return nullptr; }
     if (cfg->has_unet) {
         if (u.window_size != 8) { g_err = "only window_size 8 is supported"; return nullptr; }
-        if (u.num_heads < 1 || u.swin_embed_dim != u.num_heads * 32) { g_err = "swin head dim must be 32"; return nullptr; }
+        if (u.num_heads < 1 || u.swin_embed_dim != u.num_heads * 32) { g_err = "swin_embed_dim / num_head_channels: the swin head dim must be 32"; return nullptr; }
         if (u.n_levels < 1 || u.n_levels > RS_MAX_LEVELS) { g_err = "bad n_levels"; return nullptr; }
-        if ((u.image_size >> (u.n_levels - 1)) < 8) { g_err = "coarsest UNet level must be >= 8x8"; return nullptr; }
+        if ((u.image_size >> (u.n_levels - 1)) < 8) { g_err = "image_size / channel_mult: the coarsest UNet level must be >= 8x8"; return nullptr; }
     }
     if (cfg->has_ae && cfg->ae.n_attn_res != 0) { g_err = "AE attn_resolutions must be empty"; return nullptr; }
+    if (cfg->has_ae) {
+        // what the VQ search (elementwise.hip: rs_vq_launch) is instantiated for and keeps in LDS: refused here, not at the first decode
+        const rs_ae_config& a = cfg->ae;
+        if (a.embed_dim != 3 && a.embed_dim != 4 && a.embed_dim != 8) { g_err = "AE embed_dim must be 3, 4 or 8 (the VQ search kernel)"; return nullptr; }
+        if (a.n_embed < 1 || (long long)a.n_embed * (a.embed_dim + 1) * 4 > 160 * 1024) {
+            g_err = "AE n_embed: the codebook and its norms, n_embed * (embed_dim + 1) * 4 bytes, must fit 160 KiB of LDS"; return nullptr;
+        }
+    }
     if (!cfg->enable_f16 && !cfg->enable_f32 && !cfg->enable_split) { g_err = "enable at least one precision"; return nullptr; }
     rs_engine* e = new rs_engine();
     e->cfg = *cfg;
