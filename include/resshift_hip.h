@@ -23,7 +23,13 @@
  *   - precision: RS_PREC_F16 = fp16 storage / fp32 accumulate MFMA, RS_PREC_F32 = fp32 storage /
  *     exact fp32 MFMA, RS_PREC_SPLIT = (hi, lo) fp16 pair storage (x = hi + lo * 2^-11, 4 bytes per
  *     element) / three fp16 MFMAs per product, fp32 accumulate: fp32-class results at 1/3 of the
- *     fp16 matrix rate (the precision that keeps the VQ codes of ldm/modules/vqvae/quantize.py:276-285).
+ *     fp16 matrix rate (the precision that keeps the VQ codes of ldm/modules/vqvae/quantize.py:276-285);
+ *   - size limit: no single working tensor that an MFMA conv, GEMM or fused attention kernel reads may reach 0xF0000000 bytes (3.75 GiB;
+ *     RS_BUFFER_BYTES_LIMIT in csrc/common.h - those kernels add 32-bit byte offsets to a buffer descriptor).  The engine finds out while
+ *     it plans the call, before anything is launched: the call returns -7 and rs_last_error() names the layer, the operand, its bytes, the
+ *     limit and the largest batch that fits that operand (faceir at 512 x 512 in split storage: 59 images per call; the realsr autoencoder at
+ *     256 x 256: 119 in split and in fp16 storage).  Chunking a larger batch is the caller's business.  Every kernel family is
+ *     tested against float64 on operands past 2^31 bytes, or past 2^31 elements (tests/test_large_tensors_gpu.py).
  */
 #ifndef RESSHIFT_HIP_H
 #define RESSHIFT_HIP_H

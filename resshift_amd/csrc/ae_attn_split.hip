@@ -53,8 +53,8 @@ __global__ __launch_bounds__(512, 2) void ae_flash_attn_split_kernel(FlashSplitP
     const f16* qz = p.q + z * (long long)T * p.ldq * 2;
     const f16* kz = p.k + z * (long long)T * p.ldk * 2;
     const f16* vz = p.vt + z * (long long)C * T * 2;
-    const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)kz, 0, (unsigned)min((long long)T * p.ldk * 4, 0xF0000000LL), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)vz, 0, (unsigned)min((long long)C * T * 4, 0xF0000000LL), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)kz, 0, (unsigned)min((long long)T * p.ldk * 4, (long long)RS_BUFFER_BYTES_LIMIT), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)vz, 0, (unsigned)min((long long)C * T * 4, (long long)RS_BUFFER_BYTES_LIMIT), 0x00020000);
 
     // K tile: LDS row rho (the MFMA row of S^T) holds key kappa(rho) = 8 ((rho & 15) >> 2) + 4 ((rho >> 4) & 1) + (rho & 3) of the block;
     // 1 KB DMA pieces = 8 LDS rows of one 32-channel stage: NST * 4 pieces, wave w owns pieces w, w + 8, ...  Position (lane & 7) of a row
@@ -211,7 +211,7 @@ extern "C" int rs_ae_flash_split_supported(int C, int T) { return C == 512 && T 
 extern "C" int rs_ae_flash_split_launch(const AeFlashCall* c, hipStream_t st) {
     const int T = c->T, C = c->C;
     if (!rs_ae_flash_split_supported(C, T) || (c->ldq & 7) || (c->ldk & 7) || (c->ldo & 3)) return -2;
-    if ((long long)T * c->ldk * 4 >= 0xF0000000LL || (long long)C * T * 4 >= 0xF0000000LL) return -2;   // 32-bit buffer offsets per image
+    if ((long long)T * c->ldk * 4 >= (long long)RS_BUFFER_BYTES_LIMIT || (long long)C * T * 4 >= (long long)RS_BUFFER_BYTES_LIMIT) return -2;   // 32-bit buffer offsets per image
     FlashSplitParams p{};
     p.q = (const f16*)c->q; p.k = (const f16*)c->k; p.vt = (const f16*)c->vt; p.bv = c->bv; p.o = (f16*)c->o;
     p.T = T; p.ldq = c->ldq; p.ldk = c->ldk; p.ldo = c->ldo; p.scale = c->scale;

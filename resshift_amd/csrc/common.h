@@ -32,6 +32,12 @@ enum RsAct { RS_ACT_NONE = 0, RS_ACT_GELU = 1, RS_ACT_SILU = 2 };
 static inline size_t rs_dtype_size(int dt) { return dt == RS_F16 ? 2 : 4; }
 static inline size_t rs_dtype_chan_bytes(int dt) { return dt == RS_F32 ? 4 : 2; }
 
+// THE size limit of an operand that a kernel reaches through a buffer descriptor plus a 32-bit per-lane BYTE offset (igemm2, igemm3, the
+// halo kernel with its folded-shortcut source, igemm_split, wino, the fused window attention kernels, the streaming AE attention): the
+// operand must be SMALLER.  The value doubles as the offset those kernels give a lane that must read zeros (beyond num_records), which is
+// why it is below 2^32.  Operands at or above it are refused by name before anything is launched (launchers.h: rs_operand_over).
+#define RS_BUFFER_BYTES_LIMIT 0xF0000000ull
+
 // pointer type of split storage: pointer arithmetic counts halfs, the lo half of element i of a pixel record sits `ld`
 // halfs after its hi half
 struct h2s { unsigned short bits; };

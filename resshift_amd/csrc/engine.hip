@@ -123,6 +123,7 @@ struct rs_engine : Model {
         d.ticket_base = (unsigned*)4096;
         arena.off = 0; arena.peak = 0;
         fn(d);
+        if (d.err) { last_launches = 0; return d.err; }   // refused while planning (Exec::fail has the text, e.g. an operand over RS_BUFFER_BYTES_LIMIT): nothing was launched
         if (d.used_split && !(cfg.enable_split && split_ok))
             return fail(!cfg.enable_split ? "split precision requested but the engine was created without enable_split"
                                           : "split precision is not available for these weights: " +

@@ -365,6 +365,20 @@ public:
         if (!rs_knob_gn_epi_stats() || (pl.kernel == CK_SPLIT && !rs_knob_gn_gen_stats()) || (sub && pl.kernel != CK_SPLIT) || spx <= 0 || (HW % spx)) return;
         ex.attach_stats(y_, (sub ? 4 : 1) * (HW / spx), y_.C);
     }
+    // The planned kernel's per-operand size limit (RS_BUFFER_BYTES_LIMIT): true, with Exec::fail, when an operand of this call reaches it.
+    // Every planned conv passes here in the dry pass (launch(); Graphs::upfold for its four launches), so the call ends before any launch.
+    bool oversize(Exec& ex) const {
+        const ConvW& w = *w_;
+        const int C1 = two_ ? x1_.C : 0;
+        if (w.direct || x_.C + C1 != w.CinP) return false;
+        std::string text;
+        const IGemmParams p = params();
+        if (!rs_conv_operand_over(std::string(), p, x_.dt, plan(), &text)) return false;   // (the layer's name is put together only for a refusal)
+        const std::string layer = ex.prefix + "conv " + std::to_string(w.KH) + "x" + std::to_string(w.KW) + " " + std::to_string(x_.C + C1) + "->" + std::to_string(w.Cout);
+        (void)rs_conv_operand_over(layer, p, x_.dt, plan(), &text);
+        ex.fail(RS_ERR_OPERAND_BYTES, text);
+        return true;
+    }
     // `shared`: the tail of a group of launches that fill ONE statistics buffer (the sub-pixel form); null: this launch draws its own
     void launch(Exec& ex, const GNTail* shared = nullptr) const {
         const ConvW& w = *w_;
@@ -386,6 +400,7 @@ public:
         const ConvPlan& pl = plan();
         // split-K for launches that cannot fill the chip (8x8 / 16x16 UNet levels): fp32 slabs live in the arena
         float* const partial = pl.splitk > 1 ? (float*)ex.raw((size_t)pl.splitk * y_.B * y_.H * y_.W * w.Cout * sizeof(float)) : nullptr;
+        if (oversize(ex)) return;   // (both passes: the dry pass ends the call before anything is launched)
         if (ex.dry) return;
         if (x_.C + C1 != w.CinP) { ex.fail(-3, "conv input channels do not match the packed weights"); return; }
         if (w.direct) {
@@ -436,7 +451,7 @@ struct Graphs {
     View upfold(Exec& ex, const ConvW (&upf)[4], const View& x, const View& y, bool stats) {
         ConvCall c0 = k3(upf[0], x, y).subpixel(0, 0);
         if (stats) c0.want_stats(ex);
-        if (ex.dry) return c0.y();
+        if (c0.oversize(ex) || ex.dry) return c0.y();   // (the four launches share x, the weights' size and the plan)
         GNTail tl{};
         if (c0.y().st) (void)ex.fill_tail(c0.y().st_prod, y.B, tl);
         for (int q = 0; q < 4; ++q) c0.sibling(upf[q], q >> 1, q & 1).launch(ex, &tl);
@@ -636,6 +651,16 @@ struct Graphs {
             const bool sstats = X.dt == RS_F16S && swin_stats_split;
             if (fuse_proj && sstats && fold2) ex.attach_stats(e2, (X.H / 8) * (X.W / 8), E);   // (only where norm2 is a coefficient-only GroupNorm: the fused MLP applies it)
             if (fuse_qkv) {
+                {   // the fused kernels' per-operand size limit (RS_BUFFER_BYTES_LIMIT), both passes: the dry pass ends the call before anything is launched
+                    std::string text;
+                    const View& xin = fold1 ? e : n;
+                    if (rs_win_attn_operand_over(std::string(), X.B, X.H, X.W, xin.ld, fuse_proj ? e.ld : 0, X.dt == RS_F16S, &text)) {
+                        (void)rs_win_attn_operand_over(ex.prefix + bp + "attn", X.B, X.H, X.W, xin.ld, fuse_proj ? e.ld : 0, X.dt == RS_F16S, &text);
+                        ex.fail(RS_ERR_OPERAND_BYTES, text);
+                        ex.reset(mk);
+                        return;
+                    }
+                }
                 if (!ex.dry) {
                     WinAttnParams p{};
                     p.bias_n = s.bias_n; p.bias_c = s.bias_c; p.B = X.B; p.H = X.H; p.W = X.W; p.heads = heads; p.shift = s.shift;

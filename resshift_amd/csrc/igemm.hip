@@ -434,6 +434,10 @@ extern "C" int rs_conv_launch(const IGemmParams* pp, int in_dt, int out_dt, int 
     if (pl->kernel == CK_NONE || (p.splitk > 1 && !p.partial)) return -2;
     if (p.ystats && !pl->stats_px) return -2;                  // this kernel cannot leave output statistics
     if (p.xcoef && pl->kernel > CK_HALO_SEG) return -2;        // only the Winograd and halo kernels apply an input transform
+    {   // the 32-bit buffer offsets of every kernel but igemm.hip's: refused by name, nothing launched
+        std::string text;
+        if (rs_conv_operand_over("conv", p, in_dt, *pl, &text)) return rs_set_last_error(text.c_str(), RS_ERR_OPERAND_BYTES);
+    }
     hipError_t e;
     switch (pl->kernel) {
         case CK_WINO: return rs_wino_launch(&p, st);

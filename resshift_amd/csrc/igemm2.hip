@@ -115,7 +115,7 @@ __global__ __launch_bounds__(4 * BP, BP == 128 ? 4 : 2) void igemm2_kernel(IGemm
     // Operands are fetched with `buffer_load_dwordx4 ... lds`: a wave-uniform buffer descriptor per operand plus a 32-bit
     // per-lane BYTE offset.  Out-of-image taps, rows beyond M / Cout and the K tail use an offset beyond num_records, for
     // which the hardware returns zeros - no zero buffer, no pointer selects, and every wave still issues exactly L loads.
-    constexpr unsigned INV = 0xF0000000u;   // > any tensor size handled here (checked by the launcher)
+    constexpr unsigned INV = (unsigned)RS_BUFFER_BYTES_LIMIT;   // > any tensor size handled here (checked by the launcher)
     constexpr unsigned SZ = sizeof(TI);
     const TI* x0 = (const TI*)p.x0 + (p.splitk > 1 ? 0 : z * p.bs_x0);
     const TI* w = (const TI*)p.w + (p.splitk > 1 ? 0 : z * p.bs_w);
@@ -390,7 +390,7 @@ hipError_t launch2_cfg(IGemmParams p, int nz, hipStream_t st) {
     }
     const size_t esz = sizeof(TI);
     const size_t xb = (size_t)p.B * p.Hs * p.Ws * p.ld0 * esz, wb = (size_t)p.Cout * p.Ktot * esz;
-    if (xb >= 0xF0000000ull || wb >= 0xF0000000ull) return hipErrorInvalidValue;  // 32-bit buffer offsets
+    if (xb >= RS_BUFFER_BYTES_LIMIT || wb >= RS_BUFFER_BYTES_LIMIT) return hipErrorInvalidValue;  // 32-bit buffer offsets
     p.x_bytes = (unsigned)xb;
     p.w_bytes = (unsigned)wb;
     { static const int dbg = (int)rs_env_int("RS_IGEMM_DBG", 0); p.dbg = dbg; }

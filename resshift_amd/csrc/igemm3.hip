@@ -49,7 +49,7 @@ __global__ __launch_bounds__(512, 2) void igemm3_kernel(IGemmParams p) {
     const int m0 = (tile / nby) * BP;
     const int n0 = (tile % nby) * BC;
 
-    constexpr unsigned INV = 0xF0000000u;   // beyond num_records: the hardware returns zeros
+    constexpr unsigned INV = (unsigned)RS_BUFFER_BYTES_LIMIT;   // beyond num_records: the hardware returns zeros
     constexpr unsigned SZ = sizeof(TI);
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x0, 0, p.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
@@ -318,7 +318,7 @@ hipError_t launch3_cfg(IGemmParams p, hipStream_t st) {
         (void)hipFuncSetAttribute((const void*)igemm3_kernel<TO, BC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     const size_t xb = (size_t)p.B * p.Hs * p.Ws * p.ld0 * 2, wb = (size_t)p.Cout * p.Ktot * 2;
-    if (xb >= 0xF0000000ull || wb >= 0xF0000000ull) return hipErrorInvalidValue;  // 32-bit buffer offsets
+    if (xb >= RS_BUFFER_BYTES_LIMIT || wb >= RS_BUFFER_BYTES_LIMIT) return hipErrorInvalidValue;  // 32-bit buffer offsets
     p.x_bytes = (unsigned)xb;
     p.w_bytes = (unsigned)wb;
     const int howo = p.Ho * p.Wo;

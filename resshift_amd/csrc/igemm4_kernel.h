@@ -183,7 +183,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void igemm4_kernel(IGemmParams p) {
         }
     };
 
-    constexpr unsigned INV = 0xF0000000u;
+    constexpr unsigned INV = (unsigned)RS_BUFFER_BYTES_LIMIT;
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x0, 0, p.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
 
@@ -1000,12 +1000,12 @@ hipError_t launch4_cfg(IGemmParams p, hipStream_t st) {
     }
     const size_t esz = SPLIT ? 4 : 2;
     const size_t xb = (size_t)p.B * p.Hs * p.Ws * p.ld0 * esz, wb = (size_t)p.Cout * p.Ktot * esz;
-    if (xb >= 0xF0000000ull || wb >= 0xF0000000ull) return hipErrorInvalidValue;  // 32-bit buffer offsets
+    if (xb >= RS_BUFFER_BYTES_LIMIT || wb >= RS_BUFFER_BYTES_LIMIT) return hipErrorInvalidValue;  // 32-bit buffer offsets
     p.x_bytes = (unsigned)xb;
     p.w_bytes = (unsigned)wb;
     if (p.sx) {   // folded 1x1 shortcut: only where the kernel carries it (see SKIPOK), whole 32-channel chunks, 16-byte rows
         const size_t sxb = (size_t)p.B * p.Hs * p.Ws * p.sld * esz, swb = (size_t)p.Cout * p.sC * esz;
-        if (SEG != 0 || NWV != 8 || sk > 1 || !p.sw || p.sC < 32 || (p.sC % 32) || (p.sld % 8) || p.sld < p.sC || sxb >= 0xF0000000ull ||
+        if (SEG != 0 || NWV != 8 || sk > 1 || !p.sw || p.sC < 32 || (p.sC % 32) || (p.sld % 8) || p.sld < p.sC || sxb >= RS_BUFFER_BYTES_LIMIT ||
             ((uintptr_t)p.sx & 15) || ((uintptr_t)p.sw & 15))
             return hipErrorInvalidValue;
         p.sx_bytes = (unsigned)sxb;

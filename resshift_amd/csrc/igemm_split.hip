@@ -66,7 +66,7 @@ __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 2 : 1) void igemm_split_kernel
     const long long z = blockIdx.z;
     const bool split = p.splitk > 1;
 
-    constexpr unsigned INV = 0xF0000000u;   // beyond num_records: the hardware returns zeros
+    constexpr unsigned INV = (unsigned)RS_BUFFER_BYTES_LIMIT;   // beyond num_records: the hardware returns zeros
     const f16* x0 = (const f16*)p.x0 + (split ? 0 : 2 * z * p.bs_x0);
     const f16* w = (const f16*)p.w + (split ? 0 : 2 * z * p.bs_w);
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)x0, 0, p.x_bytes, 0x00020000);
@@ -461,7 +461,7 @@ hipError_t launch_cfg2(IGemmParams p, int nz, hipStream_t st) {
         (void)hipFuncSetAttribute((const void*)igemm_split_kernel<TO, BP, BC, NWV, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     const size_t xb = (size_t)p.B * p.Hs * p.Ws * p.ld0 * 4, wb = (size_t)p.Cout * p.Ktot * 4;
-    if (xb >= 0xF0000000ull || wb >= 0xF0000000ull) return hipErrorInvalidValue;  // 32-bit buffer offsets
+    if (xb >= RS_BUFFER_BYTES_LIMIT || wb >= RS_BUFFER_BYTES_LIMIT) return hipErrorInvalidValue;  // 32-bit buffer offsets
     p.x_bytes = (unsigned)xb;
     p.w_bytes = (unsigned)wb;
     {

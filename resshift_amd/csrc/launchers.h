@@ -3,6 +3,46 @@
 #pragma once
 #include "common.h"
 #include "../../include/resshift_hip.h"
+#include <string>
+
+// ---- the per-operand size limit (common.h: RS_BUFFER_BYTES_LIMIT), checked by name before anything is launched
+#define RS_ERR_OPERAND_BYTES (-7)   // the code of such a refusal; rs_last_error() has the text below
+struct RsOperand { const char* name; unsigned long long bytes, per_image; };   // per_image 0: the operand does not grow with the batch (weights)
+// The first of `ops` at or above the limit, as "<layer>: operand <name> of <kernel> is <n> bytes ..."; false: all fit.  The batch it quotes
+// is what fits THIS operand: a later layer of the graph may allow less.  ONE text for the graph
+// layer (Exec::fail, in the dry pass) and for the launchers (rs_set_last_error).
+static inline bool rs_operand_over(const std::string& layer, const char* kernel, const RsOperand* ops, int n, std::string* text) {
+    for (int i = 0; i < n; ++i) {
+        if (ops[i].bytes < RS_BUFFER_BYTES_LIMIT) continue;
+        const unsigned long long fit = ops[i].per_image ? (RS_BUFFER_BYTES_LIMIT - 1) / ops[i].per_image : 0;
+        *text = layer + ": operand " + ops[i].name + " of " + kernel + " is " + std::to_string(ops[i].bytes) + " bytes; the kernel addresses it with 32-bit byte "
+                "offsets and takes operands below " + std::to_string(RS_BUFFER_BYTES_LIMIT) + " bytes (RS_BUFFER_BYTES_LIMIT); " +
+                (ops[i].per_image ? "for this operand the largest batch that fits is " + std::to_string(fit) : std::string("no batch fits: the operand does not grow with it"));
+        return true;
+    }
+    return false;
+}
+static inline const char* rs_conv_kernel_name(int k) {
+    static const char* const nm[] = {"no kernel", "wino", "igemm4 (halo)", "igemm4 (halo, small planes)", "igemm_split", "igemm3", "igemm2", "igemm"};
+    return k >= 0 && k < 8 ? nm[k] : "?";
+}
+// ... of a planned conv: the operands its kernel reaches through buffer descriptors (the launchers' own x_bytes / w_bytes / sx_bytes).  igemm.hip
+// (CK_IGEMM) addresses everything through 64-bit pointers and has no limit.
+static inline bool rs_conv_operand_over(const std::string& layer, const IGemmParams& p, int in_dt, const ConvPlan& pl, std::string* text) {
+    if (pl.kernel == CK_NONE || pl.kernel == CK_IGEMM) return false;
+    const unsigned long long esz = rs_dtype_size(in_dt), px = (unsigned long long)p.Hs * p.Ws;
+    const RsOperand ops[3] = {{"x0", px * p.B * p.ld0 * esz, px * p.ld0 * esz},
+                              {"w", pl.kernel == CK_WINO ? 0ull : (unsigned long long)p.Cout * p.Ktot * esz, 0},
+                              {"sx", p.sC > 0 ? px * p.B * p.sld * esz : 0ull, px * p.sld * esz}};
+    return rs_operand_over(layer, rs_conv_kernel_name(pl.kernel), ops, 3, text);
+}
+// ... of a fused qkv + window attention launch: the tokens and the shortcut
+// (ldres 0: none - a dry pass of the graph layer has no pointers to ask)
+static inline bool rs_win_attn_operand_over(const std::string& layer, int B, int H, int W, int ldx, int ldres, bool split, std::string* text) {
+    const unsigned long long esz = split ? 4 : 2, px = (unsigned long long)H * W;
+    const RsOperand ops[2] = {{"x", px * B * ldx * esz, px * ldx * esz}, {"res", px * B * ldres * esz, px * ldres * esz}};
+    return rs_operand_over(layer, split ? "win_attn_qkv_split" : "win_attn_qkv", ops, 2, text);
+}
 
 extern "C" {
 int rs_set_last_error(const char* text, int rc);   // engine.hip (rs_last_error's text); returns rc

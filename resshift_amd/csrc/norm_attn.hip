@@ -1109,13 +1109,16 @@ extern "C" int rs_win_attn_qkv_launch(const WinAttnParams* pp, hipStream_t st) {
     if (p.shift != 0 && p.shift != 4) return -2;
     if (p.wproj && (!p.bproj || (p.res && (p.ldres % 4)))) return -2;
     const size_t xb = (size_t)p.B * p.H * p.W * p.ldx * 2;
-    if (xb >= 0xF0000000ull) return -2;
+    {   // 32-bit buffer offsets into x and the shortcut: refused by name, nothing launched
+        std::string text;
+        if (rs_win_attn_operand_over("win_attn_qkv", p.B, p.H, p.W, p.ldx, p.res ? p.ldres : 0, false, &text)) return rs_set_last_error(text.c_str(), RS_ERR_OPERAND_BYTES);
+    }
     // two windows per workgroup wherever an image has an even number of them (RS_ATTN_NW=1: one, for A/B runs)
     static const int nw_max = (int)rs_env_int("RS_ATTN_NW", 2);
     const int nwin = (p.H / 8) * (p.W / 8);
     const int NW = (nw_max >= 2 && nwin % 2 == 0) ? 2 : 1;
     const size_t rb = p.res ? (size_t)p.B * p.H * p.W * p.ldres * 2 : 0;
-    if (rb >= 0xF0000000ull || (p.wproj && p.res && (p.ldres % 8))) return -2;
+    if (p.wproj && p.res && (p.ldres % 8)) return -2;
     // token tiles + V^T + the bias table (+ with the fused projection one residual / output tile per window)
     const size_t lds = (size_t)NW * (3 * 64 * 128 + (size_t)p.heads * 32 * (64 + 8) * sizeof(f16)) + 6144 + (p.wproj ? (size_t)NW * 3 * 64 * 128 : 0);
 #ifdef RS_SPLIT_ABLATE

@@ -500,10 +500,13 @@ extern "C" int rs_win_attn_qkv_split_launch(const WinAttnParams* pp, hipStream_t
     if (p.shift != 0 && p.shift != 4) return -2;
     if (p.wproj && (!p.bproj || (p.res && (p.ldres % 4)))) return -2;
     const size_t xb = (size_t)p.B * p.H * p.W * p.ldx * 4;
-    if (xb >= 0xF0000000ull) return -2;
+    {   // 32-bit buffer offsets into x and the shortcut: refused by name, nothing launched
+        std::string text;
+        if (rs_win_attn_operand_over("win_attn_qkv_split", p.B, p.H, p.W, p.ldx, p.res ? p.ldres : 0, true, &text)) return rs_set_last_error(text.c_str(), RS_ERR_OPERAND_BYTES);
+    }
     const int nwin = (p.H / 8) * (p.W / 8);
     const size_t rb = p.res ? (size_t)p.B * p.H * p.W * p.ldres * 4 : 0;
-    if (rb >= 0xF0000000ull || (p.wproj && p.res && (p.ldres % 8))) return -2;
+    if (p.wproj && p.res && (p.ldres % 8)) return -2;
     // token tile (hi, lo) + V^T (hi, lo) + the bias table (+ with the fused projection the residual / output tile)
     const size_t lds_max = (size_t)2 * 3 * 64 * 128 + (size_t)6 * 2 * 32 * (64 + 8) * sizeof(f16) + (6 * 1024 + 256 + 2048) + (size_t)2 * 3 * 64 * 128;
     const size_t lds = lds_max - (p.wproj ? 0 : (size_t)2 * 3 * 64 * 128);

@@ -57,7 +57,7 @@ constexpr int W_COEF = W_NBUF * W_HBUF;     // GroupNorm coefficients [2][Cin] f
 constexpr int W_MAXCIN = 640;               // coefficient table: 5 120 B
 constexpr int W_LDS = 160 * 1024;
 static_assert(W_COEF + W_MAXCIN * 8 <= W_LDS && W_COEF + 8 * 1024 <= W_LDS, "LDS");   // (the table arrives as 8 x 1 KB LDS-DMA pieces)
-constexpr unsigned W_INV = 0xF0000000u;
+constexpr unsigned W_INV = (unsigned)RS_BUFFER_BYTES_LIMIT;
 // weight fragments are requested W_DEPTH steps (6 MFMAs each) ahead: as many register slots as the accumulators leave room for
 __host__ __device__ constexpr int w_depth_of(int CF) { return CF <= 8 ? 4 : 2; }
 
@@ -559,7 +559,7 @@ extern "C" int rs_wino_launch(const IGemmParams* pp, hipStream_t st) {
     IGemmParams p = *pp;
     if (((size_t)p.x0 & 15) || ((size_t)p.y & 15) || ((size_t)p.res & 15) || ((size_t)p.ww & 15)) return -2;
     const size_t xb = (size_t)p.B * p.Hs * p.Ws * p.ld0 * 4;
-    if (xb >= 0xF0000000ull) return -2;   // 32-bit buffer offsets
+    if (xb >= RS_BUFFER_BYTES_LIMIT) return -2;   // 32-bit buffer offsets
     p.x_bytes = (unsigned)xb;
     const int CF = w_cf_of(p.Cout), nby = p.Cout / (16 * CF), per_image = (p.Ho / W_TH) * (p.Wo / W_TW);
     if (p.tail.coef) {

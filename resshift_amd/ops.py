@@ -24,6 +24,14 @@ def _prec_of(t: torch.Tensor) -> int:
     return {torch.float16: F16, torch.float32: F32, torch.int32: SPLIT}[t.dtype]
 
 
+def _out_or_new(out, shape, like):
+    """the caller's result tensor (`out=` of the wrappers that take one: contiguous, of the result's shape and the operand's storage), or a new one"""
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=like.dtype)
+    assert tuple(out.shape) == tuple(shape) and out.dtype == like.dtype and out.is_contiguous()
+    return out
+
+
 def convert(x, prec):
     """Storage conversion of an NHWC tensor [..., C] (fp16 / fp32 / split-as-int32) to `prec`."""
     lib = _lib.load()
@@ -123,7 +131,7 @@ def conv3x3_halo(x, w_ref, bias=None, coef=None, act_in=0, res=None, want_stats=
     return (y, st) if want_stats else y
 
 
-def conv3x3_wino(x, w_ref, bias=None, coef=None, act_in=0, res=None, want_stats=False, reps=0):
+def conv3x3_wino(x, w_ref, bias=None, coef=None, act_in=0, res=None, want_stats=False, reps=0, out=None):
     """Winograd F(2x2,3x3) conv (wino.hip): x [B,H,W,Cin] raw split-storage tensor (int32), coef [B,2,Cin] fp32 device (GroupNorm
     affine) applied with `act_in` (0 none / 2 SiLU) inside the kernel; returns [B,H,W,Cout] in split storage (with `want_stats` also
     the [B, H*W/128, Cout, 2] sums / sums of squares of the stored output; with reps > 0 also the average ms per launch)."""
@@ -132,7 +140,7 @@ def conv3x3_wino(x, w_ref, bias=None, coef=None, act_in=0, res=None, want_stats=
     Cout = w_ref.shape[0]
     if _prec_of(x) != 2:
         raise RuntimeError("the wino kernel takes split storage")
-    y = torch.empty(B, H, W, Cout, device=x.device, dtype=x.dtype)
+    y = _out_or_new(out, (B, H, W, Cout), x)
     wh, wp = _hostf(w_ref)
     bh, bp = _hostf(bias) if bias is not None else (None, None)
     st = torch.zeros(B, (H * W) // 128, Cout, 2, device=x.device, dtype=torch.float32) if want_stats else None
@@ -159,12 +167,14 @@ def gemm_nt(a, b, bias=None, scale=1.0, out_prec=None):
     return y
 
 
-def groupnorm(x, gamma, beta, eps, act=0, film=None, groups=32):
-    """x: [B,H,W,C]; film: optional fp32 device tensor [2C] (scale, shift)."""
+def groupnorm(x, gamma, beta, eps, act=0, film=None, groups=32, out=None):
+    """x: [B,H,W,C]; film: optional fp32 device tensor [2C] (scale, shift); out: the result's tensor.  out = x (in place) is for planes above 256 pixels only: there a
+    statistics pass ends before an elementwise apply pass starts; smaller planes run one fused kernel, for which in place is neither
+    promised nor tested."""
     lib = _lib.load()
     prec = _prec_of(x)
     B, H, W, Cc = x.shape
-    y = torch.empty_like(x)
+    y = _out_or_new(out, tuple(x.shape), x)
     gh, gp = _hostf(gamma)
     bh, bp = _hostf(beta)
     rc = lib.rs_op_groupnorm(x.data_ptr(), y.data_ptr(), gp, bp, film.data_ptr() if film is not None else None, B, H * W, Cc, groups,
@@ -185,7 +195,7 @@ def window_attention(qkv, table, heads, shift):
     return out
 
 
-def window_attention_qkv(x, wqkv, bqkv, table, heads, shift, wproj=None, bproj=None, res=None):
+def window_attention_qkv(x, wqkv, bqkv, table, heads, shift, wproj=None, bproj=None, res=None, out=None):
     """x: [B,H,W,E] fp16 normalised tokens; wqkv [3E,E], bqkv [3E]; fused projection + attention (+ output projection wproj
     [E,E], bproj [E] and shortcut `res` when given); returns [B,H,W,E]."""
     lib = _lib.load()
@@ -194,7 +204,7 @@ def window_attention_qkv(x, wqkv, bqkv, table, heads, shift, wproj=None, bproj=N
     bd = bqkv.to(x.device, torch.float32).contiguous()
     wpd = wproj.to(x.device, torch.float16).contiguous() if wproj is not None else None
     bpd = bproj.to(x.device, torch.float32).contiguous() if bproj is not None else None
-    out = torch.empty(B, H, W, E, device=x.device, dtype=torch.float16)
+    out = _out_or_new(out, (B, H, W, E), x)
     th, tp = _hostf(table)
     rc = lib.rs_op_window_attention_qkv(x.data_ptr(), wd.data_ptr(), bd.data_ptr(), wpd.data_ptr() if wpd is not None else None,
                                         bpd.data_ptr() if bpd is not None else None, res.data_ptr() if res is not None else None, out.data_ptr(),
@@ -203,7 +213,7 @@ def window_attention_qkv(x, wqkv, bqkv, table, heads, shift, wproj=None, bproj=N
     return out
 
 
-def window_attention_qkv_split(x, wqkv, bqkv, table, heads, shift, wproj=None, bproj=None, res=None, xcoef=None):
+def window_attention_qkv_split(x, wqkv, bqkv, table, heads, shift, wproj=None, bproj=None, res=None, xcoef=None, out=None):
     """split storage: x [B,H,W,E] as int32 carrier ((hi, lo) fp16 pairs); weights any float dtype (packed to (hi, lo) rows here);
     `xcoef` [B,2,E] fp32: GroupNorm affine applied to x on the fly.  Returns [B,H,W,E] split storage."""
     lib = _lib.load()
@@ -213,7 +223,7 @@ def window_attention_qkv_split(x, wqkv, bqkv, table, heads, shift, wproj=None, b
     wpd = split_pack_rows(wproj).to(x.device) if wproj is not None else None
     bpd = bproj.to(x.device, torch.float32).contiguous() if bproj is not None else None
     xc = xcoef.to(x.device, torch.float32).contiguous() if xcoef is not None else None
-    out = torch.empty(B, H, W, E, device=x.device, dtype=torch.int32)
+    out = _out_or_new(out, (B, H, W, E), x)
     th, tp = _hostf(table)
     rc = lib.rs_op_window_attention_qkv_split(x.data_ptr(), wd.data_ptr(), bd.data_ptr(), wpd.data_ptr() if wpd is not None else None,
                                               bpd.data_ptr() if bpd is not None else None, res.data_ptr() if res is not None else None,
